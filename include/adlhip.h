@@ -138,7 +138,9 @@ int adlhip_unmap(adlhip_device* dev, void* dptr, void* hptr, size_t bytes);
  *                 suffices for EVERY n' <= n with the current knobs (the need of a single n is not monotone:
  *                 smaller inputs use smaller tiles and so more status rows), so a caller may size its scratch
  *                 once for its largest batch; changing "sort.tile", "sort.digit_bits" or "sort.algo" later can
- *                 raise the requirement (the sort entry points re-check and fail loudly). */
+ *                 raise the requirement (the sort entry points re-check and fail loudly).
+ * Data, tmp and work buffers of the sorts and partitions need 16-byte alignment and no more; a pointer that is not
+ * 16-byte aligned is refused before anything is enqueued.  The work buffer's contents on entry are arbitrary. */
 int adlhip_radix_sort_scratch_bytes(adlhip_device* dev, int elem_kind, size_t n,
                                     size_t* tmp_bytes, size_t* work_bytes);
 

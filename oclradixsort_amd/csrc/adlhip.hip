@@ -1627,7 +1627,7 @@ size_t sort_work_bytes_at(const adlhip_device* d, int elem_kind, size_t n, int s
     if (n > kMsd2Min && sort_bits >= 16) {
         if (level == 2) {   // lean: whole keys keep the cursor form with little head-room, pairs and partial sorts the stable form
             if (keys && whole && n <= (eb == 4 ? kMsd2MaxU32 : kMsd2MaxU64)) e = msd2_layout(n, eb, kLeanHeadroomPct).total;
-            else if (n <= kMsd2sMax) e = msd2s_layout(n, eb, false, true).total;
+            else if (n <= kMsd2sMax) e = msd2s_layout(n, eb, eb == 4 && whole, true).total;   // as msd2s_sort (test_gpu_memory_contract.py sweep)
         } else {
             if (n <= kMsd2sMax) e = msd2s_layout(n, eb, eb == 4 && whole).total;
             if (keys && whole && n <= (eb == 4 ? kMsd2MaxU32 : kMsd2MaxU64)) e = std::max(e, msd2_layout(n, eb).total);
@@ -1684,7 +1684,7 @@ int check_sort_args(adlhip_device* d, int elem_kind, const void* a, const void* 
     if (n > kMaxElems) return fail("n = %zu exceeds the supported maximum %zu", n, (size_t)kMaxElems);
     if (n == 0) return ADLHIP_SUCCESS;
     if (!a || !b || !work) return fail("null buffer passed to radix sort");
-    if ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) & 15u)
+    if ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(work)) & 15u)
         return fail("sort buffers must be 16-byte aligned");
     const size_t need = sort_work_bytes(d, elem_kind, n, sort_bits, 0);
     if (work_bytes < need)
@@ -1732,7 +1732,8 @@ int sort_entry(adlhip_device* d, int elem_kind, E* data, E* tmp, void* work, siz
         } else if (cursor_ok && msd2_layout(n, sizeof(E), kLeanHeadroomPct).total <= work_bytes) {
             form = kLargeCursor;
             headroom = kLeanHeadroomPct;
-        } else if (n <= kMsd2sMax && msd2s_layout(n, sizeof(E), false, true).total <= work_bytes) {
+        } else if (n <= kMsd2sMax && msd2s_layout(n, sizeof(E), sizeof(E) == 4 && whole, true).total <= work_bytes) {
+            // (the layout msd2s_sort takes: whole u32 keys have the 16-bit second slab; tests/test_gpu_memory_contract.py in-between sweep)
             form = kLargeStable;   // pairs, partial sorts: the stable form with statistical head-room only
             lean_stable = true;
         } else {
@@ -1769,7 +1770,8 @@ int partition_top_byte(adlhip_device* d, const E* in, E* out, void* work, size_t
     if (!in || !out) return fail("null buffer");
     const size_t need = work_bytes_three_kernel(d, n);
     if (work_bytes < need || !work) return fail("work buffer too small: %zu < %zu", work_bytes, need);
-    if ((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(out)) & 15u) return fail("buffers must be 16-byte aligned");
+    if ((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(work)) & 15u)
+        return fail("buffers must be 16-byte aligned");
     // From 24 MiB of data, and with a work buffer of the sort's full-speed size: ONE look-back pass on the top byte -- the one-sweep
     // path's histogram, tables and chain kernel with a one-pass plan -- instead of count -> scan -> scatter: the keys are read twice
     // instead of three times and there is no table scan (64 Mi keys: 0.26 -> ~0.19 ms).  Both are stable: the same output, bit for bit.
