@@ -360,6 +360,15 @@ int adlhip_generate_keys(adlhip_device* dev, int elem_kind, void* dptr, size_t n
  *                      on this handle, and how often it sorted by counting
  *   "debug.net_stamp0" .. "debug.net_stamp9" (read-only, diagnostic) when workgroup 0 of the handle's last safety net reached its
  *                      phase boundaries, 10-ns ticks (tools/net_phases.py)
+ *   "debug.idle_dirty" (read-only, diagnostic; reading waits for the stream) how many of the handle-owned device words that have an
+ *                      idle value -- cursors, flags, counters and sample words of the large sort, histograms and cursors of the
+ *                      mid-size sort, the padding of the dictionary block, the fault words (adlhip.hip kIdleTable, DESIGN.md
+ *                      "Idle state of a handle") -- do not hold it.  0 whenever the stream is drained, whatever ran before.  Copies
+ *                      the areas to the host; launches nothing and changes nothing on the device
+ *   "debug.idle_first" (read-only) the first such word as region << 24 | word (regions: 1 the large sort's words, 2 the mid-size
+ *                      sort's, 3 the dictionary block, 4 the fault words); 0 when clean
+ *   "debug.idle_poke"  (set-only; tests) region << 24 | word: flips bit 0 of that word in stream order -- the positive control of
+ *                      "debug.idle_dirty"; a second poke undoes the first
  *   "debug.resident_wgs" workgroups the device certainly keeps resident at once (asked of the runtime at creation); the
  *                      paths whose safety nets hold a grid-wide barrier over 256 workgroups are taken only when it is
  *                      >= 256.  Setting it stands in for a small partition (tests); 0 = ask the device again

@@ -112,9 +112,9 @@ struct adlhip_device {
     int dict_path = 1;                      // "sort.dict": the large sort's safety net first tries the counting sort for keys that take at most
                                             // 256 values (dict_kernels.hpp); 0 = off
     adlhip::DictBlock* d_dict = nullptr;    // its dictionary and counters (handle-owned; rebuilt by every net that uses them)
-    uint32_t* d_msd2 = nullptr;   // the large sort's handle-owned words, allocated with the handle and idle between sorts: cursors of
-                                  // pass 1 (256, one 128-byte line each) and pass 2 (65536), overflow flag, done counter, the safety
-                                  // net's barrier counter, the four sample words
+    uint32_t* d_msd2 = nullptr;   // the large sort's handle-owned words, allocated with the handle: cursors of pass 1 (256, one
+                                  // 128-byte line each) and pass 2 (65536), overflow flag, done counter, the safety net's barrier
+                                  // counter, the four sample words, ...; what each holds between sorts: kIdleTable
     // profiling
     std::vector<PendingProf> pending;
     std::vector<hipEvent_t> event_pool;
@@ -131,7 +131,8 @@ struct adlhip_device {
     uint32_t* h_fault = nullptr;   // pinned: [0..1] filled by adlhip_sync, [4] by the last adlhip_fault_check snapshot
     hipEvent_t fault_snap = nullptr;   // recorded behind the last snapshot copy; null = none pending
     uint32_t* d_mid_hist = nullptr;    // [16][4][256] slice histograms of the mid-size sort + 512 words of bucket cursors / flags
-                                       // of its keys-only form (hybrid_kernels.hpp SegSlab): zero between sorts
+                                       // of its keys-only form (hybrid_kernels.hpp SegSlab): zero between sorts, but for the
+                                       // barrier counter its first kernel clears (kIdleTable)
 };
 
 namespace {
@@ -1068,6 +1069,121 @@ uint32_t net_wgs(const adlhip_device* d) { return d->resident_wgs >= (int)kNetWg
 constexpr size_t kMsd2Words = 8192 + 65536 + 64;
 uint32_t* net_stats(const adlhip_device* d) { return d->d_msd2 + 8192 + 65536 + 16; }
 
+// ---- what the handle-owned device words hold between sorts ("debug.idle_dirty"; DESIGN.md "Idle state of a handle") ----
+// Every word of d_msd2, d_mid_hist, d_dict and d_fault[0..15] is one of three kinds:
+//   kIdleValue     holds `value` whenever the stream is drained: whoever changes it puts it back before its sort ends, on every exit
+//   kResetOnEntry  any value: the named kernel writes it before anything of the same sort reads it
+//   kFreeRunning   counters and time stamps that only ever move on
+// The ranges tile each region completely (idle_table_tiles, checked at compile time).  Words no kernel touches are kIdleValue 0:
+// the areas are zeroed with the handle, so a stray store into them shows.
+enum IdleRegion { kRegionMsd2 = 1, kRegionMidHist = 2, kRegionDict = 3, kRegionFault = 4, kIdleRegions = 4 };
+enum IdleKind { kIdleValue, kResetOnEntry, kFreeRunning };
+constexpr uint32_t kMsd2Flag = 8192 + 65536;                       // flag = d_msd2 + kMsd2Flag
+constexpr uint32_t kMidHistWords = 16 * 1024 + 8192 + 64;
+constexpr uint32_t kMidState = 16 * 1024;                          // SegSlab::state = d_mid_hist + kMidState
+constexpr uint32_t kDictSmallWords = (uint32_t)(sizeof(adlhip::DictBlock) / 4);
+constexpr uint32_t kDictWords = (uint32_t)((sizeof(adlhip::DictBlock) + sizeof(adlhip::BigDictBlock)) / 4);
+constexpr uint32_t kFaultWords = 16;
+static_assert(adlhip::kSampleRepeatsWord == 12 && adlhip::kSampleArriveWord == 13 && adlhip::kSampleThresholdWord == 14, "the idle table below");
+struct IdleRange {
+    int region;
+    uint32_t first, count;
+    IdleKind kind;
+    uint32_t value;      // kIdleValue only
+    const char* what;    // the word's role; who restores it (kIdleValue) or who writes it first (kResetOnEntry)
+};
+constexpr IdleRange kIdleTable[] = {
+    // d_msd2: the large sort
+    {kRegionMsd2, 0, 8192, kIdleValue, 0u, "first-pass cursors [32 * b]: last workgroup of msd2_offsets_kernel"},
+    {kRegionMsd2, 8192, 65536, kIdleValue, 0u, "second-pass cursors (cursor and hybrid forms): msd2_offsets_kernel / msd2s_offsets_kernel, each its own bucket's"},
+    {kRegionMsd2, kMsd2Flag + 0, 1, kIdleValue, 0u, "flag[0] overflow flag: last workgroup of msd2_offsets_kernel / msd2s_offsets_kernel"},
+    {kRegionMsd2, kMsd2Flag + 1, 1, kIdleValue, 0u, "flag[1] done counter: last workgroup of msd2_offsets_kernel / msd2s_offsets_kernel"},
+    {kRegionMsd2, kMsd2Flag + 2, 1, kResetOnEntry, 0u, "flag[2] the net's grid-barrier counter: msd2_sample_kernel / msd2s_prep_kernel"},
+    {kRegionMsd2, kMsd2Flag + 3, 5, kIdleValue, 0u, "flag[3..7] unused"},
+    {kRegionMsd2, kMsd2Flag + 8, 2, kIdleValue, 0u, "flag[8..9] sample OR words: last workgroup of msd2_offsets_kernel / last arrival of msd2s_prep_kernel"},
+    {kRegionMsd2, kMsd2Flag + 10, 2, kIdleValue, ~0u, "flag[10..11] sample AND words: last workgroup of msd2_offsets_kernel / last arrival of msd2s_prep_kernel"},
+    {kRegionMsd2, kMsd2Flag + 12, 1, kIdleValue, 0u, "flag[12] sample repeats: last workgroup of msd2_offsets_kernel / msd2s_offsets_kernel"},
+    {kRegionMsd2, kMsd2Flag + 13, 1, kIdleValue, 0u, "flag[13] arrivals: last arrival of msd2s_prep_kernel"},
+    {kRegionMsd2, kMsd2Flag + 14, 1, kResetOnEntry, 0u, "flag[14] repeat threshold: msd2_sample_kernel / msd2s_prep_kernel"},
+    {kRegionMsd2, kMsd2Flag + 15, 1, kIdleValue, 0u, "flag[15] unused"},
+    {kRegionMsd2, kMsd2Flag + 16, 2, kFreeRunning, 0u, "flag[16..17] nets run / sorted by counting (stat.net_runs, stat.net_counting)"},
+    {kRegionMsd2, kMsd2Flag + 18, 2, kIdleValue, 0u, "flag[18..19] unused"},
+    {kRegionMsd2, kMsd2Flag + 20, 10, kFreeRunning, 0u, "flag[20..29] the last net's time stamps (debug.net_stamp0..9)"},
+    {kRegionMsd2, kMsd2Flag + 30, 34, kIdleValue, 0u, "flag[30..63] unused"},
+    // d_mid_hist: the mid-size sort
+    {kRegionMidHist, 0, 16 * 1024, kIdleValue, 0u, "slice histograms [16][4][256]: last workgroup of mid_prep_kernel"},
+    {kRegionMidHist, kMidState, 8192, kIdleValue, 0u, "two-launch form's bucket cursors [32 * b]: last reader in segment_sort_kernel"},
+    {kRegionMidHist, kMidState + 8192, 2, kIdleValue, 0u, "two-launch form's overflow word and reader counter: last reader in segment_sort_kernel"},
+    {kRegionMidHist, kMidState + 8194, 1, kResetOnEntry, 0u, "two-launch form's grid-barrier counter: msd_bucket_scatter_kernel (zero_me)"},
+    {kRegionMidHist, kMidState + 8195, 61, kIdleValue, 0u, "unused"},
+    // d_dict: the net's dictionaries, rebuilt by every net that reads them
+    {kRegionDict, 0, 2, kResetOnEntry, 0u, "n_values, miss: dict_sample_build / dict_sample_build_pair_keys (workgroup 0 of the net, before its first barrier)"},
+    {kRegionDict, 2, 2, kIdleValue, 0u, "pad"},
+    {kRegionDict, 4, kDictSmallWords - 4, kResetOnEntry, 0u, "value, slots, count[]: dict_sample_build / dict_sample_build_pair_keys"},
+    {kRegionDict, kDictSmallWords + 0, 2, kResetOnEntry, 0u, "large dictionary's n_values, miss: big_dict_build"},
+    {kRegionDict, kDictSmallWords + 2, 2, kIdleValue, 0u, "pad"},
+    {kRegionDict, kDictSmallWords + 4, kDictWords - kDictSmallWords - 4, kResetOnEntry, 0u, "large dictionary's value, slots: big_dict_build; count[]: big_dict_sample"},
+    // d_fault
+    {kRegionFault, 0, 1, kResetOnEntry, 0u, "live fault word: the first kernel of every sort whose kernels wait on one another"},
+    {kRegionFault, 1, 1, kIdleValue, 0u, "sticky fault word: zero once the host has collected the report (report_fault)"},
+    {kRegionFault, 2, 6, kIdleValue, 0u, "unused"},
+    {kRegionFault, 8, 1, kResetOnEntry, 0u, "self-test result: run_lds_order_selftest's own memset"},
+    {kRegionFault, 9, 3, kIdleValue, 0u, "unused (h_fault[9], h_fault[10] are the mid-size forms' pinned reports)"},
+    {kRegionFault, 12, 1, kIdleValue, 0u, "mid_prep_kernel's arrival counter: its last workgroup"},
+    {kRegionFault, 13, 1, kResetOnEntry, 0u, "three-launch form's grid-barrier counter: last workgroup of mid_prep_kernel"},
+    {kRegionFault, 14, 2, kIdleValue, 0u, "unused"},
+};
+constexpr uint32_t idle_region_words(int region)
+{
+    return region == kRegionMsd2 ? (uint32_t)kMsd2Words : region == kRegionMidHist ? kMidHistWords : region == kRegionDict ? kDictWords
+         : region == kRegionFault ? kFaultWords : 0u;
+}
+constexpr bool idle_table_tiles()
+{
+    int region = 0;
+    uint32_t next = 0;
+    for (const IdleRange& r : kIdleTable) {
+        if (r.region != region) {
+            if (region && next != idle_region_words(region)) return false;
+            if (r.region != region + 1) return false;
+            region = r.region;
+            next = 0;
+        }
+        if (r.first != next || r.count == 0) return false;
+        next += r.count;
+    }
+    return region == kIdleRegions && next == idle_region_words(region);
+}
+static_assert(idle_table_tiles(), "kIdleTable must classify every handle-owned word exactly once, regions in order");
+uint32_t* idle_region_base(const adlhip_device* d, int region)
+{
+    return region == kRegionMsd2 ? d->d_msd2 : region == kRegionMidHist ? d->d_mid_hist
+         : region == kRegionDict ? reinterpret_cast<uint32_t*>(d->d_dict) : region == kRegionFault ? d->d_fault : nullptr;
+}
+
+// "debug.idle_dirty" / "debug.idle_first": drain the stream, copy the four areas to the host, compare the kIdleValue words.  Launches
+// nothing and writes nothing on the device.
+int idle_check(adlhip_device* d, uint32_t* dirty, uint32_t* first)
+{
+    if (bind(d)) return ADLHIP_FAILURE;
+    HIPCHK(hipStreamSynchronize(d->stream));
+    std::vector<uint32_t> host;
+    *dirty = *first = 0u;
+    for (int region = 1; region <= kIdleRegions; ++region) {
+        host.resize(idle_region_words(region));
+        HIPCHK(hipMemcpyAsync(host.data(), idle_region_base(d, region), host.size() * 4, hipMemcpyDeviceToHost, d->stream));
+        HIPCHK(hipStreamSynchronize(d->stream));
+        for (const IdleRange& r : kIdleTable) {
+            if (r.region != region || r.kind != kIdleValue) continue;
+            for (uint32_t w = r.first; w < r.first + r.count; ++w)
+                if (host[w] != r.value && (*dirty)++ == 0u) *first = ((uint32_t)region << 24) | w;
+        }
+    }
+    return ADLHIP_SUCCESS;
+}
+
+__global__ void idle_poke_kernel(uint32_t* word) { *word ^= 1u; }
+
 // Repeats the sort's first kernel must count among its samples (hybrid_kernels.hpp sample_accumulate: 16 waves, each comparing
 // its own 128 samples) to call the keys too repetitive for the slabs: D distinct values, each with n / D copies, repeat
 // 16 (128 - D (1 - e^(-128/D))) times; taken at D = n / 3072 (twice what a segment slab of ~1500 holds), with 20 % off for the
@@ -1954,7 +2070,8 @@ int adlhip_selftest_probe_positions(adlhip_device* d, size_t n, uint32_t* max_in
     if (bind(d)) return ADLHIP_FAILURE;
     if (!max_index || !out_of_cell) return fail("null out pointer");
     if (n < 16384 || n > kMaxElems) return fail("selftest: n must be in [16384, %zu]", (size_t)kMaxElems);
-    // two words of the dictionary block's count[] (idle between sorts: zero) serve as the result
+    // two words of the dictionary block's count[] serve as the result (free between sorts: a net that uses the dictionary clears
+    // count[] before it counts, kIdleTable)
     uint32_t* res = d->d_dict->count;
     HIPCHK(hipMemsetAsync(res, 0, 8, d->stream));
     int rc = launch(d, "probe_positions_selftest", [&] {
@@ -2603,6 +2720,15 @@ int adlhip_set_param(adlhip_device* d, const char* name, int value)
         // 0 = ask the device again.  Tests use it to stand in for a small partition.
         if (value < 0) return fail("debug.resident_wgs must be >= 0");
         d->resident_wgs = value ? value : d->resident_wgs_device;
+    } else if (!strcmp(name, "debug.idle_poke")) {
+        // the idle checker's positive control: flips bit 0 of one handle-owned word, in stream order (a second poke undoes it)
+        const int region = (int)((uint32_t)value >> 24);
+        const uint32_t word = (uint32_t)value & 0xffffffu;
+        if (region < 1 || region > kIdleRegions || word >= idle_region_words(region))
+            return fail("debug.idle_poke: no word %u in region %d (region << 24 | word; regions 1 d_msd2, 2 d_mid_hist, 3 d_dict, 4 d_fault)", word, region);
+        if (bind(d)) return ADLHIP_FAILURE;
+        hipLaunchKernelGGL(idle_poke_kernel, dim3(1), dim3(1), 0, d->stream, idle_region_base(d, region) + word);
+        HIPCHK(hipGetLastError());
     } else if (!strcmp(name, "sort.rank")) {
         if (value != 0 && value != 1) return fail("sort.rank must be 0 or 1");
         if (value == 1 && !d->lds_ordered) return fail("sort.rank = 1 needs lane-ordered DS atomics; the device self-test failed");
@@ -2638,6 +2764,13 @@ int adlhip_get_param(adlhip_device* d, const char* name, int* value)
         HIPCHK(hipMemcpyAsync(v, net_stats(d), 8, hipMemcpyDeviceToHost, d->stream));
         HIPCHK(hipStreamSynchronize(d->stream));
         *value = (int)v[name[9] == 'c' ? 1 : 0];
+    }
+    else if (!strcmp(name, "debug.idle_dirty") || !strcmp(name, "debug.idle_first")) {
+        // handle-owned words that are not at their idle value (kIdleTable), and the first of them as region << 24 | word (0 = clean);
+        // waits for the stream, changes nothing on the device
+        uint32_t dirty = 0u, first = 0u;
+        if (idle_check(d, &dirty, &first)) return ADLHIP_FAILURE;
+        *value = (int)(name[11] == 'd' ? dirty : first);
     }
     else if (!strncmp(name, "debug.net_stamp", 15) && name[15] >= '0' && name[15] <= '9' && !name[16]) {
         // diagnostic: when workgroup 0 of the last net reached its k-th phase boundary, in 10-ns ticks (low 31 bits; tools/net_phases.py)

@@ -20,7 +20,7 @@ struct DictBlock {                                  // handle-owned device memor
     unsigned long long value[kDictMax];             // ascending
     unsigned long long slot_key[kDictSlots];        // hash table: key (kDictEmpty = free) ...
     uint32_t slot_idx[kDictSlots];                  // ... -> its index in value[]
-    uint32_t count[kDictMax];                       // per value; cleared by the workgroup that builds the dictionary
+    uint32_t count[kDictMax];                       // per value; any value between sorts: the workgroup that builds the dictionary clears it first
 };
 
 __device__ __forceinline__ uint32_t dict_hash(unsigned long long v)

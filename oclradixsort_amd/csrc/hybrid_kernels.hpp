@@ -549,7 +549,9 @@ __device__ __forceinline__ void net_sort(E* data, E* tmp, uint32_t n, uint32_t* 
 // Keys-only mid-size sort (two launches): the segments are the 256 bucket SLABS msd_bucket_scatter_kernel filled --
 // bucket b occupies slab[b * stride, b * stride + state[b]) -- and go to out[sum of the counts before b ...).
 // state: bucket cursors = counts at [32 * b] (one 128-byte line each), [8192] overflow word, [8193] readers-done counter,
-// [8194] grid-barrier counter; handle-owned, zero between sorts: the last workgroup to have read it clears it.
+// [8194] grid-barrier counter; handle-owned.  Cursors, overflow word and reader counter are zero between sorts: the last workgroup
+// to have read them clears them.  The barrier counter holds any value between sorts: the scatter kernel, the sort's first, clears it
+// (BucketPass::zero_me; adlhip.hip kIdleTable).
 struct SegSlab {
     uint32_t* state;      // nullptr: ordinary segment list
     uint32_t stride;
