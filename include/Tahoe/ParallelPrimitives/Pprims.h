@@ -5,6 +5,7 @@
 //   radixSort u32 keys                                               (reference Pprims.h:41)
 //   radixSort u64 keys                                               (new: BASELINE config #5)
 //   copy / fill                                                      (reference Pprims.cpp:31-120, commented out there)
+//   sortKeys / argsort  signed, float and descending keys            (new: adlhip_sort_keys_typed / adlhip_argsort_typed)
 // Same argument meaning; differences, all supersets: any n >= 0 (the reference needs n % 256 == 0 for
 // keys), scan has no 1,048,576-element limit, sortBits < 32 also works on 64-bit keys up to 64.
 // Device work is enqueued and the call returns (no sync), as in the reference's GPU branches.
@@ -66,7 +67,27 @@ public:
     void radixSort(const adl::Device* device, const adl::Buffer<u64>& keys, const adl::Buffer<u64>& values, int n,
                    int sortBits = 64);
 
+    // typed keys (no reference counterpart): signed integers by value, floats in IEEE-754 totalOrder (-NaN < -inf < ... < -0 < +0
+    // < ... < +inf < +NaN), ascending or descending, in place.  A TYPE_HOST device sorts on the CPU (std::stable_sort on the same
+    // order, src/TypedSort.cpp)
+    void sortKeys(const adl::Device* device, const adl::Buffer<int>& inout, int n, bool descending = false);
+    void sortKeys(const adl::Device* device, const adl::Buffer<float>& inout, int n, bool descending = false);
+    void sortKeys(const adl::Device* device, const adl::Buffer<long long>& inout, int n, bool descending = false);
+    void sortKeys(const adl::Device* device, const adl::Buffer<double>& inout, int n, bool descending = false);
+    void sortKeys(const adl::Device* device, const adl::Buffer<u32>& inout, int n, bool descending = false);
+    void sortKeys(const adl::Device* device, const adl::Buffer<u64>& inout, int n, bool descending = false);
+    // indexOut[j] = position in keys of the j-th element of the sorted order; stable (equal keys in input order, descending too);
+    // keys is left intact
+    void argsort(const adl::Device* device, const adl::Buffer<int>& keys, adl::Buffer<u32>& indexOut, int n, bool descending = false);
+    void argsort(const adl::Device* device, const adl::Buffer<float>& keys, adl::Buffer<u32>& indexOut, int n, bool descending = false);
+    void argsort(const adl::Device* device, const adl::Buffer<long long>& keys, adl::Buffer<u32>& indexOut, int n, bool descending = false);
+    void argsort(const adl::Device* device, const adl::Buffer<double>& keys, adl::Buffer<u32>& indexOut, int n, bool descending = false);
+    void argsort(const adl::Device* device, const adl::Buffer<u32>& keys, adl::Buffer<u32>& indexOut, int n, bool descending = false);
+    void argsort(const adl::Device* device, const adl::Buffer<u64>& keys, adl::Buffer<u32>& indexOut, int n, bool descending = false);
+
 private:
+    template <typename T> void sortKeysTyped(const adl::Device* device, const adl::Buffer<T>& inout, int n, bool descending);
+    template <typename T> void argsortTyped(const adl::Device* device, const adl::Buffer<T>& keys, adl::Buffer<u32>& indexOut, int n, bool descending);
     // device scratch owned by the object and grown lazily (reference: m_u32WorkBuffer[0] = ping-pong data,
     // m_u32WorkBuffer[1] = histogram table; Pprims.h:44-45)
     void reserve(const adl::Device* device, size_t tmpBytes, size_t workBytes);

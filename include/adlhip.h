@@ -201,6 +201,64 @@ int adlhip_radix_sort_soa(adlhip_device* dev, void* d_keys_inout, int key_bytes,
 int adlhip_radix_sort_u64(adlhip_device* dev, uint64_t* d_keys_inout, uint64_t* d_tmp,
                           void* d_work, size_t work_bytes, size_t n, int sort_bits);
 
+/* ---- typed keys, order, argsort (no reference counterpart) ----------------------------------- */
+
+/* The sorts above order unsigned bit patterns, ascending -- all the reference has (Pprims.h:38-41).  These entry points sort signed
+ * integers, IEEE-754 floats and descending orders with the same kernels, through an order-preserving bijection between a typed key
+ * and an unsigned key of the same width (integer instructions only):
+ *   unsigned: identity;  signed: the sign bit flipped;  float: bits ^ (sign set ? all ones : sign bit);  descending: the complement.
+ * Floats sort in IEEE-754 totalOrder: -NaN < -inf < ... < -denormal < -0 < +0 < +denormal < ... < +inf < +NaN, NaNs of one sign by
+ * payload.  So -0 sorts before +0, and NaNs whose sign bit is set come FIRST, not last (descending: the mirror image).  Every sort
+ * below is stable: equal keys keep their input order, also descending (torch.sort(descending=True, stable=True) does the same). */
+#define ADLHIP_KEY_U32 0
+#define ADLHIP_KEY_I32 1
+#define ADLHIP_KEY_F32 2
+#define ADLHIP_KEY_U64 3
+#define ADLHIP_KEY_I64 4
+#define ADLHIP_KEY_F64 5
+
+#define ADLHIP_ORDER_ASCENDING  0
+#define ADLHIP_ORDER_DESCENDING 1
+
+/* The codec alone (no reference counterpart): d_dst[i] = enc(d_src[i]) for i < n, so that unsigned ascending order of the encoded keys
+ * is the requested order of the typed ones; adlhip_key_decode is the exact inverse -- every bit pattern round-trips, NaN payloads and
+ * -0 included.  d_dst may equal d_src; both 16-byte aligned.  One streaming sweep (read n keys, write n keys); U32 / U64 ascending is
+ * the identity and copies (nothing at all when d_dst == d_src).  For callers that feed encoded keys to the unsigned entry points
+ * themselves (partial-bit sorts, partitions, the sharded sort). */
+int adlhip_key_encode(adlhip_device* dev, int key_type, int order, void* d_dst, const void* d_src, size_t n);
+int adlhip_key_decode(adlhip_device* dev, int key_type, int order, void* d_dst, const void* d_src, size_t n);
+
+/* Scratch of the three typed sorts below (no reference counterpart).  mode 0 = keys only (adlhip_sort_keys_typed: *tmp_keys_bytes is its
+ * d_tmp), 1 = pairs (value_bytes: 4, 8 or 16; *tmp_keys_bytes is 0 for 4-byte keys, which need no partner array), 2 = argsort (no
+ * partner arrays; value_bytes is ignored).  Unlike the unsigned sorts, the typed entry points REFUSE a work buffer below
+ * *work_bytes instead of taking a slower path. */
+int adlhip_sort_typed_scratch_bytes(adlhip_device* dev, int key_type, int mode, int value_bytes, size_t n,
+                                    size_t* tmp_keys_bytes, size_t* tmp_vals_bytes, size_t* work_bytes);
+
+/* Sorts n typed keys in place (no reference counterpart): encode in place -> adlhip_radix_sort_u32 / _u64 on whole keys -> decode in
+ * place.  Cost: two streaming sweeps of n keys (read + write each) on top of the unsigned sort; U32 / U64 ascending launch no codec
+ * kernel and cost what adlhip_radix_sort_u32 / _u64 cost.  NaN and -0 order: above.  d_tmp: n keys.  Enqueues and returns.
+ * If the unsigned sort refuses after the encode has been enqueued (knobs changed since the scratch was sized: "sort.algo" = 0 or
+ * "sort.digit_bits" = 7 with a work buffer that does not hold the one-sweep path), the decode is enqueued all the same: the call
+ * fails with the sort's message and the keys are what they were, unsorted. */
+int adlhip_sort_keys_typed(adlhip_device* dev, int key_type, int order, void* d_keys_inout, void* d_tmp,
+                           void* d_work, size_t work_bytes, size_t n);
+
+/* Sorts n typed keys and their values of 4, 8 or 16 bytes in place, stably (no reference counterpart; NaN and -0 order: above).
+ * Like adlhip_radix_sort_soa with wide values it sorts {32 encoded key bits, source index} pairs -- once for 4-byte keys, twice for
+ * 8-byte keys -- and fetches keys and values once, at the end; the codec sits inside the pack and gather kernels that path runs
+ * anyway, so typed pairs cost NO sweep on top of the unsigned path.  (4-byte key, 4-byte value) takes this path too.
+ * d_tmp_keys: n keys (may be NULL for 4-byte keys), d_tmp_vals: n values.  n < 2^32.  Enqueues and returns. */
+int adlhip_sort_pairs_typed(adlhip_device* dev, int key_type, int order, void* d_keys_inout, void* d_vals_inout, int value_bytes,
+                            void* d_tmp_keys, void* d_tmp_vals, void* d_work, size_t work_bytes, size_t n);
+
+/* Argsort (no reference counterpart; NaN and -0 order: above): d_keys_in is left intact; d_index_out[j] = position in the input of the
+ * j-th element of the sorted order (stable: equal keys appear with ascending positions, descending too); d_keys_out_or_null receives
+ * the sorted keys when given (it must not be d_keys_in).  The same index sort as adlhip_sort_pairs_typed, written straight to the
+ * caller's arrays: no codec sweep, no copy back.  n < 2^32.  Enqueues and returns. */
+int adlhip_argsort_typed(adlhip_device* dev, int key_type, int order, const void* d_keys_in, void* d_keys_out_or_null,
+                         uint32_t* d_index_out, void* d_work, size_t work_bytes, size_t n);
+
 /* ---- segments finished in LDS (no reference counterpart) ------------------------------------- */
 
 /* Sorts, stably and in place, every segment [d_seg_start[s], d_seg_start[s + 1]) of an array of u32 keys

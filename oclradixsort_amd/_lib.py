@@ -64,6 +64,12 @@ SIGNATURES = {
     "adlhip_radix_sort_u64": (_I, [_VP, _VP, _VP, _VP, _SZ, _SZ, _I]),
     "adlhip_radix_sort_soa_scratch_bytes": (_I, [_VP, _I, _I, _SZ, _I, c_size_p, c_size_p, c_size_p]),
     "adlhip_radix_sort_soa": (_I, [_VP, _VP, _I, _VP, _I, _VP, _VP, _VP, _SZ, _SZ, _I]),
+    "adlhip_key_encode": (_I, [_VP, _I, _I, _VP, _VP, _SZ]),
+    "adlhip_key_decode": (_I, [_VP, _I, _I, _VP, _VP, _SZ]),
+    "adlhip_sort_typed_scratch_bytes": (_I, [_VP, _I, _I, _I, _SZ, c_size_p, c_size_p, c_size_p]),
+    "adlhip_sort_keys_typed": (_I, [_VP, _I, _I, _VP, _VP, _VP, _SZ, _SZ]),
+    "adlhip_sort_pairs_typed": (_I, [_VP, _I, _I, _VP, _VP, _I, _VP, _VP, _VP, _SZ, _SZ]),
+    "adlhip_argsort_typed": (_I, [_VP, _I, _I, _VP, _VP, _VP, _VP, _SZ, _SZ]),
     "adlhip_segment_sort": (_I, [_VP, _I, _VP, _VP, _SZ, _SZ, _I]),
     "adlhip_scan_scratch_bytes": (_I, [_VP, _SZ, c_size_p]),
     "adlhip_exclusive_scan_u32": (_I, [_VP, _VP, _VP, _VP, _SZ, _SZ, _VP]),

@@ -24,6 +24,7 @@
 #include "persist_kernels.hpp"
 #include "finish16_kernels.hpp"
 #include "soa_wide_kernels.hpp"
+#include "typed_kernels.hpp"
 
 // The large sort's kernels and the per-digit passes' are instantiated in kernels_finish.hip / kernels_passes.hip / kernels_perdigit.hip (translation units of
 // their own, compiled beside this one); here they are only declared.  -DADLHIP_SINGLE_TU builds everything in this file (what tools/gen_large_kernels.py reads the list from).
@@ -2024,6 +2025,136 @@ int soa_check_widths(int key_bytes, int value_bytes)
     return ADLHIP_SUCCESS;
 }
 
+// ---- typed keys, order, argsort (typed_kernels.hpp; no reference counterpart) ---------------------------------------------------
+struct KeyTypeInfo {
+    int bytes, kind;   // kind: adlhip::kKeyUnsigned / kKeySigned / kKeyFloat
+};
+int key_type_info(int key_type, int order, KeyTypeInfo* out)
+{
+    if (key_type < ADLHIP_KEY_U32 || key_type > ADLHIP_KEY_F64)
+        return fail("key_type must be one of ADLHIP_KEY_U32 .. ADLHIP_KEY_F64 (0..5), got %d", key_type);
+    if (order != ADLHIP_ORDER_ASCENDING && order != ADLHIP_ORDER_DESCENDING)
+        return fail("order must be ADLHIP_ORDER_ASCENDING (0) or ADLHIP_ORDER_DESCENDING (1), got %d", order);
+    out->bytes = key_type < ADLHIP_KEY_U64 ? 4 : 8;
+    out->kind = key_type % 3;
+    return ADLHIP_SUCCESS;
+}
+
+// calls F_<KIND, DESC>(...) for the run-time kind and order
+#define ADLHIP_TYPED_DISPATCH(kind_, desc_, CALL)                                    \
+    do {                                                                             \
+        switch ((kind_) * 2 + ((desc_) ? 1 : 0)) {                                   \
+        case 0: CALL(adlhip::kKeyUnsigned, 0); break;                                \
+        case 1: CALL(adlhip::kKeyUnsigned, 1); break;                                \
+        case 2: CALL(adlhip::kKeySigned, 0); break;                                  \
+        case 3: CALL(adlhip::kKeySigned, 1); break;                                  \
+        case 4: CALL(adlhip::kKeyFloat, 0); break;                                   \
+        default: CALL(adlhip::kKeyFloat, 1); break;                                  \
+        }                                                                            \
+    } while (0)
+
+// one streaming sweep: dst[i] = enc(src[i]) or dec(src[i]).  The identity (unsigned, ascending) launches nothing when dst is src.
+template <typename U>
+int key_codec(adlhip_device* d, int kind, int desc, bool decode, U* dst, const U* src, size_t n)
+{
+    if (kind == adlhip::kKeyUnsigned && !desc) {
+        if (dst != src) HIPCHK(hipMemcpyAsync(dst, src, n * sizeof(U), hipMemcpyDeviceToDevice, d->stream));
+        return ADLHIP_SUCCESS;
+    }
+    const size_t nvec = n / (16 / sizeof(U));
+    const uint32_t wgs = (uint32_t)std::min<size_t>(std::max<size_t>((nvec + adlhip::kSoaNT - 1) / adlhip::kSoaNT, 1),
+                                                    (size_t)d->prop.multiProcessorCount * 16);
+    return launch(d, decode ? "key_decode" : "key_encode", [&] {
+#define ADLHIP_CODEC(KIND_, DESC_)                                                                                              \
+    if (decode) hipLaunchKernelGGL((adlhip::key_codec_kernel<U, KIND_, DESC_, 1>), dim3(wgs), dim3(adlhip::kSoaNT), 0, d->stream, dst, src, n); \
+    else hipLaunchKernelGGL((adlhip::key_codec_kernel<U, KIND_, DESC_, 0>), dim3(wgs), dim3(adlhip::kSoaNT), 0, d->stream, dst, src, n)
+        ADLHIP_TYPED_DISPATCH(kind, desc, ADLHIP_CODEC);
+#undef ADLHIP_CODEC
+    });
+}
+
+// The typed sibling of soa_wide_sort: {32 encoded key bits, source index} pairs through the stable pair sort, once per key dword, one
+// gather at the end.  keys_out / vals_out / index_out: whichever the caller wants (null = not written); none of them may be keys_in
+// or vals_in when it is gathered (8-byte keys, values) -- the callers pass partner arrays and copy back.
+template <typename U, typename V>
+int typed_index_sort(adlhip_device* d, int kind, int desc, const U* keys_in, U* keys_out, const V* vals_in, V* vals_out,
+                     uint32_t* index_out, void* work, size_t n)
+{
+    const SoaWideLayout L = soa_wide_layout(d, n);
+    char* w = static_cast<char*>(work);
+    uint64_t* pa = reinterpret_cast<uint64_t*>(w + L.off_pairs_a);
+    uint64_t* pb = reinterpret_cast<uint64_t*>(w + L.off_pairs_b);
+    void* kv = w + L.off_kv;
+    const uint32_t nn = (uint32_t)n;
+    const uint32_t wgs = (uint32_t)std::min<size_t>((n + adlhip::kSoaNT - 1) / adlhip::kSoaNT, (size_t)d->prop.multiProcessorCount * 16);
+    int rc = launch(d, sizeof(U) == 4 ? "typed_pack_index_k32" : "typed_pack_index_k64", [&] {
+#define ADLHIP_PACK(KIND_, DESC_) \
+    hipLaunchKernelGGL((adlhip::typed_pack_index_kernel<U, KIND_, DESC_>), dim3(wgs), dim3(adlhip::kSoaNT), 0, d->stream, keys_in, pa, nn)
+        ADLHIP_TYPED_DISPATCH(kind, desc, ADLHIP_PACK);
+#undef ADLHIP_PACK
+    });
+    if (rc) return rc;
+    rc = sort_entry<uint64_t>(d, ADLHIP_ELEM_KV32, pa, pb, kv, L.kv_bytes, n, 32, 32);
+    if (rc) return rc;
+    const uint64_t* sorted = pa;
+    if constexpr (sizeof(U) == 8) {   // second 32-bit digit; the sort is stable, so equal high dwords keep the order of their low dwords
+        rc = launch(d, "typed_repack_high", [&] {
+#define ADLHIP_REPACK(KIND_, DESC_) \
+    hipLaunchKernelGGL((adlhip::typed_repack_high_kernel<KIND_, DESC_>), dim3(wgs), dim3(adlhip::kSoaNT), 0, d->stream, keys_in, (const uint64_t*)pa, pb, nn)
+            ADLHIP_TYPED_DISPATCH(kind, desc, ADLHIP_REPACK);
+#undef ADLHIP_REPACK
+        });
+        if (rc) return rc;
+        rc = sort_entry<uint64_t>(d, ADLHIP_ELEM_KV32, pb, pa, kv, L.kv_bytes, n, 32, 32);
+        if (rc) return rc;
+        sorted = pb;
+    }
+    return launch(d, "typed_gather", [&] {
+#define ADLHIP_GATHER(KIND_, DESC_) \
+    hipLaunchKernelGGL((adlhip::typed_gather_kernel<U, V, KIND_, DESC_>), dim3(wgs), dim3(adlhip::kSoaNT), 0, d->stream, sorted, keys_in, keys_out, vals_in, vals_out, index_out, nn)
+        if constexpr (sizeof(U) == 8) ADLHIP_GATHER(adlhip::kKeyUnsigned, 0);   // 8-byte keys are fetched, not decoded
+        else ADLHIP_TYPED_DISPATCH(kind, desc, ADLHIP_GATHER);
+#undef ADLHIP_GATHER
+    });
+}
+
+// in-place pairs: gathered arrays land in the partner arrays and are copied back, as soa_wide_sort does
+template <typename U, typename V>
+int typed_pairs_sort(adlhip_device* d, int kind, int desc, U* keys, V* vals, U* tmp_keys, V* tmp_vals, void* work, size_t n)
+{
+    U* kout = sizeof(U) == 4 ? keys : tmp_keys;   // 4-byte keys are the pairs' own low dwords, decoded: keys[] is not read by the gather
+    int rc = typed_index_sort<U, V>(d, kind, desc, keys, kout, vals, tmp_vals, nullptr, work, n);
+    if (rc) return rc;
+    if (sizeof(U) == 8) HIPCHK(hipMemcpyAsync(keys, tmp_keys, n * sizeof(U), hipMemcpyDeviceToDevice, d->stream));
+    HIPCHK(hipMemcpyAsync(vals, tmp_vals, n * sizeof(V), hipMemcpyDeviceToDevice, d->stream));
+    return ADLHIP_SUCCESS;
+}
+
+int typed_check_n(size_t n)
+{
+    if (n > kMaxElems) return fail("n = %zu exceeds the supported maximum %zu", n, (size_t)kMaxElems);   // (< 2^32: indices fit a dword)
+    return ADLHIP_SUCCESS;
+}
+
+// encode in place -> unsigned sort on whole keys -> decode in place.  A sort that refuses after the encode was enqueued (a work buffer
+// that does not fit the one-sweep path the knobs ask for, ...) still gets its decode: the caller's keys come back as they were.
+template <typename U>
+int typed_keys_sort(adlhip_device* d, int elem_kind, int kind, int desc, U* keys, U* tmp, void* work, size_t work_bytes, size_t n)
+{
+    int rc = key_codec<U>(d, kind, desc, false, keys, keys, n);
+    if (rc) return rc;
+    const int bits = 8 * (int)sizeof(U);
+    rc = sort_entry<U>(d, elem_kind, keys, tmp, work, work_bytes, n, bits, bits);
+    if (rc) {
+        char kept[sizeof(g_err)];
+        memcpy(kept, g_err, sizeof(kept));
+        (void)key_codec<U>(d, kind, desc, true, keys, keys, n);
+        memcpy(g_err, kept, sizeof(kept));   // the sort's message, not the decode's
+        return rc;
+    }
+    return key_codec<U>(d, kind, desc, true, keys, keys, n);
+}
+
 }  // namespace
 
 // ================================================================================================
@@ -2565,6 +2696,121 @@ int adlhip_radix_sort_soa(adlhip_device* d, void* keys, int key_bytes, void* val
     if (value_bytes == 8) ADLHIP_SOA(uint64_t, uint64_t);
     ADLHIP_SOA(uint64_t, V16);
 #undef ADLHIP_SOA
+}
+
+// ---- typed keys, order, argsort ---------------------------------------------------------------------
+
+static int key_codec_entry(adlhip_device* d, int key_type, int order, bool decode, void* dst, const void* src, size_t n)
+{
+    if (bind(d)) return ADLHIP_FAILURE;
+    KeyTypeInfo t;
+    if (key_type_info(key_type, order, &t)) return ADLHIP_FAILURE;
+    if (n > kMaxElems) return fail("n = %zu exceeds the supported maximum %zu", n, (size_t)kMaxElems);
+    if (n == 0) return ADLHIP_SUCCESS;
+    if (!dst || !src) return fail("null buffer passed to the key codec");
+    if ((reinterpret_cast<uintptr_t>(dst) | reinterpret_cast<uintptr_t>(src)) & 15u) return fail("key buffers must be 16-byte aligned");
+    if (t.bytes == 4) return key_codec<uint32_t>(d, t.kind, order, decode, (uint32_t*)dst, (const uint32_t*)src, n);
+    return key_codec<uint64_t>(d, t.kind, order, decode, (uint64_t*)dst, (const uint64_t*)src, n);
+}
+
+int adlhip_key_encode(adlhip_device* d, int key_type, int order, void* dst, const void* src, size_t n)
+{
+    return key_codec_entry(d, key_type, order, false, dst, src, n);
+}
+
+int adlhip_key_decode(adlhip_device* d, int key_type, int order, void* dst, const void* src, size_t n)
+{
+    return key_codec_entry(d, key_type, order, true, dst, src, n);
+}
+
+int adlhip_sort_typed_scratch_bytes(adlhip_device* d, int key_type, int mode, int value_bytes, size_t n, size_t* tmp_keys_bytes,
+                                    size_t* tmp_vals_bytes, size_t* work_bytes)
+{
+    if (!d) return fail("null device handle");
+    KeyTypeInfo t;
+    if (key_type_info(key_type, ADLHIP_ORDER_ASCENDING, &t)) return ADLHIP_FAILURE;
+    if (mode < 0 || mode > 2) return fail("mode must be 0 (keys only), 1 (pairs) or 2 (argsort), got %d", mode);
+    if (mode == 1 && soa_check_widths(t.bytes, value_bytes)) return ADLHIP_FAILURE;
+    size_t tk = 0, tv = 0, wb = 0;
+    if (mode == 0) {
+        tk = align_up(n * (size_t)t.bytes, 256);
+        wb = sort_work_bytes(d, t.bytes == 4 ? ADLHIP_ELEM_U32 : ADLHIP_ELEM_U64, n, 8 * t.bytes, 1);
+    } else {
+        if (mode == 1) {
+            tk = t.bytes == 8 ? align_up(n * 8, 256) : 0;   // 4-byte keys come out of the sorted pairs themselves
+            tv = align_up(n * (size_t)value_bytes, 256);
+        }
+        wb = soa_wide_layout(d, n).total;
+    }
+    if (tmp_keys_bytes) *tmp_keys_bytes = tk;
+    if (tmp_vals_bytes) *tmp_vals_bytes = tv;
+    if (work_bytes) *work_bytes = wb;
+    return ADLHIP_SUCCESS;
+}
+
+int adlhip_sort_keys_typed(adlhip_device* d, int key_type, int order, void* keys, void* tmp, void* work, size_t work_bytes, size_t n)
+{
+    if (bind(d)) return ADLHIP_FAILURE;
+    KeyTypeInfo t;
+    if (key_type_info(key_type, order, &t)) return ADLHIP_FAILURE;
+    if (typed_check_n(n)) return ADLHIP_FAILURE;
+    if (n == 0) return ADLHIP_SUCCESS;
+    if (!keys || !tmp || !work) return fail("null buffer passed to the typed sort");
+    if ((reinterpret_cast<uintptr_t>(keys) | reinterpret_cast<uintptr_t>(tmp) | reinterpret_cast<uintptr_t>(work)) & 15u)
+        return fail("sort buffers must be 16-byte aligned");
+    const int kind = t.bytes == 4 ? ADLHIP_ELEM_U32 : ADLHIP_ELEM_U64;
+    const size_t need = sort_work_bytes(d, kind, n, 8 * t.bytes, 1);
+    if (work_bytes < need) return fail("work buffer too small: %zu < %zu (adlhip_sort_typed_scratch_bytes)", work_bytes, need);
+    if (t.bytes == 4) return typed_keys_sort<uint32_t>(d, kind, t.kind, order, (uint32_t*)keys, (uint32_t*)tmp, work, work_bytes, n);
+    return typed_keys_sort<uint64_t>(d, kind, t.kind, order, (uint64_t*)keys, (uint64_t*)tmp, work, work_bytes, n);
+}
+
+int adlhip_sort_pairs_typed(adlhip_device* d, int key_type, int order, void* keys, void* vals, int value_bytes, void* tmp_keys,
+                            void* tmp_vals, void* work, size_t work_bytes, size_t n)
+{
+    if (bind(d)) return ADLHIP_FAILURE;
+    KeyTypeInfo t;
+    if (key_type_info(key_type, order, &t)) return ADLHIP_FAILURE;
+    if (soa_check_widths(t.bytes, value_bytes)) return ADLHIP_FAILURE;
+    if (typed_check_n(n)) return ADLHIP_FAILURE;
+    if (n == 0) return ADLHIP_SUCCESS;
+    if (!keys || !vals || !tmp_vals || !work || (t.bytes == 8 && !tmp_keys)) return fail("null buffer passed to the typed sort");
+    if ((reinterpret_cast<uintptr_t>(keys) | reinterpret_cast<uintptr_t>(vals) | reinterpret_cast<uintptr_t>(tmp_keys) |
+         reinterpret_cast<uintptr_t>(tmp_vals) | reinterpret_cast<uintptr_t>(work)) & 15u)
+        return fail("sort buffers must be 16-byte aligned");
+    const size_t need = soa_wide_layout(d, n).total;
+    if (work_bytes < need) return fail("work buffer too small: %zu < %zu (adlhip_sort_typed_scratch_bytes)", work_bytes, need);
+#define ADLHIP_TP(K_, V_) return typed_pairs_sort<K_, V_>(d, t.kind, order, (K_*)keys, (V_*)vals, (K_*)tmp_keys, (V_*)tmp_vals, work, n)
+    if (t.bytes == 4) {
+        if (value_bytes == 4) ADLHIP_TP(uint32_t, uint32_t);
+        if (value_bytes == 8) ADLHIP_TP(uint32_t, uint64_t);
+        ADLHIP_TP(uint32_t, V16);
+    }
+    if (value_bytes == 4) ADLHIP_TP(uint64_t, uint32_t);
+    if (value_bytes == 8) ADLHIP_TP(uint64_t, uint64_t);
+    ADLHIP_TP(uint64_t, V16);
+#undef ADLHIP_TP
+}
+
+int adlhip_argsort_typed(adlhip_device* d, int key_type, int order, const void* keys_in, void* keys_out, uint32_t* index_out, void* work,
+                         size_t work_bytes, size_t n)
+{
+    if (bind(d)) return ADLHIP_FAILURE;
+    KeyTypeInfo t;
+    if (key_type_info(key_type, order, &t)) return ADLHIP_FAILURE;
+    if (typed_check_n(n)) return ADLHIP_FAILURE;
+    if (n == 0) return ADLHIP_SUCCESS;
+    if (!keys_in || !index_out || !work) return fail("null buffer passed to the typed argsort");
+    if (keys_out == keys_in) return fail("argsort: d_keys_out must not be d_keys_in (adlhip_sort_pairs_typed sorts in place)");
+    if ((reinterpret_cast<uintptr_t>(keys_in) | reinterpret_cast<uintptr_t>(keys_out) | reinterpret_cast<uintptr_t>(index_out) |
+         reinterpret_cast<uintptr_t>(work)) & 15u)
+        return fail("sort buffers must be 16-byte aligned");
+    const size_t need = soa_wide_layout(d, n).total;
+    if (work_bytes < need) return fail("work buffer too small: %zu < %zu (adlhip_sort_typed_scratch_bytes)", work_bytes, need);
+    // (no values: the gather's value pointers are null, V only names an instantiation that exists anyway)
+    if (t.bytes == 4)
+        return typed_index_sort<uint32_t, uint32_t>(d, t.kind, order, (const uint32_t*)keys_in, (uint32_t*)keys_out, nullptr, nullptr, index_out, work, n);
+    return typed_index_sort<uint64_t, uint32_t>(d, t.kind, order, (const uint64_t*)keys_in, (uint64_t*)keys_out, nullptr, nullptr, index_out, work, n);
 }
 
 int adlhip_segment_sort(adlhip_device* d, int elem_kind, void* data, const uint32_t* seg_start, size_t num_segments,

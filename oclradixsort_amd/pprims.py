@@ -5,6 +5,9 @@
     p.radixSort(device, buffer_uint2, n, sortBits=32)      # Pprims.h:38  (dtype uint64 = {key, value})
     p.radixSort64(device, buffer_u64, n, sortBits=64)      # 64-bit keys (no reference counterpart)
     p.scan(device, dst, src, n, sumOut=None)               # Pprims.h:35
+    p.sortKeys(device, buffer, n, descending=False)        # uint32 / int32 / float32 / uint64 / int64 / float64 keys
+    p.sortPairs(device, keys, values, n, descending=False) # the same keys with values of 4, 8 or 16 bytes, stable
+    p.argsort(device, keys, n, descending=False)           # -> Buffer(uint32): the stable sorting permutation
 
 Like the reference object it owns lazily grown device scratch (m_u32WorkBuffer[0] = ping-pong data
 buffer, m_u32WorkBuffer[1] = histogram table; Pprims.h:44-45, Pprims.cpp:226-232, :332-337) and must be
@@ -23,6 +26,10 @@ ELEM_U32 = 0
 ELEM_KV32 = 1
 ELEM_U64 = 2
 ELEM_SOA32 = 3
+
+# ADLHIP_KEY_* by element type (include/adlhip.h, "typed keys, order, argsort")
+KEY_TYPES = {np.dtype(np.uint32): 0, np.dtype(np.int32): 1, np.dtype(np.float32): 2,
+             np.dtype(np.uint64): 3, np.dtype(np.int64): 4, np.dtype(np.float64): 5}
 
 
 class Pprims:
@@ -124,6 +131,74 @@ class Pprims:
     def radixSort64(self, device, inout, n, sortBits=64):
         assert inout.dtype == np.uint64
         self._sort(device, ELEM_U64, _lib.load().adlhip_radix_sort_u64, inout, n, sortBits)
+
+    # -- typed keys, order, argsort (no reference counterpart; include/adlhip.h adlhip_sort_*_typed)
+    @staticmethod
+    def _key_type(buf, what):
+        kt = KEY_TYPES.get(np.dtype(buf.dtype))
+        if kt is None:
+            raise AdlHipError("%s: unsupported key type %s (uint32, int32, float32, uint64, int64, float64)" % (what, buf.dtype))
+        return kt
+
+    def _typed_scratch(self, device, key_type, mode, value_bytes, n):
+        tk = ctypes.c_size_t()
+        tv = ctypes.c_size_t()
+        wb = ctypes.c_size_t()
+        check(_lib.load().adlhip_sort_typed_scratch_bytes(device._h, key_type, mode, value_bytes, n, ctypes.byref(tk),
+                                                          ctypes.byref(tv), ctypes.byref(wb)), "adlhip_sort_typed_scratch_bytes")
+        self._scratch(device, tk.value + tv.value, wb.value)          # tmp keys + tmp values, back to back
+        return tk.value
+
+    def sortKeys(self, device, buf, n, descending=False):
+        """Sorts n keys of buf.dtype in place: signed integers by value, floats in IEEE-754 totalOrder (-NaN < -inf < ... < -0 <
+        +0 < ... < +inf < +NaN), ascending or descending.  Two streaming sweeps (encode, decode) around the unsigned sort."""
+        if device is None:
+            raise AdlHipError("sortKeys needs a device")
+        kt = self._key_type(buf, "sortKeys")
+        n = int(n)
+        self._typed_scratch(device, kt, 0, 0, n)
+        check(_lib.load().adlhip_sort_keys_typed(device._h, kt, 1 if descending else 0, buf.ptr(), self.m_tmp.ptr(),
+                                                 self.m_work.ptr(), self.m_work.getSize(), n), "sortKeys")
+
+    def sortPairs(self, device, keys, values, n, descending=False):
+        """Sorts n typed keys and their values (any element type of 4, 8 or 16 bytes) in place, stably: equal keys keep their
+        input order, descending too.  Key order as sortKeys."""
+        if device is None:
+            raise AdlHipError("sortPairs needs a device")
+        kt = self._key_type(keys, "sortPairs")
+        vb = values.dtype.itemsize
+        if vb not in (4, 8, 16):
+            raise AdlHipError("sortPairs: values %s unsupported (4, 8 or 16 bytes)" % values.dtype)
+        n = int(n)
+        tk = self._typed_scratch(device, kt, 1, vb, n)
+        tmp_k = self.m_tmp.ptr() if tk else None
+        tmp_v = ctypes.c_void_p(self.m_tmp.m_ptr + tk) if self.m_tmp.m_ptr else None
+        check(_lib.load().adlhip_sort_pairs_typed(device._h, kt, 1 if descending else 0, keys.ptr(), values.ptr(), vb, tmp_k, tmp_v,
+                                                  self.m_work.ptr(), self.m_work.getSize(), n), "sortPairs")
+
+    def argsort(self, device, keys, n, descending=False, keysOut=None, indexOut=None):
+        """Returns a Buffer(uint32) with the stable sorting permutation of the first n keys: out[j] = position in `keys` of the
+        j-th element of the sorted order.  `keys` is left intact; keysOut (same dtype, not `keys`) receives the sorted keys.
+        indexOut: a uint32 buffer of n elements to fill and return instead of a new one."""
+        if device is None:
+            raise AdlHipError("argsort needs a device")
+        kt = self._key_type(keys, "argsort")
+        if keysOut is not None and np.dtype(keysOut.dtype) != np.dtype(keys.dtype):
+            raise AdlHipError("argsort: keysOut is %s, keys are %s" % (keysOut.dtype, keys.dtype))
+        if indexOut is not None and (np.dtype(indexOut.dtype) != np.uint32 or indexOut.getSize() < int(n)):
+            raise AdlHipError("argsort: indexOut must hold n uint32 elements")
+        n = int(n)
+        self._typed_scratch(device, kt, 2, 0, n)
+        out = indexOut if indexOut is not None else Buffer(device, n, np.uint32)
+        try:
+            check(_lib.load().adlhip_argsort_typed(device._h, kt, 1 if descending else 0, keys.ptr(),
+                                                   keysOut.ptr() if keysOut is not None else None, out.ptr(), self.m_work.ptr(),
+                                                   self.m_work.getSize(), n), "argsort")
+        except AdlHipError:
+            if indexOut is None:
+                out.release()
+            raise
+        return out
 
     def copy(self, device, dst, src, n):
         """Pprims::copy (Pprims.cpp:31-67, commented out in the reference): first n elements of src -> dst."""

@@ -1,0 +1,99 @@
+"""torch front end of the typed sorts: what `torch.sort` / `torch.argsort` return for a 1-D tensor, computed by the HIP
+back-end on torch's own stream.
+
+    s = TorchSorter()                       # one adlhip_device on the stream that is torch's current one NOW + its scratch
+    values, indices = s.sort(t)             # t: 1-D CUDA tensor, int32 / int64 / float32 / float64
+    indices = s.argsort(t, descending=True)
+    s.close()
+
+Always out of place and always stable.  The ONE difference from `torch.sort(t, stable=True)`: floats are ordered by
+IEEE-754 totalOrder, so NaNs with the sign bit set sort FIRST (torch puts every NaN last) and -0 sorts before +0 (torch
+treats them as equal and keeps their input order).  Inputs without NaN and -0 give torch's result bit for bit.
+
+A sorter is bound to the stream that was torch's current stream on its device when it was constructed (as dist._Stage is): its sorts
+are enqueued there.  Calling it while another stream is current (`with torch.cuda.stream(other)`) would leave the sort unordered
+against the producer of its input and against the caching allocator, so sort() / argsort() raise RuntimeError then; make one sorter
+per stream.
+
+torch and the HIP back-end must share one HIP runtime (they share a stream).  A torch wheel that bundles its own runtime has to be
+imported before the back-end's library is loaded -- `import torch` before the first oclradixsort_amd call, as dist.py does --;
+TorchSorter refuses to start when torch cannot see the device.
+"""
+import numpy as np
+import torch
+
+from ._lib import AdlHipError
+from .adl import Buffer, Config, DeviceUtils
+from .pprims import Pprims
+
+_NP_DTYPE = {torch.int32: np.int32, torch.int64: np.int64, torch.float32: np.float32, torch.float64: np.float64}
+
+
+class TorchSorter:
+    def __init__(self, device_index=0):
+        if not torch.cuda.is_available():
+            raise AdlHipError("TorchSorter: torch sees no GPU (if the HIP back-end was used before torch was imported, the process "
+                              "holds two HIP runtimes: import torch first)")
+        self.torch_device = torch.device("cuda", int(device_index))
+        with torch.cuda.device(self.torch_device):
+            raw = torch.cuda.current_stream().cuda_stream
+        self.raw_stream = raw
+        self.device = DeviceUtils.allocate(cfg=Config(int(device_index)), stream=raw)
+        self.pprims = Pprims()
+
+    def close(self):
+        if self.device is not None:
+            torch.cuda.synchronize(self.torch_device)   # the scratch may still be in use by enqueued sorts
+            self.pprims.close()
+            DeviceUtils.deallocate(self.device)
+            self.device = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def _check(self, t):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError("TorchSorter: expected a torch.Tensor, got %s" % type(t).__name__)
+        if t.dtype not in _NP_DTYPE:
+            raise TypeError("TorchSorter: dtype %s unsupported (int32, int64, float32, float64)" % t.dtype)
+        if t.dim() != 1:
+            raise ValueError("TorchSorter: 1-D tensors only, got %d dimensions" % t.dim())
+        if t.device != self.torch_device:
+            raise ValueError("TorchSorter: tensor is on %s, the sorter on %s" % (t.device, self.torch_device))
+        if t.numel() >= 1 << 32:
+            raise ValueError("TorchSorter: fewer than 2^32 elements")
+
+    def _wrap(self, t, dtype):
+        b = Buffer(dtype=dtype)
+        b.setRawPtr(self.device, t.data_ptr(), t.numel())
+        return b
+
+    def _run(self, t, descending, want_values):
+        self._check(t)
+        if torch.cuda.current_stream(self.torch_device).cuda_stream != self.raw_stream:
+            raise RuntimeError("TorchSorter: bound to the stream that was current at construction; another stream is current now")
+        n = t.numel()
+        src = t.contiguous()           # (a copy only for a strided input; the sort never writes its input)
+        values = torch.empty(n, dtype=t.dtype, device=t.device) if want_values else None
+        if n == 0:
+            return values, torch.empty(0, dtype=torch.int64, device=t.device)
+        npdt = _NP_DTYPE[t.dtype]
+        idx32 = torch.empty(n, dtype=torch.int32, device=t.device)   # uint32 positions in an int32 tensor
+        lib_idx = self._wrap(idx32, np.uint32)
+        p = self.pprims
+        p.argsort(self.device, self._wrap(src, npdt), n, descending=descending,
+                  keysOut=self._wrap(values, npdt) if want_values else None, indexOut=lib_idx)
+        # the stream is synchronised by torch, never by adlhip_sync: pick up device-side faults of earlier, completed sorts
+        self.device.checkFault()
+        return values, idx32.to(torch.int64) & 0xffffffff
+
+    def sort(self, t, descending=False):
+        """(values, indices) like torch.sort(t, descending=descending, stable=True); indices are int64."""
+        return self._run(t, bool(descending), True)
+
+    def argsort(self, t, descending=False):
+        """indices like torch.argsort(t, descending=descending, stable=True), int64."""
+        return self._run(t, bool(descending), False)[1]

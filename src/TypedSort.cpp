@@ -1,0 +1,142 @@
+// Pprims::sortKeys / Pprims::argsort: signed, floating-point and descending keys (no reference counterpart; the reference sorts
+// u32 bit patterns, ascending: Tahoe/ParallelPrimitives/Pprims.h:38-41).  A TYPE_CL (HIP) device runs adlhip_sort_keys_typed /
+// adlhip_argsort_typed; a TYPE_HOST device sorts on the CPU with std::stable_sort on the same total order, as the reference's
+// host branches do for u32 keys (Pprims.cpp:202-212, :306-316).
+#include <Tahoe/ParallelPrimitives/Pprims.h>
+
+#include <algorithm>
+#include <cstring>
+#include <vector>
+
+namespace Tahoe {
+
+namespace {
+
+template <typename T> struct KeyTraits;
+template <> struct KeyTraits<u32>       { typedef u32 Bits; enum { TYPE = ADLHIP_KEY_U32, SIGNED = 0, FLOAT = 0 }; };
+template <> struct KeyTraits<int>       { typedef u32 Bits; enum { TYPE = ADLHIP_KEY_I32, SIGNED = 1, FLOAT = 0 }; };
+template <> struct KeyTraits<float>     { typedef u32 Bits; enum { TYPE = ADLHIP_KEY_F32, SIGNED = 0, FLOAT = 1 }; };
+template <> struct KeyTraits<u64>       { typedef u64 Bits; enum { TYPE = ADLHIP_KEY_U64, SIGNED = 0, FLOAT = 0 }; };
+template <> struct KeyTraits<long long> { typedef u64 Bits; enum { TYPE = ADLHIP_KEY_I64, SIGNED = 1, FLOAT = 0 }; };
+template <> struct KeyTraits<double>    { typedef u64 Bits; enum { TYPE = ADLHIP_KEY_F64, SIGNED = 0, FLOAT = 1 }; };
+
+// the key's rank among all bit patterns of its width: unsigned order of the result is the order of the typed keys (floats: IEEE-754
+// totalOrder) -- the host's statement of the device codec (oclradixsort_amd/csrc/typed_kernels.hpp)
+template <typename T>
+inline typename KeyTraits<T>::Bits ordinal(const T& key, bool descending)
+{
+    typedef typename KeyTraits<T>::Bits B;
+    const B sign = (B)1 << (8 * sizeof(B) - 1);
+    B b;
+    memcpy(&b, &key, sizeof(B));
+    if (KeyTraits<T>::SIGNED) b ^= sign;
+    if (KeyTraits<T>::FLOAT) b ^= (b & sign) ? (B)~(B)0 : sign;
+    return descending ? (B)~b : b;
+}
+
+template <typename B>
+struct Ranked {
+    B ord;
+    u32 idx;
+    bool operator<(const Ranked& o) const { return ord < o.ord; }
+};
+
+// order[j] = position of the j-th element of the sorted order (stable)
+template <typename T>
+void hostArgsort(const T* keys, int n, bool descending, std::vector<Ranked<typename KeyTraits<T>::Bits> >& order)
+{
+    order.resize((size_t)n);
+    for (int i = 0; i < n; ++i) {
+        order[i].ord = ordinal(keys[i], descending);
+        order[i].idx = (u32)i;
+    }
+    std::stable_sort(order.begin(), order.end());
+}
+
+inline bool onDevice(const adl::Device* device)
+{
+    return device && device->getType() == adl::TYPE_CL && device->getProcType() == adl::Device::Config::DEVICE_GPU && device->hip() != 0;
+}
+
+}  // namespace
+
+template <typename T>
+void Pprims::sortKeysTyped(const adl::Device* device, const adl::Buffer<T>& inout, int n, bool descending)
+{
+    ADLASSERT(n >= 0);
+    if (n <= 0) return;
+    ADLASSERT(device != 0);
+    ADLASSERT((adl::u64)n <= inout.getSize());
+    if (!onDevice(device)) {
+        ADLASSERT(device->getType() == adl::TYPE_HOST);   // a HIP device never falls back to the CPU
+        if (device->getType() != adl::TYPE_HOST) return;
+        T* host = inout.getHostPtr(n);
+        adl::DeviceUtils::waitForCompletion(device);
+        std::vector<Ranked<typename KeyTraits<T>::Bits> > order;
+        hostArgsort(host, n, descending, order);
+        std::vector<T> sorted((size_t)n);
+        for (int j = 0; j < n; ++j) sorted[j] = host[order[j].idx];
+        memcpy(host, sorted.data(), sizeof(T) * (size_t)n);
+        inout.returnHostPtr(host);
+        adl::DeviceUtils::waitForCompletion(device);
+        return;
+    }
+    size_t tk = 0, tv = 0, wb = 0;
+    const int rcq = adlhip_sort_typed_scratch_bytes(device->hip(), KeyTraits<T>::TYPE, 0, 0, (size_t)n, &tk, &tv, &wb);
+    ADLASSERT(rcq == ADLHIP_SUCCESS);
+    reserve(device, tk, wb);
+    const int rc = adlhip_sort_keys_typed(device->hip(), KeyTraits<T>::TYPE, descending ? ADLHIP_ORDER_DESCENDING : ADLHIP_ORDER_ASCENDING,
+                                          inout.m_ptr, m_tmp->m_ptr, m_work->m_ptr, (size_t)m_work->getSize(), (size_t)n);
+    if (rc != ADLHIP_SUCCESS) TH_LOG_ERROR("Pprims::sortKeys: %s\n", adlhip_last_error());
+    ADLASSERT(rc == ADLHIP_SUCCESS);
+}
+
+template <typename T>
+void Pprims::argsortTyped(const adl::Device* device, const adl::Buffer<T>& keys, adl::Buffer<u32>& indexOut, int n, bool descending)
+{
+    ADLASSERT(n >= 0);
+    if (n <= 0) return;
+    ADLASSERT(device != 0);
+    ADLASSERT((adl::u64)n <= keys.getSize() && (adl::u64)n <= indexOut.getSize());
+    if (!onDevice(device)) {
+        ADLASSERT(device->getType() == adl::TYPE_HOST);   // a HIP device never falls back to the CPU
+        if (device->getType() != adl::TYPE_HOST) return;
+        T* host = keys.getHostPtr(n);
+        u32* out = indexOut.getHostPtr(n);
+        adl::DeviceUtils::waitForCompletion(device);
+        std::vector<Ranked<typename KeyTraits<T>::Bits> > order;
+        hostArgsort(host, n, descending, order);
+        for (int j = 0; j < n; ++j) out[j] = order[j].idx;
+        keys.returnHostPtr(host);
+        indexOut.returnHostPtr(out);
+        adl::DeviceUtils::waitForCompletion(device);
+        return;
+    }
+    size_t tk = 0, tv = 0, wb = 0;
+    const int rcq = adlhip_sort_typed_scratch_bytes(device->hip(), KeyTraits<T>::TYPE, 2, 0, (size_t)n, &tk, &tv, &wb);
+    ADLASSERT(rcq == ADLHIP_SUCCESS);
+    reserve(device, tk, wb);
+    const int rc = adlhip_argsort_typed(device->hip(), KeyTraits<T>::TYPE, descending ? ADLHIP_ORDER_DESCENDING : ADLHIP_ORDER_ASCENDING,
+                                        keys.m_ptr, 0, indexOut.m_ptr, m_work->m_ptr, (size_t)m_work->getSize(), (size_t)n);
+    if (rc != ADLHIP_SUCCESS) TH_LOG_ERROR("Pprims::argsort: %s\n", adlhip_last_error());
+    ADLASSERT(rc == ADLHIP_SUCCESS);
+}
+
+#define TAHOE_TYPED(T)                                                                                                              \
+    void Pprims::sortKeys(const adl::Device* device, const adl::Buffer<T>& inout, int n, bool descending)                         \
+    {                                                                                                                               \
+        sortKeysTyped<T>(device, inout, n, descending);                                                                             \
+    }                                                                                                                               \
+    void Pprims::argsort(const adl::Device* device, const adl::Buffer<T>& keys, adl::Buffer<u32>& indexOut, int n, bool descending) \
+    {                                                                                                                               \
+        argsortTyped<T>(device, keys, indexOut, n, descending);                                                                     \
+    }
+TAHOE_TYPED(int)
+TAHOE_TYPED(float)
+TAHOE_TYPED(long long)
+TAHOE_TYPED(double)
+TAHOE_TYPED(u32)
+TAHOE_TYPED(u64)
+#undef TAHOE_TYPED
+
+}  // namespace Tahoe
