@@ -6,6 +6,7 @@
 //   radixSort u64 keys                                               (new: BASELINE config #5)
 //   copy / fill                                                      (reference Pprims.cpp:31-120, commented out there)
 //   sortKeys / argsort  signed, float and descending keys            (new: adlhip_sort_keys_typed / adlhip_argsort_typed)
+//   topK      the first k entries of argsort, by selection           (new: adlhip_topk_typed)
 // Same argument meaning; differences, all supersets: any n >= 0 (the reference needs n % 256 == 0 for
 // keys), scan has no 1,048,576-element limit, sortBits < 32 also works on 64-bit keys up to 64.
 // Device work is enqueued and the call returns (no sync), as in the reference's GPU branches.
@@ -84,8 +85,24 @@ public:
     void argsort(const adl::Device* device, const adl::Buffer<double>& keys, adl::Buffer<u32>& indexOut, int n, bool descending = false);
     void argsort(const adl::Device* device, const adl::Buffer<u32>& keys, adl::Buffer<u32>& indexOut, int n, bool descending = false);
     void argsort(const adl::Device* device, const adl::Buffer<u64>& keys, adl::Buffer<u32>& indexOut, int n, bool descending = false);
+    // the first k entries of argsort: indexOut[j] (j < k) = position of the j-th smallest (descending: largest) key, ties by ascending
+    // position; keysOut[j] = that key.  keys is left intact.  A TYPE_HOST device sorts (ordinal, position) on the CPU
+    void topK(const adl::Device* device, const adl::Buffer<int>& keys, adl::Buffer<int>& keysOut, adl::Buffer<u32>& indexOut, int n, int k,
+              bool descending = false);
+    void topK(const adl::Device* device, const adl::Buffer<float>& keys, adl::Buffer<float>& keysOut, adl::Buffer<u32>& indexOut, int n, int k,
+              bool descending = false);
+    void topK(const adl::Device* device, const adl::Buffer<long long>& keys, adl::Buffer<long long>& keysOut, adl::Buffer<u32>& indexOut, int n, int k,
+              bool descending = false);
+    void topK(const adl::Device* device, const adl::Buffer<double>& keys, adl::Buffer<double>& keysOut, adl::Buffer<u32>& indexOut, int n, int k,
+              bool descending = false);
+    void topK(const adl::Device* device, const adl::Buffer<u32>& keys, adl::Buffer<u32>& keysOut, adl::Buffer<u32>& indexOut, int n, int k,
+              bool descending = false);
+    void topK(const adl::Device* device, const adl::Buffer<u64>& keys, adl::Buffer<u64>& keysOut, adl::Buffer<u32>& indexOut, int n, int k,
+              bool descending = false);
 
 private:
+    template <typename T> void topKTyped(const adl::Device* device, const adl::Buffer<T>& keys, adl::Buffer<T>& keysOut, adl::Buffer<u32>& indexOut, int n,
+                                         int k, bool descending);
     template <typename T> void sortKeysTyped(const adl::Device* device, const adl::Buffer<T>& inout, int n, bool descending);
     template <typename T> void argsortTyped(const adl::Device* device, const adl::Buffer<T>& keys, adl::Buffer<u32>& indexOut, int n, bool descending);
     // device scratch owned by the object and grown lazily (reference: m_u32WorkBuffer[0] = ping-pong data,

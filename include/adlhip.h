@@ -259,6 +259,36 @@ int adlhip_sort_pairs_typed(adlhip_device* dev, int key_type, int order, void* d
 int adlhip_argsort_typed(adlhip_device* dev, int key_type, int order, const void* d_keys_in, void* d_keys_out_or_null,
                          uint32_t* d_index_out, void* d_work, size_t work_bytes, size_t n);
 
+/* ---- top-k (no reference counterpart) --------------------------------------------------------- */
+
+/* Work bytes of adlhip_topk_typed for (key_type, n, k); one size covers both of its paths.  With kb = bytes per key, every part
+ * rounded up to 256 bytes:
+ *   max( 82176 (selection state: ten 2048-bin histograms, ranks, cursors) + 4 k (result list)
+ *          + max( 2 n (kb + 4)                                     two survivor lists of {code, position}
+ *               , 4 k + kb k + max(W_u32(k), W_argsort(k)) ),      the finish, which runs when the lists are dead
+ *        W_argsort(n) + n kb + 4 n )                               the full argsort and its full-length outputs
+ * W_argsort = *work_bytes of adlhip_sort_typed_scratch_bytes (mode 2), W_u32 = *work_bytes of adlhip_radix_sort_scratch_bytes (u32 keys).
+ * W_argsort(n) holds two arrays of n 8-byte pairs, so the first term exceeds the second only for small n (the fixed state) and for
+ * 8-byte keys by less than the k-element finish. */
+int adlhip_topk_scratch_bytes(adlhip_device* dev, int key_type, size_t n, size_t k, size_t* work_bytes);
+
+/* The k first elements of the stable order, sorted (NaN and -0 order: above): exactly the first k entries of what
+ * adlhip_argsort_typed(dev, key_type, order, ...) returns for the same input.  d_index_out[j] = position in the input of the j-th
+ * element, d_keys_out[j] = its key, bit for bit; ADLHIP_ORDER_DESCENDING gives the k largest, largest first, ascending the k smallest.
+ * Ties at the k-th key go to the lower input position in both orders, so the result is deterministic.
+ * d_keys_in is never written.  At least one output must be given; each holds k elements, is 16-byte aligned (as are d_keys_in and
+ * d_work) and must not overlap the input.  0 <= k <= n < 2^32; k == 0 succeeds and enqueues nothing.  k > n, a misaligned pointer, an
+ * unknown key type or order, or work_bytes below adlhip_topk_scratch_bytes fail before anything is enqueued.
+ * Enqueues and returns: nothing is copied to the host and nothing is remembered between calls.  Small k ("topk.algo"): radix select on
+ * the composite (encoded key, position) in 11-bit digits, most significant first -- one histogram sweep of the keys, one filtering
+ * sweep, then one launch per further digit on the keys that share the k-th key's leading digits; which bin holds the k-th key, how
+ * many keys survive and whether selection is complete are decided on the device (launch grids depend on n alone; a level with
+ * nothing to do leaves at once).  The k positions are then sorted, their keys gathered and the stable typed pair sort orders the k
+ * (key, position) pairs.  Large k: the full argsort into d_work, its first k entries copied out.  All selection state lives in
+ * d_work, whose contents on entry are arbitrary; the handle owns no word of it. */
+int adlhip_topk_typed(adlhip_device* dev, int key_type, int order, const void* d_keys_in, size_t n, size_t k,
+                      void* d_keys_out_or_null, uint32_t* d_index_out_or_null, void* d_work, size_t work_bytes);
+
 /* ---- segments finished in LDS (no reference counterpart) ------------------------------------- */
 
 /* Sorts, stably and in place, every segment [d_seg_start[s], d_seg_start[s + 1]) of an array of u32 keys
@@ -407,6 +437,9 @@ int adlhip_generate_keys(adlhip_device* dev, int elem_kind, void* dptr, size_t n
  *                      keys are interchangeable -- and {key, value} pairs by ONE stable pass on the key's rank in the
  *                      dictionary; u32 keys of up to 4096 values are counted with a larger dictionary (64 Ki samples); it
  *                      falls through to its LSD passes when a key misses the dictionary
+ *   "topk.algo"        -1 [default] / 0 / 1: adlhip_topk_typed selects (radix select + a k-element finish) while k <= n / 8 and runs
+ *                      the full argsort above; 0 always runs the argsort and copies its first k, 1 always selects (tests,
+ *                      measurements).  The same result bit for bit either way
  *   "sort.net_lookback" 1 [default] / 0: the LSD passes of the large sort's safety net on whole keys are look-back passes -- the
  *                      one-sweep path's histogram, tables and tile body, taken in turns by the net's resident workgroups, four
  *                      passes at a time (u64 keys: two rounds) -- instead of count -> scan -> scatter passes with per-workgroup

@@ -25,6 +25,7 @@
 #include "finish16_kernels.hpp"
 #include "soa_wide_kernels.hpp"
 #include "typed_kernels.hpp"
+#include "select_kernels.hpp"
 
 // The large sort's kernels and the per-digit passes' are instantiated in kernels_finish.hip / kernels_passes.hip / kernels_perdigit.hip (translation units of
 // their own, compiled beside this one); here they are only declared.  -DADLHIP_SINGLE_TU builds everything in this file (what tools/gen_large_kernels.py reads the list from).
@@ -34,6 +35,7 @@
 #include "wavefinish_kernels.inc"
 #include "passes_kernels.inc"
 #include "perdigit_kernels.inc"
+#include "select_kernels.inc"
 #undef X
 #endif
 
@@ -112,6 +114,8 @@ struct adlhip_device {
     int partition_lookback = 1;             // "partition.lookback": the MSB partition as one look-back pass where it pays (0: always three kernels)
     int dict_path = 1;                      // "sort.dict": the large sort's safety net first tries the counting sort for keys that take at most
                                             // 256 values (dict_kernels.hpp); 0 = off
+    int topk_algo = -1;                     // "topk.algo": -1 selection up to kTopkSelectMaxFraction of n, the full argsort above; 0 / 1 force
+                                            // the argsort / the selection
     adlhip::DictBlock* d_dict = nullptr;    // its dictionary and counters (handle-owned; rebuilt by every net that uses them)
     uint32_t* d_msd2 = nullptr;   // the large sort's handle-owned words, allocated with the handle: cursors of pass 1 (256, one
                                   // 128-byte line each) and pass 2 (65536), overflow flag, done counter, the safety net's barrier
@@ -2155,6 +2159,133 @@ int typed_keys_sort(adlhip_device* d, int elem_kind, int kind, int desc, U* keys
     return key_codec<U>(d, kind, desc, true, keys, keys, n);
 }
 
+// ---- top-k (select_kernels.hpp; no reference counterpart) ----------------------------------------------------------------------
+// Work buffer of adlhip_topk_typed: the larger of
+//   selection   [SelState][result: k positions][X], X = the larger of
+//                 two survivor lists of n {code, position} each (codes and positions in arrays of their own), and
+//                 the finish, which runs when the lists are dead: [partner array of the position sort: k u32][gathered keys: k]
+//                 [work of the position sort / of the k-element typed pair sort, whichever is larger]
+//   fallback    [work of the n-element argsort][its sorted keys: n][its index: n u32]
+// every part 256-byte aligned.
+constexpr size_t kTopkSelectMaxFraction = 8;   // "topk.algo" = -1: selection while k <= n / 8 (unmeasured; tools/topk_bench.py)
+struct TopkLayout {
+    size_t off_result, off_x;                               // selection
+    size_t off_codes[2], off_pos[2];                        //   X as survivor lists
+    size_t off_ptmp, off_keys, off_fwork, fwork_bytes;      //   X as the finish's scratch
+    size_t off_akeys, off_aidx, awork_bytes;                // fallback (its sort's work at offset 0)
+    size_t total;
+};
+TopkLayout topk_layout(const adlhip_device* d, size_t key_bytes, size_t n, size_t k)
+{
+    TopkLayout L;
+    L.off_result = sizeof(adlhip::SelState);
+    L.off_x = L.off_result + align_up(k * 4, 256);
+    size_t o = L.off_x;
+    for (int i = 0; i < 2; ++i) {
+        L.off_codes[i] = o;
+        L.off_pos[i] = o + align_up(n * key_bytes, 256);
+        o = L.off_pos[i] + align_up(n * 4, 256);
+    }
+    const size_t lists_end = o;
+    L.off_ptmp = L.off_x;
+    L.off_keys = L.off_ptmp + align_up(k * 4, 256);
+    L.off_fwork = L.off_keys + align_up(k * key_bytes, 256);
+    L.fwork_bytes = std::max(sort_work_bytes(d, ADLHIP_ELEM_U32, k, 32, 1), soa_wide_layout(d, k).total);
+    const size_t select_total = std::max(lists_end, L.off_fwork + L.fwork_bytes);
+    L.awork_bytes = soa_wide_layout(d, n).total;
+    L.off_akeys = align_up(L.awork_bytes, 256);
+    L.off_aidx = L.off_akeys + align_up(n * key_bytes, 256);
+    L.total = std::max(select_total, L.off_aidx + align_up(n * 4, 256));
+    return L;
+}
+
+// digit `level` of the composite (code of `key_bits` bits, position of `pos_bits` bits), most significant first, 11 bits each but
+// for the last digit of either part
+adlhip::SelDigit topk_digit(int level, int key_bits, int pos_bits)
+{
+    const int key_levels = (key_bits + adlhip::kSelDigitBits - 1) / adlhip::kSelDigitBits;
+    const bool from_pos = level >= key_levels;
+    const int left = from_pos ? pos_bits - adlhip::kSelDigitBits * (level - key_levels) : key_bits - adlhip::kSelDigitBits * level;
+    if (left <= 0) return adlhip::SelDigit{0u, 0u, 0u};   // behind the last digit: everything counts as digit 0
+    const int bits = std::min(left, adlhip::kSelDigitBits);
+    return adlhip::SelDigit{from_pos ? 1u : 0u, (uint32_t)(left - bits), (1u << bits) - 1u};
+}
+
+// the full argsort into the work buffer, its first k entries to the caller
+template <typename U>
+int topk_by_sort(adlhip_device* d, int kind, int desc, const U* keys_in, U* keys_out, uint32_t* index_out, void* work, size_t n, size_t k)
+{
+    const TopkLayout L = topk_layout(d, sizeof(U), n, k);
+    char* w = static_cast<char*>(work);
+    U* akeys = reinterpret_cast<U*>(w + L.off_akeys);
+    uint32_t* aidx = reinterpret_cast<uint32_t*>(w + L.off_aidx);
+    const int rc = typed_index_sort<U, uint32_t>(d, kind, desc, keys_in, keys_out ? akeys : nullptr, nullptr, nullptr, aidx, work, n);
+    if (rc) return rc;
+    if (keys_out) HIPCHK(hipMemcpyAsync(keys_out, akeys, k * sizeof(U), hipMemcpyDeviceToDevice, d->stream));
+    if (index_out) HIPCHK(hipMemcpyAsync(index_out, aidx, k * 4, hipMemcpyDeviceToDevice, d->stream));
+    return ADLHIP_SUCCESS;
+}
+
+template <typename U>
+int topk_by_select(adlhip_device* d, int kind, int desc, const U* keys_in, U* keys_out, uint32_t* index_out, void* work, size_t n, size_t k)
+{
+    const TopkLayout L = topk_layout(d, sizeof(U), n, k);
+    char* w = static_cast<char*>(work);
+    adlhip::SelState* st = reinterpret_cast<adlhip::SelState*>(w);
+    uint32_t* result = reinterpret_cast<uint32_t*>(w + L.off_result);
+    U* codes[2] = {reinterpret_cast<U*>(w + L.off_codes[0]), reinterpret_cast<U*>(w + L.off_codes[1])};
+    uint32_t* pos[2] = {reinterpret_cast<uint32_t*>(w + L.off_pos[0]), reinterpret_cast<uint32_t*>(w + L.off_pos[1])};
+    const uint32_t nn = (uint32_t)n, kk = (uint32_t)k;
+    const int key_bits = 8 * (int)sizeof(U);
+    int pos_bits = 1;
+    while (pos_bits < 32 && ((size_t)1 << pos_bits) < n) ++pos_bits;
+    const int key_levels = (key_bits + adlhip::kSelDigitBits - 1) / adlhip::kSelDigitBits;
+    const int levels = key_levels + (pos_bits + adlhip::kSelDigitBits - 1) / adlhip::kSelDigitBits;   // <= kSelMaxLevels
+    constexpr size_t tile = (size_t)adlhip::kSelNT * adlhip::kSelVecs * (16 / sizeof(U));
+    const uint32_t wgs = (uint32_t)std::min<size_t>((n + tile - 1) / tile, (size_t)d->prop.multiProcessorCount * 8);
+
+    HIPCHK(hipMemsetAsync(st, 0, sizeof(adlhip::SelState), d->stream));   // the starting state, whatever the buffer held
+    int rc = launch(d, "select_hist", [&] {
+#define ADLHIP_SELH(KIND_, DESC_) \
+    hipLaunchKernelGGL((adlhip::select_hist_kernel<U, KIND_, DESC_>), dim3(wgs), dim3(adlhip::kSelNT), 0, d->stream, keys_in, nn, st, topk_digit(0, key_bits, pos_bits))
+        ADLHIP_TYPED_DISPATCH(kind, desc, ADLHIP_SELH);
+#undef ADLHIP_SELH
+    });
+    if (rc) return rc;
+    rc = launch(d, "select_filter_first", [&] {
+#define ADLHIP_SELF(KIND_, DESC_)                                                                                                   \
+    hipLaunchKernelGGL((adlhip::select_filter_kernel<U, KIND_, DESC_, 1>), dim3(wgs), dim3(adlhip::kSelNT), 0, d->stream, keys_in, \
+                       (const uint32_t*)nullptr, codes[1], pos[1], result, st, 1u, nn, kk, topk_digit(0, key_bits, pos_bits),       \
+                       topk_digit(1, key_bits, pos_bits))
+        ADLHIP_TYPED_DISPATCH(kind, desc, ADLHIP_SELF);
+#undef ADLHIP_SELF
+    });
+    if (rc) return rc;
+    for (int lv = 2; lv <= levels; ++lv) {   // the worst case; a level behind the one that completed the selection leaves at once
+        rc = launch(d, "select_filter", [&] {
+            hipLaunchKernelGGL((adlhip::select_filter_kernel<U, 0, 0, 0>), dim3(wgs), dim3(adlhip::kSelNT), 0, d->stream,
+                               (const U*)codes[(lv - 1) & 1], (const uint32_t*)pos[(lv - 1) & 1], codes[lv & 1], pos[lv & 1], result, st,
+                               (uint32_t)lv, nn, kk, topk_digit(lv - 1, key_bits, pos_bits), topk_digit(lv, key_bits, pos_bits));
+        });
+        if (rc) return rc;
+    }
+
+    // finish: the k positions ascending, their keys, then the stable typed pair sort of (key, position) -- stability and ascending
+    // positions give the tie order of the argsort
+    uint32_t* ptmp = reinterpret_cast<uint32_t*>(w + L.off_ptmp);
+    U* gkeys = reinterpret_cast<U*>(w + L.off_keys);
+    void* fwork = w + L.off_fwork;
+    rc = sort_entry<uint32_t>(d, ADLHIP_ELEM_U32, result, ptmp, fwork, L.fwork_bytes, k, 32, 32);
+    if (rc) return rc;
+    const uint32_t gwgs = (uint32_t)std::min<size_t>((k + adlhip::kSelNT - 1) / adlhip::kSelNT, (size_t)d->prop.multiProcessorCount * 16);
+    rc = launch(d, "select_gather", [&] {
+        hipLaunchKernelGGL((adlhip::select_gather_kernel<U>), dim3(gwgs), dim3(adlhip::kSelNT), 0, d->stream, keys_in, (const uint32_t*)result,
+                           gkeys, kk);
+    });
+    if (rc) return rc;
+    return typed_index_sort<U, uint32_t>(d, kind, desc, gkeys, keys_out, index_out ? result : nullptr, index_out, nullptr, fwork, k);
+}
+
 }  // namespace
 
 // ================================================================================================
@@ -2813,6 +2944,48 @@ int adlhip_argsort_typed(adlhip_device* d, int key_type, int order, const void* 
     return typed_index_sort<uint64_t, uint32_t>(d, t.kind, order, (const uint64_t*)keys_in, (uint64_t*)keys_out, nullptr, nullptr, index_out, work, n);
 }
 
+int adlhip_topk_scratch_bytes(adlhip_device* d, int key_type, size_t n, size_t k, size_t* work_bytes)
+{
+    if (!d) return fail("null device handle");
+    KeyTypeInfo t;
+    if (key_type_info(key_type, ADLHIP_ORDER_ASCENDING, &t)) return ADLHIP_FAILURE;
+    if (typed_check_n(n)) return ADLHIP_FAILURE;
+    if (k > n) return fail("top-k: k = %zu exceeds n = %zu", k, n);
+    if (work_bytes) *work_bytes = topk_layout(d, (size_t)t.bytes, n, k).total;
+    return ADLHIP_SUCCESS;
+}
+
+int adlhip_topk_typed(adlhip_device* d, int key_type, int order, const void* keys_in, size_t n, size_t k, void* keys_out,
+                      uint32_t* index_out, void* work, size_t work_bytes)
+{
+    if (bind(d)) return ADLHIP_FAILURE;
+    KeyTypeInfo t;
+    if (key_type_info(key_type, order, &t)) return ADLHIP_FAILURE;
+    if (typed_check_n(n)) return ADLHIP_FAILURE;
+    if (k > n) return fail("top-k: k = %zu exceeds n = %zu", k, n);
+    if (k == 0) return ADLHIP_SUCCESS;   // (n == 0 included)
+    if (!keys_out && !index_out) return fail("top-k: at least one of d_keys_out and d_index_out must be given");
+    if (!keys_in || !work) return fail("null buffer passed to top-k");
+    if ((reinterpret_cast<uintptr_t>(keys_in) | reinterpret_cast<uintptr_t>(keys_out) | reinterpret_cast<uintptr_t>(index_out) |
+         reinterpret_cast<uintptr_t>(work)) & 15u)
+        return fail("top-k buffers must be 16-byte aligned");
+    const char* in0 = static_cast<const char*>(keys_in);
+    const char* in1 = in0 + n * (size_t)t.bytes;
+    const char* ko = static_cast<const char*>(keys_out);
+    const char* io = reinterpret_cast<const char*>(index_out);
+    if ((ko && ko < in1 && in0 < ko + k * (size_t)t.bytes) || (io && io < in1 && in0 < io + k * 4))
+        return fail("top-k: the outputs must not overlap d_keys_in");
+    const size_t need = topk_layout(d, (size_t)t.bytes, n, k).total;
+    if (work_bytes < need) return fail("work buffer too small: %zu < %zu (adlhip_topk_scratch_bytes)", work_bytes, need);
+    const bool select = d->topk_algo < 0 ? k <= n / kTopkSelectMaxFraction : d->topk_algo == 1;
+#define ADLHIP_TOPK(U_)                                                                                                             \
+    return select ? topk_by_select<U_>(d, t.kind, order, (const U_*)keys_in, (U_*)keys_out, index_out, work, n, k)                  \
+                  : topk_by_sort<U_>(d, t.kind, order, (const U_*)keys_in, (U_*)keys_out, index_out, work, n, k)
+    if (t.bytes == 4) ADLHIP_TOPK(uint32_t);
+    ADLHIP_TOPK(uint64_t);
+#undef ADLHIP_TOPK
+}
+
 int adlhip_segment_sort(adlhip_device* d, int elem_kind, void* data, const uint32_t* seg_start, size_t num_segments,
                         size_t max_segment, int low_bits)
 {
@@ -2961,6 +3134,9 @@ int adlhip_set_param(adlhip_device* d, const char* name, int value)
     } else if (!strcmp(name, "sort.binfinish")) {
         if (value < 0 || value > 2) return fail("sort.binfinish must be 0 (LSD finish), 1 (binning finish for whole u64 keys from 24 Mi keys up) or 2 (always, u32 keys too)");
         d->bin_finish = value;
+    } else if (!strcmp(name, "topk.algo")) {
+        if (value < -1 || value > 1) return fail("topk.algo must be -1 (by k), 0 (always the full argsort) or 1 (always the selection)");
+        d->topk_algo = value;
     } else if (!strcmp(name, "debug.resident_wgs")) {
         // what the paths with a grid-wide barrier (the safety nets) and the one-workgroup-per-bucket finish may count on;
         // 0 = ask the device again.  Tests use it to stand in for a small partition.
@@ -3001,6 +3177,7 @@ int adlhip_get_param(adlhip_device* d, const char* name, int* value)
     else if (!strcmp(name, "sort.binfinish")) *value = d->bin_finish;
     else if (!strcmp(name, "sort.persist")) *value = d->persist;
     else if (!strcmp(name, "sort.dict")) *value = d->dict_path;
+    else if (!strcmp(name, "topk.algo")) *value = d->topk_algo;
     else if (!strcmp(name, "partition.lookback")) *value = d->partition_lookback;
     else if (!strcmp(name, "sort.net_lookback")) *value = d->net_lookback;
     else if (!strcmp(name, "debug.resident_wgs")) *value = d->resident_wgs;

@@ -13,6 +13,11 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+// non-template kernels: external linkage in adlhip.hip, internal in the units that only instantiate kernel templates (radix_kernels.hpp)
+#ifndef ADLHIP_KERNEL
+#define ADLHIP_KERNEL
+#endif
+
 namespace adlhip {
 
 constexpr int kSoaNT = 256;
@@ -27,8 +32,9 @@ __global__ __launch_bounds__(kSoaNT) void soa_pack_index_kernel(const K* __restr
 }
 
 // second round of 64-bit keys: out[j] = {high dword of keys[idx], idx}, idx = the index in[j] carries
-__global__ __launch_bounds__(kSoaNT) void soa_repack_high_kernel(const uint64_t* __restrict__ keys, const uint64_t* __restrict__ in,
-                                                                 uint64_t* __restrict__ out, uint32_t n)
+ADLHIP_KERNEL __global__ __launch_bounds__(kSoaNT) void soa_repack_high_kernel(const uint64_t* __restrict__ keys,
+                                                                               const uint64_t* __restrict__ in,
+                                                                               uint64_t* __restrict__ out, uint32_t n)
 {
     const uint32_t stride = gridDim.x * (uint32_t)kSoaNT;
     for (uint32_t j = blockIdx.x * (uint32_t)kSoaNT + threadIdx.x; j < n; j += stride) {

@@ -8,6 +8,7 @@
     p.sortKeys(device, buffer, n, descending=False)        # uint32 / int32 / float32 / uint64 / int64 / float64 keys
     p.sortPairs(device, keys, values, n, descending=False) # the same keys with values of 4, 8 or 16 bytes, stable
     p.argsort(device, keys, n, descending=False)           # -> Buffer(uint32): the stable sorting permutation
+    p.topk(device, keys, n, k, descending=False)           # -> Buffer(uint32): its first k entries, by selection
 
 Like the reference object it owns lazily grown device scratch (m_u32WorkBuffer[0] = ping-pong data
 buffer, m_u32WorkBuffer[1] = histogram table; Pprims.h:44-45, Pprims.cpp:226-232, :332-337) and must be
@@ -194,6 +195,34 @@ class Pprims:
             check(_lib.load().adlhip_argsort_typed(device._h, kt, 1 if descending else 0, keys.ptr(),
                                                    keysOut.ptr() if keysOut is not None else None, out.ptr(), self.m_work.ptr(),
                                                    self.m_work.getSize(), n), "argsort")
+        except AdlHipError:
+            if indexOut is None:
+                out.release()
+            raise
+        return out
+
+    def topk(self, device, keys, n, k, descending=False, keysOut=None, indexOut=None):
+        """Returns a Buffer(uint32) with the first k entries of argsort(device, keys, n, descending): the positions of the k smallest
+        (descending: largest) of the first n keys, sorted, ties by ascending position.  `keys` is left intact; keysOut (same dtype,
+        k elements, not `keys`) receives the k keys.  indexOut: a uint32 buffer of k elements to fill and return instead of a new one."""
+        if device is None:
+            raise AdlHipError("topk needs a device")
+        kt = self._key_type(keys, "topk")
+        n, k = int(n), int(k)
+        if k < 0 or k > n:
+            raise AdlHipError("topk: k = %d outside [0, n = %d]" % (k, n))
+        if keysOut is not None and (np.dtype(keysOut.dtype) != np.dtype(keys.dtype) or keysOut.getSize() < k):
+            raise AdlHipError("topk: keysOut must hold k elements of %s" % keys.dtype)
+        if indexOut is not None and (np.dtype(indexOut.dtype) != np.uint32 or indexOut.getSize() < k):
+            raise AdlHipError("topk: indexOut must hold k uint32 elements")
+        wb = ctypes.c_size_t()
+        check(_lib.load().adlhip_topk_scratch_bytes(device._h, kt, n, k, ctypes.byref(wb)), "adlhip_topk_scratch_bytes")
+        self._scratch(device, 0, wb.value)
+        out = indexOut if indexOut is not None else Buffer(device, k, np.uint32)
+        try:
+            check(_lib.load().adlhip_topk_typed(device._h, kt, 1 if descending else 0, keys.ptr(), n, k,
+                                                keysOut.ptr() if keysOut is not None else None, out.ptr(), self.m_work.ptr(),
+                                                self.m_work.getSize()), "topk")
         except AdlHipError:
             if indexOut is None:
                 out.release()

@@ -4,6 +4,7 @@ back-end on torch's own stream.
     s = TorchSorter()                       # one adlhip_device on the stream that is torch's current one NOW + its scratch
     values, indices = s.sort(t)             # t: 1-D CUDA tensor, int32 / int64 / float32 / float64
     indices = s.argsort(t, descending=True)
+    values, indices = s.topk(t, 10)         # the 10 largest, largest first; ties to the lower index
     s.close()
 
 Always out of place and always stable.  The ONE difference from `torch.sort(t, stable=True)`: floats are ordered by
@@ -87,6 +88,27 @@ class TorchSorter:
         p.argsort(self.device, self._wrap(src, npdt), n, descending=descending,
                   keysOut=self._wrap(values, npdt) if want_values else None, indexOut=lib_idx)
         # the stream is synchronised by torch, never by adlhip_sync: pick up device-side faults of earlier, completed sorts
+        self.device.checkFault()
+        return values, idx32.to(torch.int64) & 0xffffffff
+
+    def topk(self, t, k, largest=True, sorted=True):
+        """(values, indices) like torch.topk(t, k, largest=largest, sorted=True); indices are int64.  sorted=False is accepted and
+        still returns sorted output.  Ties go to the lower index: indices equal
+        torch.sort(t, descending=largest, stable=True).indices[:k] (torch.topk leaves the tie order unspecified)."""
+        self._check(t)
+        if torch.cuda.current_stream(self.torch_device).cuda_stream != self.raw_stream:
+            raise RuntimeError("TorchSorter: bound to the stream that was current at construction; another stream is current now")
+        n, k = t.numel(), int(k)
+        if k < 0 or k > n:
+            raise ValueError("TorchSorter.topk: k = %d outside [0, numel = %d]" % (k, n))
+        values = torch.empty(k, dtype=t.dtype, device=t.device)
+        if k == 0:
+            return values, torch.empty(0, dtype=torch.int64, device=t.device)
+        src = t.contiguous()
+        npdt = _NP_DTYPE[t.dtype]
+        idx32 = torch.empty(k, dtype=torch.int32, device=t.device)   # uint32 positions in an int32 tensor
+        self.pprims.topk(self.device, self._wrap(src, npdt), n, k, descending=bool(largest), keysOut=self._wrap(values, npdt),
+                         indexOut=self._wrap(idx32, np.uint32))
         self.device.checkFault()
         return values, idx32.to(torch.int64) & 0xffffffff
 

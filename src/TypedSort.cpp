@@ -1,7 +1,8 @@
 // Pprims::sortKeys / Pprims::argsort: signed, floating-point and descending keys (no reference counterpart; the reference sorts
 // u32 bit patterns, ascending: Tahoe/ParallelPrimitives/Pprims.h:38-41).  A TYPE_CL (HIP) device runs adlhip_sort_keys_typed /
 // adlhip_argsort_typed; a TYPE_HOST device sorts on the CPU with std::stable_sort on the same total order, as the reference's
-// host branches do for u32 keys (Pprims.cpp:202-212, :306-316).
+// host branches do for u32 keys (Pprims.cpp:202-212, :306-316).  Pprims::topK: adlhip_topk_typed, or a partial sort on (ordinal,
+// position) on the host.
 #include <Tahoe/ParallelPrimitives/Pprims.h>
 
 #include <algorithm>
@@ -122,6 +123,51 @@ void Pprims::argsortTyped(const adl::Device* device, const adl::Buffer<T>& keys,
     ADLASSERT(rc == ADLHIP_SUCCESS);
 }
 
+template <typename T>
+void Pprims::topKTyped(const adl::Device* device, const adl::Buffer<T>& keys, adl::Buffer<T>& keysOut, adl::Buffer<u32>& indexOut, int n, int k,
+                       bool descending)
+{
+    ADLASSERT(n >= 0 && k >= 0 && k <= n);
+    if (n <= 0 || k <= 0 || k > n) return;
+    ADLASSERT(device != 0);
+    ADLASSERT((adl::u64)n <= keys.getSize() && (adl::u64)k <= keysOut.getSize() && (adl::u64)k <= indexOut.getSize());
+    if (!onDevice(device)) {
+        ADLASSERT(device->getType() == adl::TYPE_HOST);   // a HIP device never falls back to the CPU
+        if (device->getType() != adl::TYPE_HOST) return;
+        typedef Ranked<typename KeyTraits<T>::Bits> R;
+        T* host = keys.getHostPtr(n);
+        T* kout = keysOut.getHostPtr(k);
+        u32* out = indexOut.getHostPtr(k);
+        adl::DeviceUtils::waitForCompletion(device);
+        std::vector<R> order((size_t)n);
+        for (int i = 0; i < n; ++i) {
+            order[i].ord = ordinal(host[i], descending);
+            order[i].idx = (u32)i;
+        }
+        // all (ordinal, position) composites are distinct, so the partial sort needs no stability
+        std::partial_sort(order.begin(), order.begin() + k, order.end(),
+                          [](const R& a, const R& b) { return a.ord != b.ord ? a.ord < b.ord : a.idx < b.idx; });
+        for (int j = 0; j < k; ++j) {
+            out[j] = order[j].idx;
+            kout[j] = host[order[j].idx];
+        }
+        keys.returnHostPtr(host);
+        keysOut.returnHostPtr(kout);
+        indexOut.returnHostPtr(out);
+        adl::DeviceUtils::waitForCompletion(device);
+        return;
+    }
+    size_t wb = 0;
+    const int rcq = adlhip_topk_scratch_bytes(device->hip(), KeyTraits<T>::TYPE, (size_t)n, (size_t)k, &wb);
+    ADLASSERT(rcq == ADLHIP_SUCCESS);
+    reserve(device, 0, wb);
+    const int rc = adlhip_topk_typed(device->hip(), KeyTraits<T>::TYPE, descending ? ADLHIP_ORDER_DESCENDING : ADLHIP_ORDER_ASCENDING,
+                                     keys.m_ptr, (size_t)n, (size_t)k, keysOut.m_ptr, (uint32_t*)indexOut.m_ptr, m_work->m_ptr,
+                                     (size_t)m_work->getSize());
+    if (rc != ADLHIP_SUCCESS) TH_LOG_ERROR("Pprims::topK: %s\n", adlhip_last_error());
+    ADLASSERT(rc == ADLHIP_SUCCESS);
+}
+
 #define TAHOE_TYPED(T)                                                                                                              \
     void Pprims::sortKeys(const adl::Device* device, const adl::Buffer<T>& inout, int n, bool descending)                         \
     {                                                                                                                               \
@@ -130,6 +176,11 @@ void Pprims::argsortTyped(const adl::Device* device, const adl::Buffer<T>& keys,
     void Pprims::argsort(const adl::Device* device, const adl::Buffer<T>& keys, adl::Buffer<u32>& indexOut, int n, bool descending) \
     {                                                                                                                               \
         argsortTyped<T>(device, keys, indexOut, n, descending);                                                                     \
+    }                                                                                                                               \
+    void Pprims::topK(const adl::Device* device, const adl::Buffer<T>& keys, adl::Buffer<T>& keysOut, adl::Buffer<u32>& indexOut,  \
+                      int n, int k, bool descending)                                                                                \
+    {                                                                                                                               \
+        topKTyped<T>(device, keys, keysOut, indexOut, n, k, descending);                                                            \
     }
 TAHOE_TYPED(int)
 TAHOE_TYPED(float)
