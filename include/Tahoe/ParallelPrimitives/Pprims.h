@@ -7,6 +7,7 @@
 //   copy / fill                                                      (reference Pprims.cpp:31-120, commented out there)
 //   sortKeys / argsort  signed, float and descending keys            (new: adlhip_sort_keys_typed / adlhip_argsort_typed)
 //   topK      the first k entries of argsort, by selection           (new: adlhip_topk_typed)
+//   topKRows  topK of every row of a rows x cols matrix              (new: adlhip_topk_rows_typed)
 // Same argument meaning; differences, all supersets: any n >= 0 (the reference needs n % 256 == 0 for
 // keys), scan has no 1,048,576-element limit, sortBits < 32 also works on 64-bit keys up to 64.
 // Device work is enqueued and the call returns (no sync), as in the reference's GPU branches.
@@ -99,8 +100,25 @@ public:
               bool descending = false);
     void topK(const adl::Device* device, const adl::Buffer<u64>& keys, adl::Buffer<u64>& keysOut, adl::Buffer<u32>& indexOut, int n, int k,
               bool descending = false);
+    // topK of every row of a rows x cols matrix, row r at element r * rowStride (0: cols): indexOut[r * k + j] = column of the j-th
+    // smallest (descending: largest) key of row r, ties by ascending column; keysOut[r * k + j] = that key.  keys is left intact.  A
+    // TYPE_HOST device partially sorts (ordinal, column) per row on the CPU
+    void topKRows(const adl::Device* device, const adl::Buffer<int>& keys, adl::Buffer<int>& keysOut, adl::Buffer<u32>& indexOut, int rows,
+                  int cols, int k, bool descending = false, int rowStride = 0);
+    void topKRows(const adl::Device* device, const adl::Buffer<float>& keys, adl::Buffer<float>& keysOut, adl::Buffer<u32>& indexOut, int rows,
+                  int cols, int k, bool descending = false, int rowStride = 0);
+    void topKRows(const adl::Device* device, const adl::Buffer<long long>& keys, adl::Buffer<long long>& keysOut, adl::Buffer<u32>& indexOut, int rows,
+                  int cols, int k, bool descending = false, int rowStride = 0);
+    void topKRows(const adl::Device* device, const adl::Buffer<double>& keys, adl::Buffer<double>& keysOut, adl::Buffer<u32>& indexOut, int rows,
+                  int cols, int k, bool descending = false, int rowStride = 0);
+    void topKRows(const adl::Device* device, const adl::Buffer<u32>& keys, adl::Buffer<u32>& keysOut, adl::Buffer<u32>& indexOut, int rows,
+                  int cols, int k, bool descending = false, int rowStride = 0);
+    void topKRows(const adl::Device* device, const adl::Buffer<u64>& keys, adl::Buffer<u64>& keysOut, adl::Buffer<u32>& indexOut, int rows,
+                  int cols, int k, bool descending = false, int rowStride = 0);
 
 private:
+    template <typename T> void topKRowsTyped(const adl::Device* device, const adl::Buffer<T>& keys, adl::Buffer<T>& keysOut, adl::Buffer<u32>& indexOut,
+                                             int rows, int cols, int k, bool descending, int rowStride);
     template <typename T> void topKTyped(const adl::Device* device, const adl::Buffer<T>& keys, adl::Buffer<T>& keysOut, adl::Buffer<u32>& indexOut, int n,
                                          int k, bool descending);
     template <typename T> void sortKeysTyped(const adl::Device* device, const adl::Buffer<T>& inout, int n, bool descending);

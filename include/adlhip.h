@@ -289,6 +289,32 @@ int adlhip_topk_scratch_bytes(adlhip_device* dev, int key_type, size_t n, size_t
 int adlhip_topk_typed(adlhip_device* dev, int key_type, int order, const void* d_keys_in, size_t n, size_t k,
                       void* d_keys_out_or_null, uint32_t* d_index_out_or_null, void* d_work, size_t work_bytes);
 
+/* Work bytes of adlhip_topk_rows_typed: one size for both of its paths -- what adlhip_topk_scratch_bytes(dev, key_type, cols, k) reports,
+ * the need of the per-row loop; the rows share it.  The row kernel uses no global scratch and never touches d_work. */
+int adlhip_topk_rows_scratch_bytes(adlhip_device* dev, int key_type, size_t rows, size_t cols, size_t k, size_t* work_bytes);
+
+/* Top-k along the rows of a rows x cols matrix: for every row r < rows the output row is exactly the first k entries of
+ * adlhip_argsort_typed applied to that row alone (same key order, NaN and -0 included; ties go to the lower column in both orders).
+ * Row r of the input starts at element r * row_stride (row_stride in elements, >= cols); the outputs are dense rows x k, row-major:
+ * d_index_out[r * k + j] = the COLUMN of the j-th element of row r, d_keys_out[r * k + j] = its key, bit for bit.
+ * Only the base pointers (d_keys_in, the outputs, d_work) need 16-byte alignment: a row may start at any element, cols and row_stride
+ * may be odd.  d_keys_in is never written; the elements between cols and row_stride are never read either.  At least one output must
+ * be given and neither may overlap the input.  0 <= k <= cols < 2^32; k == 0 or rows == 0 succeeds and enqueues nothing.  k > cols,
+ * row_stride < cols, a misaligned base pointer, both outputs NULL, an output overlapping the input, an unknown key type or order, or
+ * work_bytes below adlhip_topk_rows_scratch_bytes fail before anything is enqueued.  Enqueues and returns; nothing data-dependent
+ * reaches the host and nothing is remembered between calls (the handle owns no device word of it).
+ * Two paths ("topk.rows_algo"), the same result bit for bit:
+ *   the row kernel (k <= 2048): one workgroup of 256 threads per row, workgroups take rows in turns; everything lives in LDS (4096
+ *     composites {encoded key, column} + a 2048-bin histogram).  cols <= 4096: the row is read once, sorted in LDS, its first k
+ *     written.  Longer rows: radix select on the composite in the 11-bit digits of adlhip_topk_typed -- each level re-reads the row
+ *     (from L2) and counts one digit -- until the certain items and the chosen bin together fit the 4096 slots, one collecting read,
+ *     then the same sort.  No global scratch, no atomics to global memory, no workgroup depends on another.
+ *   the per-row loop: `rows` runs of adlhip_topk_typed's own paths ("topk.algo" decides per row as there) on the shared d_work, in
+ *     stream order.  Correct for every shape; rows * (a dozen launches or more). */
+int adlhip_topk_rows_typed(adlhip_device* dev, int key_type, int order, const void* d_keys_in, size_t rows, size_t cols,
+                           size_t row_stride, size_t k, void* d_keys_out_or_null, uint32_t* d_index_out_or_null,
+                           void* d_work, size_t work_bytes);
+
 /* ---- segments finished in LDS (no reference counterpart) ------------------------------------- */
 
 /* Sorts, stably and in place, every segment [d_seg_start[s], d_seg_start[s + 1]) of an array of u32 keys
@@ -440,6 +466,12 @@ int adlhip_generate_keys(adlhip_device* dev, int elem_kind, void* dptr, size_t n
  *   "topk.algo"        -1 [default] / 0 / 1: adlhip_topk_typed selects (radix select + a k-element finish) while k <= n / 8 and runs
  *                      the full argsort above; 0 always runs the argsort and copies its first k, 1 always selects (tests,
  *                      measurements).  The same result bit for bit either way
+ *   "topk.rows_algo"   -1 [default] / 0 / 1: adlhip_topk_rows_typed runs its row kernel while k <= 2048 and cols <= 256 Ki and the
+ *                      per-row loop otherwise; 0 always loops, 1 always runs the row kernel (k > 2048 is then refused).  The 256 Ki
+ *                      is a PLACEHOLDER: where one workgroup per row starts to lose to the loop has not been measured
+ *                      (tools/topk_rows_bench.py measures it).  The same result bit for bit either way
+ *   "debug.topk_rows_grid" workgroups the row kernel is launched with at most (0 [default]: 4 per CU); tests set it to make few
+ *                      workgroups take many rows in turns
  *   "sort.net_lookback" 1 [default] / 0: the LSD passes of the large sort's safety net on whole keys are look-back passes -- the
  *                      one-sweep path's histogram, tables and tile body, taken in turns by the net's resident workgroups, four
  *                      passes at a time (u64 keys: two rounds) -- instead of count -> scan -> scatter passes with per-workgroup

@@ -26,6 +26,7 @@
 #include "soa_wide_kernels.hpp"
 #include "typed_kernels.hpp"
 #include "select_kernels.hpp"
+#include "toprows_kernels.hpp"
 
 // The large sort's kernels and the per-digit passes' are instantiated in kernels_finish.hip / kernels_passes.hip / kernels_perdigit.hip (translation units of
 // their own, compiled beside this one); here they are only declared.  -DADLHIP_SINGLE_TU builds everything in this file (what tools/gen_large_kernels.py reads the list from).
@@ -36,6 +37,7 @@
 #include "passes_kernels.inc"
 #include "perdigit_kernels.inc"
 #include "select_kernels.inc"
+#include "toprows_kernels.inc"
 #undef X
 #endif
 
@@ -116,6 +118,9 @@ struct adlhip_device {
                                             // 256 values (dict_kernels.hpp); 0 = off
     int topk_algo = -1;                     // "topk.algo": -1 selection up to kTopkSelectMaxFraction of n, the full argsort above; 0 / 1 force
                                             // the argsort / the selection
+    int topk_rows_algo = -1;                // "topk.rows_algo": -1 the row kernel while k <= kRowMaxK and cols <= kTopkRowsMaxCols, the per-row
+                                            // loop above; 0 / 1 force the loop / the row kernel
+    int topk_rows_grid = 0;                 // "debug.topk_rows_grid": workgroups of the row kernel at most (0: kTopkRowsWgsPerCu per CU)
     adlhip::DictBlock* d_dict = nullptr;    // its dictionary and counters (handle-owned; rebuilt by every net that uses them)
     uint32_t* d_msd2 = nullptr;   // the large sort's handle-owned words, allocated with the handle: cursors of pass 1 (256, one
                                   // 128-byte line each) and pass 2 (65536), overflow flag, done counter, the safety net's barrier
@@ -2226,8 +2231,11 @@ int topk_by_sort(adlhip_device* d, int kind, int desc, const U* keys_in, U* keys
     return ADLHIP_SUCCESS;
 }
 
+// keys_in need not be 16-byte aligned when stage_keys is set: the two kernels that load the keys in 16-byte vectors then read a copy
+// of them in the first survivor list (dead until level 2 writes it, by which time both have run); the gather reads keys_in itself
 template <typename U>
-int topk_by_select(adlhip_device* d, int kind, int desc, const U* keys_in, U* keys_out, uint32_t* index_out, void* work, size_t n, size_t k)
+int topk_by_select(adlhip_device* d, int kind, int desc, const U* keys_in, U* keys_out, uint32_t* index_out, void* work, size_t n, size_t k,
+                   bool stage_keys = false)
 {
     const TopkLayout L = topk_layout(d, sizeof(U), n, k);
     char* w = static_cast<char*>(work);
@@ -2245,16 +2253,21 @@ int topk_by_select(adlhip_device* d, int kind, int desc, const U* keys_in, U* ke
     const uint32_t wgs = (uint32_t)std::min<size_t>((n + tile - 1) / tile, (size_t)d->prop.multiProcessorCount * 8);
 
     HIPCHK(hipMemsetAsync(st, 0, sizeof(adlhip::SelState), d->stream));   // the starting state, whatever the buffer held
+    const U* keys_vec = keys_in;
+    if (stage_keys) {
+        HIPCHK(hipMemcpyAsync(codes[0], keys_in, n * sizeof(U), hipMemcpyDeviceToDevice, d->stream));
+        keys_vec = codes[0];
+    }
     int rc = launch(d, "select_hist", [&] {
 #define ADLHIP_SELH(KIND_, DESC_) \
-    hipLaunchKernelGGL((adlhip::select_hist_kernel<U, KIND_, DESC_>), dim3(wgs), dim3(adlhip::kSelNT), 0, d->stream, keys_in, nn, st, topk_digit(0, key_bits, pos_bits))
+    hipLaunchKernelGGL((adlhip::select_hist_kernel<U, KIND_, DESC_>), dim3(wgs), dim3(adlhip::kSelNT), 0, d->stream, keys_vec, nn, st, topk_digit(0, key_bits, pos_bits))
         ADLHIP_TYPED_DISPATCH(kind, desc, ADLHIP_SELH);
 #undef ADLHIP_SELH
     });
     if (rc) return rc;
     rc = launch(d, "select_filter_first", [&] {
 #define ADLHIP_SELF(KIND_, DESC_)                                                                                                   \
-    hipLaunchKernelGGL((adlhip::select_filter_kernel<U, KIND_, DESC_, 1>), dim3(wgs), dim3(adlhip::kSelNT), 0, d->stream, keys_in, \
+    hipLaunchKernelGGL((adlhip::select_filter_kernel<U, KIND_, DESC_, 1>), dim3(wgs), dim3(adlhip::kSelNT), 0, d->stream, keys_vec, \
                        (const uint32_t*)nullptr, codes[1], pos[1], result, st, 1u, nn, kk, topk_digit(0, key_bits, pos_bits),       \
                        topk_digit(1, key_bits, pos_bits))
         ADLHIP_TYPED_DISPATCH(kind, desc, ADLHIP_SELF);
@@ -2284,6 +2297,53 @@ int topk_by_select(adlhip_device* d, int kind, int desc, const U* keys_in, U* ke
     });
     if (rc) return rc;
     return typed_index_sort<U, uint32_t>(d, kind, desc, gkeys, keys_out, index_out ? result : nullptr, index_out, nullptr, fwork, k);
+}
+
+// ---- row-wise top-k (toprows_kernels.hpp; no reference counterpart) ---------------------------------------------------------------
+// "topk.rows_algo" = -1: the row kernel while k <= kRowMaxK and cols <= kTopkRowsMaxCols.  One workgroup streaming a very long row
+// loses to the per-row loop, which puts the whole device on each row; where has NOT been measured (tools/topk_rows_bench.py measures
+// it): 256 Ki is a placeholder, as kTopkSelectMaxFraction is.
+constexpr size_t kTopkRowsMaxCols = size_t(256) << 10;
+constexpr int kTopkRowsWgsPerCu = 4;   // default grid of the row kernel per CU (its LDS admits 3 workgroups of 4-byte keys, 2 of 8-byte keys)
+
+// the per-row loop: `rows` 1-D top-k calls on the shared work buffer, in stream order
+template <typename U>
+int topk_rows_loop(adlhip_device* d, int kind, int desc, const U* keys_in, size_t rows, size_t cols, size_t row_stride, size_t k,
+                   U* keys_out, uint32_t* index_out, void* work)
+{
+    const bool select = d->topk_algo < 0 ? k <= cols / kTopkSelectMaxFraction : d->topk_algo == 1;
+    for (size_t r = 0; r < rows; ++r) {
+        const U* row = keys_in + r * row_stride;
+        U* ko = keys_out ? keys_out + r * k : nullptr;
+        uint32_t* io = index_out ? index_out + r * k : nullptr;
+        // (the selection loads its keys in 16-byte vectors; a row that starts elsewhere is staged.  The argsort reads key by key.)
+        const int rc = select ? topk_by_select<U>(d, kind, desc, row, ko, io, work, cols, k, (reinterpret_cast<uintptr_t>(row) & 15u) != 0)
+                              : topk_by_sort<U>(d, kind, desc, row, ko, io, work, cols, k);
+        if (rc) return rc;
+    }
+    return ADLHIP_SUCCESS;
+}
+
+template <typename U>
+int topk_rows_kernel_path(adlhip_device* d, int kind, int desc, const U* keys_in, size_t rows, size_t cols, size_t row_stride, size_t k,
+                          U* keys_out, uint32_t* index_out)
+{
+    adlhip::RowPlan plan;
+    const int key_bits = 8 * (int)sizeof(U);
+    int pos_bits = 1;
+    while (pos_bits < 32 && ((size_t)1 << pos_bits) < cols) ++pos_bits;
+    const int key_levels = (key_bits + adlhip::kSelDigitBits - 1) / adlhip::kSelDigitBits;
+    plan.levels = (uint32_t)(key_levels + (pos_bits + adlhip::kSelDigitBits - 1) / adlhip::kSelDigitBits);   // <= kSelMaxLevels
+    for (int lv = 0; lv < adlhip::kSelMaxLevels; ++lv) plan.d[lv] = topk_digit(lv, key_bits, pos_bits);
+    const size_t cap = d->topk_rows_grid > 0 ? (size_t)d->topk_rows_grid : (size_t)d->prop.multiProcessorCount * kTopkRowsWgsPerCu;
+    const uint32_t wgs = (uint32_t)std::min(rows, cap);
+    return launch(d, sizeof(U) == 4 ? "topk_rows_k32" : "topk_rows_k64", [&] {
+#define ADLHIP_ROWS(KIND_, DESC_)                                                                                                   \
+    hipLaunchKernelGGL((adlhip::topk_rows_kernel<U, KIND_, DESC_>), dim3(wgs), dim3(adlhip::kSelNT), 0, d->stream, keys_in, rows,  \
+                       (uint32_t)cols, row_stride, (uint32_t)k, keys_out, index_out, plan)
+        ADLHIP_TYPED_DISPATCH(kind, desc, ADLHIP_ROWS);
+#undef ADLHIP_ROWS
+    });
 }
 
 }  // namespace
@@ -2986,6 +3046,50 @@ int adlhip_topk_typed(adlhip_device* d, int key_type, int order, const void* key
 #undef ADLHIP_TOPK
 }
 
+int adlhip_topk_rows_scratch_bytes(adlhip_device* d, int key_type, size_t rows, size_t cols, size_t k, size_t* work_bytes)
+{
+    (void)rows;   // the rows share one work buffer
+    return adlhip_topk_scratch_bytes(d, key_type, cols, k, work_bytes);
+}
+
+int adlhip_topk_rows_typed(adlhip_device* d, int key_type, int order, const void* keys_in, size_t rows, size_t cols, size_t row_stride,
+                           size_t k, void* keys_out, uint32_t* index_out, void* work, size_t work_bytes)
+{
+    if (bind(d)) return ADLHIP_FAILURE;
+    KeyTypeInfo t;
+    if (key_type_info(key_type, order, &t)) return ADLHIP_FAILURE;
+    if (typed_check_n(cols)) return ADLHIP_FAILURE;
+    if (k > cols) return fail("top-k of rows: k = %zu exceeds cols = %zu", k, cols);
+    if (row_stride < cols) return fail("top-k of rows: row_stride = %zu is below cols = %zu", row_stride, cols);
+    if (k == 0 || rows == 0) return ADLHIP_SUCCESS;   // (cols == 0 included)
+    if (!keys_out && !index_out) return fail("top-k of rows: at least one of d_keys_out and d_index_out must be given");
+    if (!keys_in || !work) return fail("null buffer passed to top-k of rows");
+    if ((reinterpret_cast<uintptr_t>(keys_in) | reinterpret_cast<uintptr_t>(keys_out) | reinterpret_cast<uintptr_t>(index_out) |
+         reinterpret_cast<uintptr_t>(work)) & 15u)
+        return fail("top-k buffers must be 16-byte aligned");
+    size_t in_elems = 0, out_elems = 0;
+    if (__builtin_mul_overflow(rows - 1, row_stride, &in_elems) || __builtin_add_overflow(in_elems, cols, &in_elems) ||
+        in_elems > (SIZE_MAX >> 4) || __builtin_mul_overflow(rows, k, &out_elems) || out_elems > (SIZE_MAX >> 4))
+        return fail("top-k of rows: rows = %zu with row_stride = %zu, k = %zu is beyond the address space", rows, row_stride, k);
+    const char* in0 = static_cast<const char*>(keys_in);
+    const char* in1 = in0 + in_elems * (size_t)t.bytes;
+    const char* ko = static_cast<const char*>(keys_out);
+    const char* io = reinterpret_cast<const char*>(index_out);
+    if ((ko && ko < in1 && in0 < ko + out_elems * (size_t)t.bytes) || (io && io < in1 && in0 < io + out_elems * 4))
+        return fail("top-k of rows: the outputs must not overlap d_keys_in");
+    const size_t need = topk_layout(d, (size_t)t.bytes, cols, k).total;
+    if (work_bytes < need) return fail("work buffer too small: %zu < %zu (adlhip_topk_rows_scratch_bytes)", work_bytes, need);
+    if (d->topk_rows_algo == 1 && k > (size_t)adlhip::kRowMaxK)
+        return fail("top-k of rows: the row kernel (\"topk.rows_algo\" = 1) serves k <= %d, got %zu", adlhip::kRowMaxK, k);
+    const bool kernel = d->topk_rows_algo < 0 ? k <= (size_t)adlhip::kRowMaxK && cols <= kTopkRowsMaxCols : d->topk_rows_algo == 1;
+#define ADLHIP_TOPK_ROWS(U_)                                                                                                        \
+    return kernel ? topk_rows_kernel_path<U_>(d, t.kind, order, (const U_*)keys_in, rows, cols, row_stride, k, (U_*)keys_out, index_out) \
+                  : topk_rows_loop<U_>(d, t.kind, order, (const U_*)keys_in, rows, cols, row_stride, k, (U_*)keys_out, index_out, work)
+    if (t.bytes == 4) ADLHIP_TOPK_ROWS(uint32_t);
+    ADLHIP_TOPK_ROWS(uint64_t);
+#undef ADLHIP_TOPK_ROWS
+}
+
 int adlhip_segment_sort(adlhip_device* d, int elem_kind, void* data, const uint32_t* seg_start, size_t num_segments,
                         size_t max_segment, int low_bits)
 {
@@ -3137,6 +3241,12 @@ int adlhip_set_param(adlhip_device* d, const char* name, int value)
     } else if (!strcmp(name, "topk.algo")) {
         if (value < -1 || value > 1) return fail("topk.algo must be -1 (by k), 0 (always the full argsort) or 1 (always the selection)");
         d->topk_algo = value;
+    } else if (!strcmp(name, "topk.rows_algo")) {
+        if (value < -1 || value > 1) return fail("topk.rows_algo must be -1 (by k and cols), 0 (always the per-row loop) or 1 (always the row kernel)");
+        d->topk_rows_algo = value;
+    } else if (!strcmp(name, "debug.topk_rows_grid")) {
+        if (value < 0) return fail("debug.topk_rows_grid must be >= 0");
+        d->topk_rows_grid = value;
     } else if (!strcmp(name, "debug.resident_wgs")) {
         // what the paths with a grid-wide barrier (the safety nets) and the one-workgroup-per-bucket finish may count on;
         // 0 = ask the device again.  Tests use it to stand in for a small partition.
@@ -3178,6 +3288,8 @@ int adlhip_get_param(adlhip_device* d, const char* name, int* value)
     else if (!strcmp(name, "sort.persist")) *value = d->persist;
     else if (!strcmp(name, "sort.dict")) *value = d->dict_path;
     else if (!strcmp(name, "topk.algo")) *value = d->topk_algo;
+    else if (!strcmp(name, "topk.rows_algo")) *value = d->topk_rows_algo;
+    else if (!strcmp(name, "debug.topk_rows_grid")) *value = d->topk_rows_grid;
     else if (!strcmp(name, "partition.lookback")) *value = d->partition_lookback;
     else if (!strcmp(name, "sort.net_lookback")) *value = d->net_lookback;
     else if (!strcmp(name, "debug.resident_wgs")) *value = d->resident_wgs;

@@ -9,6 +9,7 @@
     p.sortPairs(device, keys, values, n, descending=False) # the same keys with values of 4, 8 or 16 bytes, stable
     p.argsort(device, keys, n, descending=False)           # -> Buffer(uint32): the stable sorting permutation
     p.topk(device, keys, n, k, descending=False)           # -> Buffer(uint32): its first k entries, by selection
+    p.topkRows(device, keys, rows, cols, k)                # -> Buffer(uint32): rows x k columns, top-k of every row
 
 Like the reference object it owns lazily grown device scratch (m_u32WorkBuffer[0] = ping-pong data
 buffer, m_u32WorkBuffer[1] = histogram table; Pprims.h:44-45, Pprims.cpp:226-232, :332-337) and must be
@@ -223,6 +224,42 @@ class Pprims:
             check(_lib.load().adlhip_topk_typed(device._h, kt, 1 if descending else 0, keys.ptr(), n, k,
                                                 keysOut.ptr() if keysOut is not None else None, out.ptr(), self.m_work.ptr(),
                                                 self.m_work.getSize()), "topk")
+        except AdlHipError:
+            if indexOut is None:
+                out.release()
+            raise
+        return out
+
+    def topkRows(self, device, keys, rows, cols, k, descending=False, keysOut=None, indexOut=None, rowStride=None):
+        """Top-k along the rows of a rows x cols matrix (row r starts at element r * rowStride; default cols): returns a
+        Buffer(uint32) of rows * k columns, row-major -- per row the first k entries of the row's own argsort, ties by ascending
+        column.  `keys` is left intact; keysOut (same dtype, rows * k elements, not `keys`) receives the keys.  indexOut: a uint32
+        buffer of rows * k elements to fill and return instead of a new one."""
+        if device is None:
+            raise AdlHipError("topkRows needs a device")
+        kt = self._key_type(keys, "topkRows")
+        rows, cols, k = int(rows), int(cols), int(k)
+        stride = cols if rowStride is None else int(rowStride)
+        if rows < 0 or cols < 0:
+            raise AdlHipError("topkRows: rows = %d, cols = %d" % (rows, cols))
+        if k < 0 or k > cols:
+            raise AdlHipError("topkRows: k = %d outside [0, cols = %d]" % (k, cols))
+        if stride < cols:
+            raise AdlHipError("topkRows: rowStride = %d is below cols = %d" % (stride, cols))
+        if rows and keys.getSize() < (rows - 1) * stride + cols:
+            raise AdlHipError("topkRows: keys must hold (rows - 1) * rowStride + cols = %d elements" % ((rows - 1) * stride + cols))
+        if keysOut is not None and (np.dtype(keysOut.dtype) != np.dtype(keys.dtype) or keysOut.getSize() < rows * k):
+            raise AdlHipError("topkRows: keysOut must hold rows * k elements of %s" % keys.dtype)
+        if indexOut is not None and (np.dtype(indexOut.dtype) != np.uint32 or indexOut.getSize() < rows * k):
+            raise AdlHipError("topkRows: indexOut must hold rows * k uint32 elements")
+        wb = ctypes.c_size_t()
+        check(_lib.load().adlhip_topk_rows_scratch_bytes(device._h, kt, rows, cols, k, ctypes.byref(wb)), "adlhip_topk_rows_scratch_bytes")
+        self._scratch(device, 0, wb.value)
+        out = indexOut if indexOut is not None else Buffer(device, rows * k, np.uint32)
+        try:
+            check(_lib.load().adlhip_topk_rows_typed(device._h, kt, 1 if descending else 0, keys.ptr(), rows, cols, stride, k,
+                                                     keysOut.ptr() if keysOut is not None else None, out.ptr(), self.m_work.ptr(),
+                                                     self.m_work.getSize()), "topkRows")
         except AdlHipError:
             if indexOut is None:
                 out.release()

@@ -5,6 +5,7 @@ back-end on torch's own stream.
     values, indices = s.sort(t)             # t: 1-D CUDA tensor, int32 / int64 / float32 / float64
     indices = s.argsort(t, descending=True)
     values, indices = s.topk(t, 10)         # the 10 largest, largest first; ties to the lower index
+    values, indices = s.topk_rows(m, 10)    # m: 2-D or more; the same along the last dimension of every row
     s.close()
 
 Always out of place and always stable.  The ONE difference from `torch.sort(t, stable=True)`: floats are ordered by
@@ -109,6 +110,39 @@ class TorchSorter:
         idx32 = torch.empty(k, dtype=torch.int32, device=t.device)   # uint32 positions in an int32 tensor
         self.pprims.topk(self.device, self._wrap(src, npdt), n, k, descending=bool(largest), keysOut=self._wrap(values, npdt),
                          indexOut=self._wrap(idx32, np.uint32))
+        self.device.checkFault()
+        return values, idx32.to(torch.int64) & 0xffffffff
+
+    def topk_rows(self, t, k, largest=True, sorted=True):
+        """(values, indices) like torch.topk(t, k, dim=-1, largest=largest, sorted=True) for t.dim() >= 2: top-k along the last
+        dimension, the leading dimensions flattened to rows; both results have shape t.shape[:-1] + (k,), indices are int64.
+        sorted=False is accepted and still returns sorted output.  Ties go to the lower index: indices equal
+        torch.sort(t, dim=-1, descending=largest, stable=True).indices[..., :k].  A 1-D tensor is topk()'s."""
+        if not isinstance(t, torch.Tensor):
+            raise TypeError("TorchSorter: expected a torch.Tensor, got %s" % type(t).__name__)
+        if t.dtype not in _NP_DTYPE:
+            raise TypeError("TorchSorter: dtype %s unsupported (int32, int64, float32, float64)" % t.dtype)
+        if t.dim() < 2:
+            raise ValueError("TorchSorter.topk_rows: 2-D tensors and above, got %d dimensions (topk serves 1-D)" % t.dim())
+        if t.device != self.torch_device:
+            raise ValueError("TorchSorter: tensor is on %s, the sorter on %s" % (t.device, self.torch_device))
+        cols, k = t.shape[-1], int(k)
+        if cols >= 1 << 32:
+            raise ValueError("TorchSorter: fewer than 2^32 elements per row")
+        if torch.cuda.current_stream(self.torch_device).cuda_stream != self.raw_stream:
+            raise RuntimeError("TorchSorter: bound to the stream that was current at construction; another stream is current now")
+        if k < 0 or k > cols:
+            raise ValueError("TorchSorter.topk_rows: k = %d outside [0, last dimension = %d]" % (k, cols))
+        shape = tuple(t.shape[:-1]) + (k,)
+        rows = t.numel() // cols if cols else 0
+        values = torch.empty(shape, dtype=t.dtype, device=t.device)
+        if k == 0 or rows == 0:
+            return values, torch.empty(shape, dtype=torch.int64, device=t.device)
+        src = t.contiguous()
+        npdt = _NP_DTYPE[t.dtype]
+        idx32 = torch.empty(shape, dtype=torch.int32, device=t.device)   # uint32 columns in an int32 tensor
+        self.pprims.topkRows(self.device, self._wrap(src, npdt), rows, cols, k, descending=bool(largest),
+                             keysOut=self._wrap(values, npdt), indexOut=self._wrap(idx32, np.uint32))
         self.device.checkFault()
         return values, idx32.to(torch.int64) & 0xffffffff
 

@@ -2,7 +2,7 @@
 // u32 bit patterns, ascending: Tahoe/ParallelPrimitives/Pprims.h:38-41).  A TYPE_CL (HIP) device runs adlhip_sort_keys_typed /
 // adlhip_argsort_typed; a TYPE_HOST device sorts on the CPU with std::stable_sort on the same total order, as the reference's
 // host branches do for u32 keys (Pprims.cpp:202-212, :306-316).  Pprims::topK: adlhip_topk_typed, or a partial sort on (ordinal,
-// position) on the host.
+// position) on the host.  Pprims::topKRows: adlhip_topk_rows_typed, or the same partial sort per row.
 #include <Tahoe/ParallelPrimitives/Pprims.h>
 
 #include <algorithm>
@@ -168,6 +168,56 @@ void Pprims::topKTyped(const adl::Device* device, const adl::Buffer<T>& keys, ad
     ADLASSERT(rc == ADLHIP_SUCCESS);
 }
 
+template <typename T>
+void Pprims::topKRowsTyped(const adl::Device* device, const adl::Buffer<T>& keys, adl::Buffer<T>& keysOut, adl::Buffer<u32>& indexOut, int rows,
+                           int cols, int k, bool descending, int rowStride)
+{
+    const int stride = rowStride ? rowStride : cols;
+    ADLASSERT(rows >= 0 && cols >= 0 && k >= 0 && k <= cols && stride >= cols);
+    if (rows <= 0 || k <= 0 || k > cols || stride < cols) return;
+    ADLASSERT(device != 0);
+    const adl::u64 inElems = (adl::u64)(rows - 1) * (adl::u64)stride + (adl::u64)cols, outElems = (adl::u64)rows * (adl::u64)k;
+    ADLASSERT(inElems <= keys.getSize() && outElems <= keysOut.getSize() && outElems <= indexOut.getSize());
+    if (!onDevice(device)) {
+        ADLASSERT(device->getType() == adl::TYPE_HOST);   // a HIP device never falls back to the CPU
+        if (device->getType() != adl::TYPE_HOST) return;
+        typedef Ranked<typename KeyTraits<T>::Bits> R;
+        T* host = keys.getHostPtr(inElems);
+        T* kout = keysOut.getHostPtr(outElems);
+        u32* out = indexOut.getHostPtr(outElems);
+        adl::DeviceUtils::waitForCompletion(device);
+        std::vector<R> order((size_t)cols);
+        for (int r = 0; r < rows; ++r) {
+            const T* row = host + (size_t)r * (size_t)stride;
+            for (int i = 0; i < cols; ++i) {
+                order[i].ord = ordinal(row[i], descending);
+                order[i].idx = (u32)i;
+            }
+            // all (ordinal, column) composites of a row are distinct, so the partial sort needs no stability
+            std::partial_sort(order.begin(), order.begin() + k, order.end(),
+                              [](const R& a, const R& b) { return a.ord != b.ord ? a.ord < b.ord : a.idx < b.idx; });
+            for (int j = 0; j < k; ++j) {
+                out[(size_t)r * k + j] = order[j].idx;
+                kout[(size_t)r * k + j] = row[order[j].idx];
+            }
+        }
+        keys.returnHostPtr(host);
+        keysOut.returnHostPtr(kout);
+        indexOut.returnHostPtr(out);
+        adl::DeviceUtils::waitForCompletion(device);
+        return;
+    }
+    size_t wb = 0;
+    const int rcq = adlhip_topk_rows_scratch_bytes(device->hip(), KeyTraits<T>::TYPE, (size_t)rows, (size_t)cols, (size_t)k, &wb);
+    ADLASSERT(rcq == ADLHIP_SUCCESS);
+    reserve(device, 0, wb);
+    const int rc = adlhip_topk_rows_typed(device->hip(), KeyTraits<T>::TYPE, descending ? ADLHIP_ORDER_DESCENDING : ADLHIP_ORDER_ASCENDING,
+                                          keys.m_ptr, (size_t)rows, (size_t)cols, (size_t)stride, (size_t)k, keysOut.m_ptr,
+                                          (uint32_t*)indexOut.m_ptr, m_work->m_ptr, (size_t)m_work->getSize());
+    if (rc != ADLHIP_SUCCESS) TH_LOG_ERROR("Pprims::topKRows: %s\n", adlhip_last_error());
+    ADLASSERT(rc == ADLHIP_SUCCESS);
+}
+
 #define TAHOE_TYPED(T)                                                                                                              \
     void Pprims::sortKeys(const adl::Device* device, const adl::Buffer<T>& inout, int n, bool descending)                         \
     {                                                                                                                               \
@@ -181,6 +231,11 @@ void Pprims::topKTyped(const adl::Device* device, const adl::Buffer<T>& keys, ad
                       int n, int k, bool descending)                                                                                \
     {                                                                                                                               \
         topKTyped<T>(device, keys, keysOut, indexOut, n, k, descending);                                                            \
+    }                                                                                                                               \
+    void Pprims::topKRows(const adl::Device* device, const adl::Buffer<T>& keys, adl::Buffer<T>& keysOut, adl::Buffer<u32>& indexOut, \
+                          int rows, int cols, int k, bool descending, int rowStride)                                                \
+    {                                                                                                                               \
+        topKRowsTyped<T>(device, keys, keysOut, indexOut, rows, cols, k, descending, rowStride);                                    \
     }
 TAHOE_TYPED(int)
 TAHOE_TYPED(float)
