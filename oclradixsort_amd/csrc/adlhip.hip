@@ -111,6 +111,8 @@ struct adlhip_device {
     int bin_finish = 1;       // "sort.binfinish": the large keys-only sort finishes its segments with one counting pass + compares
                               // (1: u64 keys, 2: u32 keys too, 0: the wave-per-segment LSD finish)
     int persist = 1;          // "sort.persist": the cursor passes of the large sort as persistent, prefetching kernels + the 16-bit finish
+    int finish16_alg = -1;    // "debug.finish16_alg": the variant of the 16-bit finish (finish16_kernels.hpp ALG); -1 = the adopted one (2:
+                              // plain LDS gathers), 1 = the round-4 kernel (gathers through a volatile pointer); A/B runs and tests
     int msd2_path = 1;        // "sort.msd2": the large sort (msd2_sort for keys, msd2s_sort for pairs); 2 = forced (tests)
     int net_lookback = 1;                   // "sort.net_lookback": the large sort's safety net runs look-back passes (0: count-scan-scatter passes)
     int partition_lookback = 1;             // "partition.lookback": the MSB partition as one look-back pass where it pays (0: always three kernels)
@@ -1511,7 +1513,8 @@ int launch_large_finish(adlhip_device* d, const E* slab_b, E* out, uint32_t* out
             const uint16_t* sb = reinterpret_cast<const uint16_t*>(slab_b);
 #define ADLHIP_F16(R2_, WAVES_)                                                                                                      \
     {                                                                                                                                \
-        auto kf = adlhip::wave_finish16_kernel<R2_, WAVES_, true, true, 1>;                                                                   \
+        auto kf = d->finish16_alg == 1 ? adlhip::wave_finish16_kernel<R2_, WAVES_, true, true, 1>                                    \
+                                       : adlhip::wave_finish16_kernel<R2_, WAVES_, true, true, 2>;                                   \
         const size_t lds = (size_t)WAVES_ * adlhip::Finish16Cfg<R2_>::PER_WAVE;                                                      \
         if (ensure_lds(kf, lds)) return ADLHIP_FAILURE;                                                                              \
         return launch(d, "segment_sort_wave_u32", [&] {                                                                              \
@@ -3247,6 +3250,9 @@ int adlhip_set_param(adlhip_device* d, const char* name, int value)
     } else if (!strcmp(name, "debug.topk_rows_grid")) {
         if (value < 0) return fail("debug.topk_rows_grid must be >= 0");
         d->topk_rows_grid = value;
+    } else if (!strcmp(name, "debug.finish16_alg")) {
+        if (value != -1 && value != 1 && value != 2) return fail("debug.finish16_alg must be -1 (the adopted variant), 1 (the round-4 kernel) or 2");
+        d->finish16_alg = value;
     } else if (!strcmp(name, "debug.resident_wgs")) {
         // what the paths with a grid-wide barrier (the safety nets) and the one-workgroup-per-bucket finish may count on;
         // 0 = ask the device again.  Tests use it to stand in for a small partition.
@@ -3292,6 +3298,7 @@ int adlhip_get_param(adlhip_device* d, const char* name, int* value)
     else if (!strcmp(name, "debug.topk_rows_grid")) *value = d->topk_rows_grid;
     else if (!strcmp(name, "partition.lookback")) *value = d->partition_lookback;
     else if (!strcmp(name, "sort.net_lookback")) *value = d->net_lookback;
+    else if (!strcmp(name, "debug.finish16_alg")) *value = d->finish16_alg;
     else if (!strcmp(name, "debug.resident_wgs")) *value = d->resident_wgs;
     else if (!strcmp(name, "stat.net_runs") || !strcmp(name, "stat.net_counting")) {
         // how often the large sort's safety net has run on this handle, and how often it sorted by counting (waits for the stream)

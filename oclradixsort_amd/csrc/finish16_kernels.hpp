@@ -12,6 +12,16 @@
 // bank conflicts; conflicts of 64 random bins over 32 banks cannot be laid out away, so what this kernel buys is fewer LDS
 // instructions per key and more waves in flight to keep the LDS pipe full while others wait for memory.
 //
+// Variants (ALG; "debug.finish16_alg" chooses between 1 and 2, launch_large_finish): 0 and 1 are round 4's.  1 reads the bin starts
+// through a volatile pointer, which the compiler cannot place in LDS: a FLAT load and a full wait per key.  2 gathers them with plain
+// LDS reads (the compiler keeps eight ahead of their 16-bit stores, counted lgkmcnt waits) and is what runs: 64 Mi keys 0.102 ->
+// 0.096-0.097 ms.  There the LDS array is the limit -- SQ_LDS_IDX_ACTIVE is 186 K cycles per CU, 62 % of them bank conflicts of the
+// returning atomics, the gathers and the 16-bit scatter, in either variant -- and what was tried on top changed nothing: 8 waves per
+// SIMD instead of 5 (bounded batches of ranks and gathers, digits recomputed: 63 VGPRs), a prologue of one round trip, a tile index
+// of four instructions instead of eight (CHANGELOG.md, profiles/finish16_ab.txt, finish16_pmc.txt).  Registers: <10,4> 73, <12,4> 86,
+// <20,4> 125 VGPRs, no scratch.
+// What the wave's LDS accesses may assume of each other is written down once, at finish16_lds_order().
+//
 // Reference behaviour: Tahoe/ClKernels/RadixSort32Kernels.cl:401-489 (sort4Bits1: the stable local sort of a block).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -29,10 +39,17 @@ struct Finish16Cfg {
 
 __device__ __forceinline__ uint32_t finish16_index(uint32_t p) { return (p & ~127u) | ((p & 63u) << 1) | ((p >> 6) & 1u); }
 
+// The ordering contract of a wave's slice of LDS.  One wave owns the tile and the counters; the hardware executes a wave's DS
+// operations in the order they were issued, so a lane that reads what another lane of the same wave wrote needs no wait and no
+// barrier -- only that the compiler ISSUES the write first.  Nothing in the types says so: the tile is written as uint16_t and read
+// back as uint32_t (strict aliasing lets the loads move above the stores), and the bin starts are written as one u32x4 per lane and
+// gathered by other lanes.  This point is that promise: no LDS access moves across it.  It emits no instruction.
+__device__ __forceinline__ void finish16_lds_order() { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); }
+
 // RR row pairs; the first RR - 1 are full (m > 128 (RR - 1)), only the last is tested per lane
 // NTL / NTS: non-temporal loads of the slab / stores of the result.  ALG: 0 = count, scan, then a returning atomic per key hands out
 // its slot; 1 = ONE returning atomic per key counts and ranks (its arrival number inside its bin, in position order), then scan and
-// slot = bin start (a gather: cheaper than an atomic, tools/r4_lds_bench) + rank.
+// slot = bin start (a gather: cheaper than an atomic, tools/r4_lds_bench) + rank; 2 = the same, the gather a plain LDS read.
 template <int RR, bool NTL, bool NTS, int ALG>
 __device__ __forceinline__ void finish16_rows(const uint32_t* __restrict__ src32, uint32_t* __restrict__ out, uint32_t m, int lane,
                                               uint16_t* __restrict__ buf16, uint32_t* __restrict__ cnt, uint32_t low_bits, uint32_t hi)
@@ -94,6 +111,7 @@ __device__ __forceinline__ void finish16_rows(const uint32_t* __restrict__ src32
             o.w = o.z + c.z;
             *reinterpret_cast<u32x4*>(cnt + 4 * lane) = o;
         }
+        finish16_lds_order();   // the bin starts are written before any lane gathers one
         if constexpr (ALG == 0) {
             // slots: one returning atomic per key in position order (row 2j before row 2j + 1; colliding lanes are served in lane
             // order: stable, radix_kernels.hpp rank_in_wave), then its 16-bit store
@@ -105,7 +123,7 @@ __device__ __forceinline__ void finish16_rows(const uint32_t* __restrict__ src32
                 if (j < L || v_lo) buf16[finish16_index(p0)] = (uint16_t)kp[j];
                 if (j < L || v_hi) buf16[finish16_index(p1)] = (uint16_t)(kp[j] >> 16);
             }
-        } else {
+        } else if constexpr (ALG == 1) {
             const volatile uint32_t* start = cnt;
 #pragma unroll
             for (int j = 0; j < RR; ++j) {
@@ -115,7 +133,17 @@ __device__ __forceinline__ void finish16_rows(const uint32_t* __restrict__ src32
                 if (j < L || v_lo) buf16[finish16_index(p0)] = (uint16_t)kp[j];
                 if (j < L || v_hi) buf16[finish16_index(p1)] = (uint16_t)(kp[j] >> 16);
             }
+        } else {   // ALG 2: plain LDS reads
+#pragma unroll
+            for (int j = 0; j < RR; ++j) {
+                uint32_t p0 = 0u, p1 = 0u;
+                if (j < L || v_lo) p0 = cnt[dlo(kp[j])] + (rk[j] & 0xffffu);
+                if (j < L || v_hi) p1 = cnt[dhi(kp[j])] + (rk[j] >> 16);
+                if (j < L || v_lo) buf16[finish16_index(p0)] = (uint16_t)kp[j];
+                if (j < L || v_hi) buf16[finish16_index(p1)] = (uint16_t)(kp[j] >> 16);
+            }
         }
+        finish16_lds_order();   // the 16-bit stores of the tile are issued before its 32-bit read-back
 #pragma unroll
         for (int j = 0; j < RR; ++j)
             if (j < L || b_lo) kp[j] = buf32[j * 64 + lane];
