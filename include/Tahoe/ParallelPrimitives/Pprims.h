@@ -8,6 +8,7 @@
 //   sortKeys / argsort  signed, float and descending keys            (new: adlhip_sort_keys_typed / adlhip_argsort_typed)
 //   topK      the first k entries of argsort, by selection           (new: adlhip_topk_typed)
 //   topKRows  topK of every row of a rows x cols matrix              (new: adlhip_topk_rows_typed)
+//   unique    distinct keys in sorted order and their counts         (new: adlhip_unique_typed)
 // Same argument meaning; differences, all supersets: any n >= 0 (the reference needs n % 256 == 0 for
 // keys), scan has no 1,048,576-element limit, sortBits < 32 also works on 64-bit keys up to 64.
 // Device work is enqueued and the call returns (no sync), as in the reference's GPU branches.
@@ -115,8 +116,26 @@ public:
                   int cols, int k, bool descending = false, int rowStride = 0);
     void topKRows(const adl::Device* device, const adl::Buffer<u64>& keys, adl::Buffer<u64>& keysOut, adl::Buffer<u32>& indexOut, int rows,
                   int cols, int k, bool descending = false, int rowStride = 0);
+    // the distinct keys among the first n of keys, in the order of sortKeys(descending), and how often each occurs: uniqueOut[r] and
+    // countsOut[r] for r < R; both hold n elements, those at R and beyond are left alone.  Keys are equal when their bits are (-0 and
+    // +0 are two keys, NaNs with different payloads too).  keys is left intact.  Unlike the calls above this one WAITS and returns R.
+    // A TYPE_HOST device sorts on the CPU (std::stable_sort on the same order)
+    int unique(const adl::Device* device, const adl::Buffer<int>& keys, adl::Buffer<int>& uniqueOut, adl::Buffer<u32>& countsOut, int n,
+               bool descending = false);
+    int unique(const adl::Device* device, const adl::Buffer<float>& keys, adl::Buffer<float>& uniqueOut, adl::Buffer<u32>& countsOut, int n,
+               bool descending = false);
+    int unique(const adl::Device* device, const adl::Buffer<long long>& keys, adl::Buffer<long long>& uniqueOut, adl::Buffer<u32>& countsOut, int n,
+               bool descending = false);
+    int unique(const adl::Device* device, const adl::Buffer<double>& keys, adl::Buffer<double>& uniqueOut, adl::Buffer<u32>& countsOut, int n,
+               bool descending = false);
+    int unique(const adl::Device* device, const adl::Buffer<u32>& keys, adl::Buffer<u32>& uniqueOut, adl::Buffer<u32>& countsOut, int n,
+               bool descending = false);
+    int unique(const adl::Device* device, const adl::Buffer<u64>& keys, adl::Buffer<u64>& uniqueOut, adl::Buffer<u32>& countsOut, int n,
+               bool descending = false);
 
 private:
+    template <typename T> int uniqueTyped(const adl::Device* device, const adl::Buffer<T>& keys, adl::Buffer<T>& uniqueOut, adl::Buffer<u32>& countsOut,
+                                          int n, bool descending);
     template <typename T> void topKRowsTyped(const adl::Device* device, const adl::Buffer<T>& keys, adl::Buffer<T>& keysOut, adl::Buffer<u32>& indexOut,
                                              int rows, int cols, int k, bool descending, int rowStride);
     template <typename T> void topKTyped(const adl::Device* device, const adl::Buffer<T>& keys, adl::Buffer<T>& keysOut, adl::Buffer<u32>& indexOut, int n,

@@ -209,7 +209,9 @@ int adlhip_radix_sort_u64(adlhip_device* dev, uint64_t* d_keys_inout, uint64_t* 
  *   unsigned: identity;  signed: the sign bit flipped;  float: bits ^ (sign set ? all ones : sign bit);  descending: the complement.
  * Floats sort in IEEE-754 totalOrder: -NaN < -inf < ... < -denormal < -0 < +0 < +denormal < ... < +inf < +NaN, NaNs of one sign by
  * payload.  So -0 sorts before +0, and NaNs whose sign bit is set come FIRST, not last (descending: the mirror image).  Every sort
- * below is stable: equal keys keep their input order, also descending (torch.sort(descending=True, stable=True) does the same). */
+ * below is stable: equal keys keep their input order, also descending (torch.sort(descending=True, stable=True) does the same).
+ * Where keys are compared for EQUALITY (adlhip_run_length_encode, adlhip_unique_typed) it is equality of bits, consistent with that
+ * order: -0 and +0 are two keys, NaNs with different payloads are different keys. */
 #define ADLHIP_KEY_U32 0
 #define ADLHIP_KEY_I32 1
 #define ADLHIP_KEY_F32 2
@@ -314,6 +316,59 @@ int adlhip_topk_rows_scratch_bytes(adlhip_device* dev, int key_type, size_t rows
 int adlhip_topk_rows_typed(adlhip_device* dev, int key_type, int order, const void* d_keys_in, size_t rows, size_t cols,
                            size_t row_stride, size_t k, void* d_keys_out_or_null, uint32_t* d_index_out_or_null,
                            void* d_work, size_t work_bytes);
+
+/* ---- unique keys, run lengths, inverse indices (no reference counterpart) --------------------- */
+
+/* Key equality in this block is equality of BITS, consistent with the totalOrder above (NaN and -0 order): -0 and +0 are two keys, NaNs
+ * with different payloads are different keys, NaNs with the same bits are one key.
+ *
+ * Contract common to adlhip_run_length_encode and adlhip_unique_typed: n < 2^32.  d_keys_in is never written.  d_unique_out and the count
+ * word (d_num_runs_out / d_num_unique_out) are required, the other outputs optional.  d_unique_out, counts and first_index hold n
+ * elements, offsets n + 1, inverse n; with R the number of runs, the elements at R and beyond (offsets: R + 1 and beyond) are NEVER
+ * written.  d_keys_in, d_work and every output array are 16-byte aligned, the count word 4-byte aligned; no output (the count word
+ * included) may overlap d_keys_in.  n == 0 enqueues one 4-byte clear of the count word and nothing else (only the count word is looked at).
+ * A NULL required pointer, a misaligned pointer, an overlap, an unknown key_type, order or key_bytes, and a work buffer one byte short
+ * (the message names the needed size) fail before anything is enqueued.  The calls enqueue and return: nothing data-dependent reaches
+ * the host (R stays on the device; launch grids depend on n alone), nothing is remembered between calls, all state lives in d_work --
+ * whose contents on entry are arbitrary -- and the handle owns no device word of it.  No kernel of the run stage waits on another
+ * workgroup, so there is no new fault condition.
+ *
+ * Work bytes, every part rounded up to 256 bytes, with CUs = adlhip_info.compute_units and kb = bytes per key:
+ *   W_runs(n)   = 16 CUs (one head count per workgroup of the largest grid, 4 workgroups per CU) + 4 (n + 1) (offsets, used when counts
+ *                 are asked without offsets)
+ *   adlhip_run_length_encode_scratch_bytes = W_runs(n)
+ *   keys path   = W_runs(n) + n kb (the sorted keys) + n kb (the sort's partner array) + W_keys(n)
+ *   index path  = W_runs(n) + n kb (the sorted keys) + 4 n (the argsort's index) + W_argsort(n)
+ *   adlhip_unique_scratch_bytes = want_index ? max(keys path, index path) : keys path
+ * W_keys / W_argsort = *work_bytes of adlhip_sort_typed_scratch_bytes, mode 0 / mode 2.  The value suffices for every n' <= n. */
+
+/* Run-length encode of keys that are already grouped (no reference counterpart); key_bytes: 4 or 8.  A run is a maximal stretch of
+ * adjacent keys with identical bits.  With R runs: d_unique_out[r] = the key of run r, d_offsets_out[r] = its first position and
+ * d_offsets_out[R] = n, d_counts_out[r] = its length, *d_num_runs_out = R -- the contract of torch.unique_consecutive, and the
+ * segment-start array adlhip_segment_sort takes.  Keys that are grouped but not sorted (A A B A) give one run per stretch (A B A).
+ * Three or four launches: the workgroups count the run heads of their chunks (a head is position 0 or a key that differs from the one
+ * in front of it), one workgroup scans the counts and writes R, the workgroups walk their chunks again and write the heads where their
+ * ranks say, counts are the differences of the offsets. */
+int adlhip_run_length_encode_scratch_bytes(adlhip_device* dev, int key_bytes, size_t n, size_t* work_bytes);
+int adlhip_run_length_encode(adlhip_device* dev, int key_bytes, const void* d_keys_in, size_t n,
+                             void* d_unique_out, uint32_t* d_counts_out_or_null, uint32_t* d_offsets_out_or_null,
+                             uint32_t* d_num_runs_out, void* d_work, size_t work_bytes);
+
+/* The distinct keys of d_keys_in in the order of adlhip_sort_keys_typed(key_type, order) (no reference counterpart).  With P the result
+ * of adlhip_argsort_typed on the same input, S the sorted keys and off the run starts of S:
+ *   d_unique_out[r] = S[off[r]], bit for bit;  d_offsets_out[r] = off[r], d_offsets_out[R] = n;  d_counts_out[r] = off[r + 1] - off[r];
+ *   d_first_index_out[r] = P[off[r]] -- the argsort is stable, so this is the LOWEST input position that holds the key, in both orders;
+ *   d_inverse_out[i] = the r for which d_keys_in[i] has the bits of d_unique_out[r];  *d_num_unique_out = R.
+ * Two paths, the same common outputs bit for bit ("unique.algo"): the keys path, when neither first_index nor inverse is asked, copies
+ * the keys into d_work, sorts them there with adlhip_sort_keys_typed and runs the run stage of adlhip_run_length_encode; the index path
+ * runs adlhip_argsort_typed into d_work (S and P) and the run stage with P.  want_index of the scratch query: non-zero when
+ * first_index or inverse will be asked or "unique.algo" = 1 is set.  As for the typed sorts, a sort that refuses after the copy has
+ * been enqueued (knobs changed since the scratch was sized) fails the call with the sort's message. */
+int adlhip_unique_scratch_bytes(adlhip_device* dev, int key_type, size_t n, int want_index, size_t* work_bytes);
+int adlhip_unique_typed(adlhip_device* dev, int key_type, int order, const void* d_keys_in, size_t n,
+                        void* d_unique_out, uint32_t* d_counts_out_or_null, uint32_t* d_offsets_out_or_null,
+                        uint32_t* d_first_index_out_or_null, uint32_t* d_inverse_out_or_null,
+                        uint32_t* d_num_unique_out, void* d_work, size_t work_bytes);
 
 /* ---- segments finished in LDS (no reference counterpart) ------------------------------------- */
 
@@ -472,6 +527,12 @@ int adlhip_generate_keys(adlhip_device* dev, int elem_kind, void* dptr, size_t n
  *                      (tools/topk_rows_bench.py measures it).  The same result bit for bit either way
  *   "debug.topk_rows_grid" workgroups the row kernel is launched with at most (0 [default]: 4 per CU); tests set it to make few
  *                      workgroups take many rows in turns
+ *   "unique.algo"      -1 [default] / 1: adlhip_unique_typed takes its keys path (copy, typed keys sort, run stage) unless first_index or
+ *                      inverse is asked, which need the index path (argsort, run stage with the permutation); 1 always takes the index
+ *                      path (tests, measurements; the work buffer must then have the want_index size).  The same unique, counts and
+ *                      offsets bit for bit either way
+ *   "debug.unique_grid" workgroups the run stage of adlhip_run_length_encode / adlhip_unique_typed is launched with at most (0 [default]:
+ *                      4 per CU; larger values change nothing); tests set it to make few workgroups take many tiles
  *   "sort.net_lookback" 1 [default] / 0: the LSD passes of the large sort's safety net on whole keys are look-back passes -- the
  *                      one-sweep path's histogram, tables and tile body, taken in turns by the net's resident workgroups, four
  *                      passes at a time (u64 keys: two rounds) -- instead of count -> scan -> scatter passes with per-workgroup

@@ -27,6 +27,7 @@
 #include "typed_kernels.hpp"
 #include "select_kernels.hpp"
 #include "toprows_kernels.hpp"
+#include "unique_kernels.hpp"
 
 // The large sort's kernels and the per-digit passes' are instantiated in kernels_finish.hip / kernels_passes.hip / kernels_perdigit.hip (translation units of
 // their own, compiled beside this one); here they are only declared.  -DADLHIP_SINGLE_TU builds everything in this file (what tools/gen_large_kernels.py reads the list from).
@@ -38,6 +39,7 @@
 #include "perdigit_kernels.inc"
 #include "select_kernels.inc"
 #include "toprows_kernels.inc"
+#include "unique_kernels.inc"
 #undef X
 #endif
 
@@ -123,6 +125,8 @@ struct adlhip_device {
     int topk_rows_algo = -1;                // "topk.rows_algo": -1 the row kernel while k <= kRowMaxK and cols <= kTopkRowsMaxCols, the per-row
                                             // loop above; 0 / 1 force the loop / the row kernel
     int topk_rows_grid = 0;                 // "debug.topk_rows_grid": workgroups of the row kernel at most (0: kTopkRowsWgsPerCu per CU)
+    int unique_algo = -1;                   // "unique.algo": -1 the keys path unless first_index or inverse is asked, 1 always the index path
+    int unique_grid = 0;                    // "debug.unique_grid": workgroups of the run stage at most (0: kUniqueWgsPerCu per CU)
     adlhip::DictBlock* d_dict = nullptr;    // its dictionary and counters (handle-owned; rebuilt by every net that uses them)
     uint32_t* d_msd2 = nullptr;   // the large sort's handle-owned words, allocated with the handle: cursors of pass 1 (256, one
                                   // 128-byte line each) and pass 2 (65536), overflow flag, done counter, the safety net's barrier
@@ -2349,6 +2353,130 @@ int topk_rows_kernel_path(adlhip_device* d, int kind, int desc, const U* keys_in
     });
 }
 
+// ---- unique / run-length encode (unique_kernels.hpp; no reference counterpart) ------------------------------------------------------
+// Work of the run stage: [chunk head counts: one u32 per workgroup of the largest grid][offsets: n + 1 u32, used when the caller wants
+// counts but passes no offsets], each rounded up to 256 bytes.
+constexpr int kUniqueWgsPerCu = 4;   // grid of the run stage per CU at most ("debug.unique_grid" lowers it)
+struct RunsLayout {
+    size_t off_offsets, total;
+};
+RunsLayout runs_layout(const adlhip_device* d, size_t n)
+{
+    RunsLayout L;
+    L.off_offsets = align_up((size_t)d->prop.multiProcessorCount * kUniqueWgsPerCu * 4, 256);
+    L.total = L.off_offsets + align_up((n + 1) * 4, 256);
+    return L;
+}
+
+// Work of adlhip_unique_typed: [run stage][S: the sorted keys, n][the sort's own buffers]
+//   keys path   [tmp: the sort's partner array, n keys][work of the typed keys sort]
+//   index path  [P: the argsort's index, n u32][work of the argsort]
+struct UniqueLayout {
+    size_t off_sorted, off_tmp, off_swork, swork_bytes, keys_total;   // keys path
+    size_t off_perm, off_awork, awork_bytes, index_total;             // index path
+};
+UniqueLayout unique_layout(const adlhip_device* d, size_t key_bytes, size_t n)
+{
+    UniqueLayout L;
+    L.off_sorted = runs_layout(d, n).total;
+    const size_t behind = L.off_sorted + align_up(n * key_bytes, 256);
+    L.off_tmp = behind;
+    L.off_swork = L.off_tmp + align_up(n * key_bytes, 256);
+    L.swork_bytes = sort_work_bytes(d, key_bytes == 4 ? ADLHIP_ELEM_U32 : ADLHIP_ELEM_U64, n, 8 * (int)key_bytes, 1);
+    L.keys_total = L.off_swork + align_up(L.swork_bytes, 256);
+    L.off_perm = behind;
+    L.off_awork = L.off_perm + align_up(n * 4, 256);
+    L.awork_bytes = soa_wide_layout(d, n).total;
+    L.index_total = L.off_awork + align_up(L.awork_bytes, 256);
+    return L;
+}
+
+// the run stage on n > 0 grouped keys; perm (null or the argsort's index) feeds first_index and inverse
+template <typename U>
+int runs_stage(adlhip_device* d, const U* keys, const uint32_t* perm, size_t n, U* unique_out, uint32_t* counts, uint32_t* offsets,
+               uint32_t* first_index, uint32_t* inverse, uint32_t* num_out, void* work)
+{
+    const RunsLayout L = runs_layout(d, n);
+    char* w = static_cast<char*>(work);
+    uint32_t* chunk = reinterpret_cast<uint32_t*>(w);
+    if (counts && !offsets) offsets = reinterpret_cast<uint32_t*>(w + L.off_offsets);
+    // the chunk split: every workgroup owns tiles_per_wg whole tiles (the last one what is left, at least one)
+    constexpr size_t tile = (size_t)adlhip::kSelNT * adlhip::kSelVecs * (16 / sizeof(U));
+    const size_t tiles = (n + tile - 1) / tile;
+    size_t cap = (size_t)d->prop.multiProcessorCount * kUniqueWgsPerCu;
+    if (d->unique_grid > 0) cap = std::min(cap, (size_t)d->unique_grid);
+    const size_t tiles_per_wg = (tiles + cap - 1) / cap;
+    const uint32_t wgs = (uint32_t)((tiles + tiles_per_wg - 1) / tiles_per_wg);
+    const uint32_t nn = (uint32_t)n, nt = (uint32_t)tiles, tpw = (uint32_t)tiles_per_wg;
+    int rc = launch(d, sizeof(U) == 4 ? "runs_count_k32" : "runs_count_k64", [&] {
+        hipLaunchKernelGGL((adlhip::runs_count_kernel<U>), dim3(wgs), dim3(adlhip::kSelNT), 0, d->stream, keys, nn, nt, tpw, chunk);
+    });
+    if (rc) return rc;
+    rc = launch(d, "runs_scan", [&] {   // in place; the total is the number of runs
+        hipLaunchKernelGGL(adlhip::scan_single_kernel, dim3(1), dim3(adlhip::kScanNT), 0, d->stream, (const uint32_t*)chunk, chunk, (size_t)wgs,
+                           num_out);
+    });
+    if (rc) return rc;
+    rc = launch(d, sizeof(U) == 4 ? "runs_emit_k32" : "runs_emit_k64", [&] {
+        if (perm)
+            hipLaunchKernelGGL((adlhip::runs_emit_kernel<U, 1>), dim3(wgs), dim3(adlhip::kSelNT), 0, d->stream, keys, perm, nn, nt, tpw,
+                               (const uint32_t*)chunk, unique_out, offsets, first_index, inverse);
+        else
+            hipLaunchKernelGGL((adlhip::runs_emit_kernel<U, 0>), dim3(wgs), dim3(adlhip::kSelNT), 0, d->stream, keys, (const uint32_t*)nullptr, nn,
+                               nt, tpw, (const uint32_t*)chunk, unique_out, offsets, (uint32_t*)nullptr, (uint32_t*)nullptr);
+    });
+    if (rc || !counts) return rc;
+    const uint32_t cwgs = (uint32_t)((n + adlhip::kRunsCountsPerWg - 1) / adlhip::kRunsCountsPerWg);   // (at most 2^21)
+    return launch(d, "runs_counts", [&] {
+        hipLaunchKernelGGL(adlhip::runs_counts_kernel, dim3(cwgs), dim3(adlhip::kSelNT), 0, d->stream, (const uint32_t*)offsets,
+                           (const uint32_t*)num_out, nn, counts);
+    });
+}
+
+// what both entry points refuse about their buffers, before anything is enqueued
+struct RunsOut {
+    const void* p;
+    size_t bytes;
+    const char* name;
+};
+int runs_check_buffers(const char* what, const void* keys_in, size_t in_bytes, const RunsOut* outs, int num_outs, const void* num_out,
+                       const void* work)
+{
+    if (!keys_in || !outs[0].p || !work) return fail("null buffer passed to %s", what);
+    uintptr_t bits = reinterpret_cast<uintptr_t>(keys_in) | reinterpret_cast<uintptr_t>(work);
+    for (int i = 0; i < num_outs; ++i) bits |= reinterpret_cast<uintptr_t>(outs[i].p);
+    if (bits & 15u) return fail("%s buffers must be 16-byte aligned", what);
+    const char* in0 = static_cast<const char*>(keys_in);
+    const char* in1 = in0 + in_bytes;
+    for (int i = 0; i <= num_outs; ++i) {
+        const char* o = static_cast<const char*>(i < num_outs ? outs[i].p : num_out);
+        const size_t bytes = i < num_outs ? outs[i].bytes : 4;
+        if (o && o < in1 && in0 < o + bytes) return fail("%s: %s must not overlap d_keys_in", what, i < num_outs ? outs[i].name : "the count word");
+    }
+    return ADLHIP_SUCCESS;
+}
+
+// sort (keys path: a copy of the keys, in place; index path: the argsort, which also gives P), then the run stage
+template <typename U>
+int unique_run(adlhip_device* d, const KeyTypeInfo& t, int order, bool index_path, const U* keys_in, size_t n, U* unique_out,
+                      uint32_t* counts, uint32_t* offsets, uint32_t* first_index, uint32_t* inverse, uint32_t* num_out, void* work)
+{
+    const UniqueLayout L = unique_layout(d, sizeof(U), n);
+    char* w = static_cast<char*>(work);
+    U* sorted = reinterpret_cast<U*>(w + L.off_sorted);
+    if (index_path) {
+        uint32_t* perm = reinterpret_cast<uint32_t*>(w + L.off_perm);
+        const int rc = typed_index_sort<U, uint32_t>(d, t.kind, order, keys_in, sorted, nullptr, nullptr, perm, w + L.off_awork, n);
+        if (rc) return rc;
+        return runs_stage<U>(d, sorted, perm, n, unique_out, counts, offsets, first_index, inverse, num_out, work);
+    }
+    HIPCHK(hipMemcpyAsync(sorted, keys_in, n * sizeof(U), hipMemcpyDeviceToDevice, d->stream));
+    const int rc = typed_keys_sort<U>(d, sizeof(U) == 4 ? ADLHIP_ELEM_U32 : ADLHIP_ELEM_U64, t.kind, order, sorted, reinterpret_cast<U*>(w + L.off_tmp),
+                                      w + L.off_swork, L.swork_bytes, n);
+    if (rc) return rc;
+    return runs_stage<U>(d, sorted, nullptr, n, unique_out, counts, offsets, nullptr, nullptr, num_out, work);
+}
+
 }  // namespace
 
 // ================================================================================================
@@ -3093,6 +3221,82 @@ int adlhip_topk_rows_typed(adlhip_device* d, int key_type, int order, const void
 #undef ADLHIP_TOPK_ROWS
 }
 
+// ---- unique / run-length encode ---------------------------------------------------------------------
+
+int adlhip_run_length_encode_scratch_bytes(adlhip_device* d, int key_bytes, size_t n, size_t* work_bytes)
+{
+    if (!d) return fail("null device handle");
+    if (key_bytes != 4 && key_bytes != 8) return fail("run-length encode: key_bytes must be 4 or 8, got %d", key_bytes);
+    if (typed_check_n(n)) return ADLHIP_FAILURE;
+    if (work_bytes) *work_bytes = runs_layout(d, n).total;
+    return ADLHIP_SUCCESS;
+}
+
+int adlhip_run_length_encode(adlhip_device* d, int key_bytes, const void* keys_in, size_t n, void* unique_out, uint32_t* counts_out,
+                             uint32_t* offsets_out, uint32_t* num_runs_out, void* work, size_t work_bytes)
+{
+    if (bind(d)) return ADLHIP_FAILURE;
+    if (key_bytes != 4 && key_bytes != 8) return fail("run-length encode: key_bytes must be 4 or 8, got %d", key_bytes);
+    if (typed_check_n(n)) return ADLHIP_FAILURE;
+    if (!num_runs_out) return fail("run-length encode: d_num_runs_out is required");
+    if (reinterpret_cast<uintptr_t>(num_runs_out) & 3u) return fail("run-length encode: d_num_runs_out must be 4-byte aligned");
+    if (n == 0) {
+        HIPCHK(hipMemsetAsync(num_runs_out, 0, 4, d->stream));
+        return ADLHIP_SUCCESS;
+    }
+    const RunsOut outs[] = {{unique_out, n * (size_t)key_bytes, "d_unique_out"}, {counts_out, n * 4, "d_counts_out"},
+                            {offsets_out, (n + 1) * 4, "d_offsets_out"}};
+    if (runs_check_buffers("run-length encode", keys_in, n * (size_t)key_bytes, outs, 3, num_runs_out, work)) return ADLHIP_FAILURE;
+    const size_t need = runs_layout(d, n).total;
+    if (work_bytes < need) return fail("work buffer too small: %zu < %zu (adlhip_run_length_encode_scratch_bytes)", work_bytes, need);
+    if (key_bytes == 4)
+        return runs_stage<uint32_t>(d, (const uint32_t*)keys_in, nullptr, n, (uint32_t*)unique_out, counts_out, offsets_out, nullptr, nullptr,
+                                    num_runs_out, work);
+    return runs_stage<uint64_t>(d, (const uint64_t*)keys_in, nullptr, n, (uint64_t*)unique_out, counts_out, offsets_out, nullptr, nullptr,
+                                num_runs_out, work);
+}
+
+int adlhip_unique_scratch_bytes(adlhip_device* d, int key_type, size_t n, int want_index, size_t* work_bytes)
+{
+    if (!d) return fail("null device handle");
+    KeyTypeInfo t;
+    if (key_type_info(key_type, ADLHIP_ORDER_ASCENDING, &t)) return ADLHIP_FAILURE;
+    if (typed_check_n(n)) return ADLHIP_FAILURE;
+    const UniqueLayout L = unique_layout(d, (size_t)t.bytes, n);
+    if (work_bytes) *work_bytes = want_index ? std::max(L.keys_total, L.index_total) : L.keys_total;
+    return ADLHIP_SUCCESS;
+}
+
+int adlhip_unique_typed(adlhip_device* d, int key_type, int order, const void* keys_in, size_t n, void* unique_out, uint32_t* counts_out,
+                        uint32_t* offsets_out, uint32_t* first_index_out, uint32_t* inverse_out, uint32_t* num_unique_out, void* work,
+                        size_t work_bytes)
+{
+    if (bind(d)) return ADLHIP_FAILURE;
+    KeyTypeInfo t;
+    if (key_type_info(key_type, order, &t)) return ADLHIP_FAILURE;
+    if (typed_check_n(n)) return ADLHIP_FAILURE;
+    if (!num_unique_out) return fail("unique: d_num_unique_out is required");
+    if (reinterpret_cast<uintptr_t>(num_unique_out) & 3u) return fail("unique: d_num_unique_out must be 4-byte aligned");
+    if (n == 0) {
+        HIPCHK(hipMemsetAsync(num_unique_out, 0, 4, d->stream));
+        return ADLHIP_SUCCESS;
+    }
+    const RunsOut outs[] = {{unique_out, n * (size_t)t.bytes, "d_unique_out"}, {counts_out, n * 4, "d_counts_out"},
+                            {offsets_out, (n + 1) * 4, "d_offsets_out"}, {first_index_out, n * 4, "d_first_index_out"},
+                            {inverse_out, n * 4, "d_inverse_out"}};
+    if (runs_check_buffers("unique", keys_in, n * (size_t)t.bytes, outs, 5, num_unique_out, work)) return ADLHIP_FAILURE;
+    const bool index_path = d->unique_algo == 1 || first_index_out || inverse_out;
+    const UniqueLayout L = unique_layout(d, (size_t)t.bytes, n);
+    const size_t need = index_path ? L.index_total : L.keys_total;
+    if (work_bytes < need)
+        return fail("work buffer too small: %zu < %zu (adlhip_unique_scratch_bytes, want_index = %d)", work_bytes, need, index_path ? 1 : 0);
+    if (t.bytes == 4)
+        return unique_run<uint32_t>(d, t, order, index_path, (const uint32_t*)keys_in, n, (uint32_t*)unique_out, counts_out, offsets_out,
+                                    first_index_out, inverse_out, num_unique_out, work);
+    return unique_run<uint64_t>(d, t, order, index_path, (const uint64_t*)keys_in, n, (uint64_t*)unique_out, counts_out, offsets_out,
+                                first_index_out, inverse_out, num_unique_out, work);
+}
+
 int adlhip_segment_sort(adlhip_device* d, int elem_kind, void* data, const uint32_t* seg_start, size_t num_segments,
                         size_t max_segment, int low_bits)
 {
@@ -3250,6 +3454,12 @@ int adlhip_set_param(adlhip_device* d, const char* name, int value)
     } else if (!strcmp(name, "debug.topk_rows_grid")) {
         if (value < 0) return fail("debug.topk_rows_grid must be >= 0");
         d->topk_rows_grid = value;
+    } else if (!strcmp(name, "unique.algo")) {
+        if (value != -1 && value != 1) return fail("unique.algo must be -1 (by the outputs asked) or 1 (always the index path)");
+        d->unique_algo = value;
+    } else if (!strcmp(name, "debug.unique_grid")) {
+        if (value < 0) return fail("debug.unique_grid must be >= 0");
+        d->unique_grid = value;
     } else if (!strcmp(name, "debug.finish16_alg")) {
         if (value != -1 && value != 1 && value != 2) return fail("debug.finish16_alg must be -1 (the adopted variant), 1 (the round-4 kernel) or 2");
         d->finish16_alg = value;
@@ -3296,6 +3506,8 @@ int adlhip_get_param(adlhip_device* d, const char* name, int* value)
     else if (!strcmp(name, "topk.algo")) *value = d->topk_algo;
     else if (!strcmp(name, "topk.rows_algo")) *value = d->topk_rows_algo;
     else if (!strcmp(name, "debug.topk_rows_grid")) *value = d->topk_rows_grid;
+    else if (!strcmp(name, "unique.algo")) *value = d->unique_algo;
+    else if (!strcmp(name, "debug.unique_grid")) *value = d->unique_grid;
     else if (!strcmp(name, "partition.lookback")) *value = d->partition_lookback;
     else if (!strcmp(name, "sort.net_lookback")) *value = d->net_lookback;
     else if (!strcmp(name, "debug.finish16_alg")) *value = d->finish16_alg;

@@ -10,12 +10,15 @@
     p.argsort(device, keys, n, descending=False)           # -> Buffer(uint32): the stable sorting permutation
     p.topk(device, keys, n, k, descending=False)           # -> Buffer(uint32): its first k entries, by selection
     p.topkRows(device, keys, rows, cols, k)                # -> Buffer(uint32): rows x k columns, top-k of every row
+    p.unique(device, keys, n, counts=True, inverse=True)   # -> UniqueResult: distinct keys in sorted order, counts, inverse, ...
+    p.runLengthEncode(device, keys, n, counts=True)        # -> UniqueResult: the runs of keys that are already grouped
 
 Like the reference object it owns lazily grown device scratch (m_u32WorkBuffer[0] = ping-pong data
 buffer, m_u32WorkBuffer[1] = histogram table; Pprims.h:44-45, Pprims.cpp:226-232, :332-337) and must be
 destroyed (close()) before DeviceUtils.deallocate, which refuses while memory is live (Adl.inl:102).
 Calls enqueue and return without synchronising, as the reference's GPU branches do.
 """
+import collections
 import ctypes
 
 import numpy as np
@@ -32,6 +35,10 @@ ELEM_SOA32 = 3
 # ADLHIP_KEY_* by element type (include/adlhip.h, "typed keys, order, argsort")
 KEY_TYPES = {np.dtype(np.uint32): 0, np.dtype(np.int32): 1, np.dtype(np.float32): 2,
              np.dtype(np.uint64): 3, np.dtype(np.int64): 4, np.dtype(np.float64): 5}
+
+# What unique / runLengthEncode return: device Buffers (None where not asked).  `count` is a one-element uint32 Buffer that holds R, the
+# number of runs; unique, counts and firstIndex have n elements of which the first R are written, offsets n + 1 (R + 1 written), inverse n.
+UniqueResult = collections.namedtuple("UniqueResult", "unique counts offsets firstIndex inverse count")
 
 
 class Pprims:
@@ -265,6 +272,106 @@ class Pprims:
                 out.release()
             raise
         return out
+
+    # -- unique keys, run lengths, inverse indices (no reference counterpart; include/adlhip.h adlhip_unique_typed)
+    @staticmethod
+    def _runs_outputs(what, device, n, asked):
+        """asked: [(name, value, elements)], value False / None (not asked), True (a new uint32 Buffer) or a uint32 Buffer of at least
+        `elements` elements to fill.  Checks every value first -- nothing is allocated when one is refused -- then returns the Buffers
+        (None where not asked) and the ones that were allocated here."""
+        for name, v, elems in asked:
+            if v is None or v is False or v is True:
+                continue
+            if not hasattr(v, "getSize") or np.dtype(v.dtype) != np.uint32 or v.getSize() < elems:
+                raise AdlHipError("%s: %s must be True or a uint32 buffer of %d elements" % (what, name, elems))
+        out, own = [], []
+        for name, v, elems in asked:
+            if v is True:
+                v = Buffer(device, elems, np.uint32)
+                own.append(v)
+            out.append(v if v is not None and v is not False else None)
+        return out, own
+
+    def unique(self, device, keys, n, descending=False, counts=False, offsets=False, firstIndex=False, inverse=False,
+               uniqueOut=None, countOut=None):
+        """The distinct keys among the first n of `keys` in the order of sortKeys(descending) -> UniqueResult.  Keys are equal when
+        their bits are: -0 and +0 are two keys, NaNs with different payloads too.  With R distinct keys (result.count, on the device):
+        unique[r] the r-th key, counts[r] how often it occurs, offsets[r] where its run starts in the sorted order (offsets[R] = n),
+        firstIndex[r] the lowest position in `keys` that holds it, inverse[i] the r of keys[i].  counts / offsets / firstIndex /
+        inverse: True for a new uint32 Buffer, or a uint32 Buffer to fill (n elements; offsets n + 1).  uniqueOut (keys' dtype, n
+        elements) and countOut (uint32, 1 element) likewise replace the Buffers allocated here.  `keys` is left intact.  Enqueues and
+        returns; read result.count (toHost) to learn R."""
+        if device is None:
+            raise AdlHipError("unique needs a device")
+        kt = self._key_type(keys, "unique")
+        n = int(n)
+        if n < 0 or keys.getSize() < n:
+            raise AdlHipError("unique: n = %d outside [0, %d]" % (n, keys.getSize()))
+        if uniqueOut is not None and (np.dtype(uniqueOut.dtype) != np.dtype(keys.dtype) or uniqueOut.getSize() < n):
+            raise AdlHipError("unique: uniqueOut must hold n elements of %s" % keys.dtype)
+        if countOut is not None and (np.dtype(countOut.dtype) != np.uint32 or countOut.getSize() < 1):
+            raise AdlHipError("unique: countOut must hold one uint32 element")
+        (c, o, f, i), own = self._runs_outputs("unique", device, n, [("counts", counts, n), ("offsets", offsets, n + 1),
+                                                                     ("firstIndex", firstIndex, n), ("inverse", inverse, n)])
+        try:
+            lib = _lib.load()
+            wb = ctypes.c_size_t()
+            want_index = 1 if (f is not None or i is not None or device.getParam("unique.algo") == 1) else 0
+            check(lib.adlhip_unique_scratch_bytes(device._h, kt, n, want_index, ctypes.byref(wb)), "adlhip_unique_scratch_bytes")
+            self._scratch(device, 0, wb.value)
+            if uniqueOut is None:
+                uniqueOut = Buffer(device, n, keys.dtype)
+                own.append(uniqueOut)
+            if countOut is None:
+                countOut = Buffer(device, 1, np.uint32)
+                own.append(countOut)
+
+            def p(b):
+                return b.ptr() if b is not None else None
+            check(lib.adlhip_unique_typed(device._h, kt, 1 if descending else 0, keys.ptr(), n, uniqueOut.ptr(), p(c), p(o), p(f), p(i),
+                                          countOut.ptr(), self.m_work.ptr(), self.m_work.getSize()), "unique")
+        except AdlHipError:
+            for b in own:
+                b.release()
+            raise
+        return UniqueResult(uniqueOut, c, o, f, i, countOut)
+
+    def runLengthEncode(self, device, keys, n, counts=False, offsets=False, uniqueOut=None, countOut=None):
+        """The runs (maximal stretches of adjacent keys with identical bits) of the first n of `keys`, which are already grouped; any
+        element type of 4 or 8 bytes -> UniqueResult (firstIndex and inverse are None).  With R runs (result.count): unique[r] the
+        key of run r, offsets[r] its first position (offsets[R] = n), counts[r] its length.  Buffers as in unique()."""
+        if device is None:
+            raise AdlHipError("runLengthEncode needs a device")
+        kb = np.dtype(keys.dtype).itemsize
+        if kb not in (4, 8):
+            raise AdlHipError("runLengthEncode: unsupported key type %s (4 or 8 bytes)" % keys.dtype)
+        n = int(n)
+        if n < 0 or keys.getSize() < n:
+            raise AdlHipError("runLengthEncode: n = %d outside [0, %d]" % (n, keys.getSize()))
+        if uniqueOut is not None and (np.dtype(uniqueOut.dtype) != np.dtype(keys.dtype) or uniqueOut.getSize() < n):
+            raise AdlHipError("runLengthEncode: uniqueOut must hold n elements of %s" % keys.dtype)
+        if countOut is not None and (np.dtype(countOut.dtype) != np.uint32 or countOut.getSize() < 1):
+            raise AdlHipError("runLengthEncode: countOut must hold one uint32 element")
+        (c, o), own = self._runs_outputs("runLengthEncode", device, n, [("counts", counts, n), ("offsets", offsets, n + 1)])
+        try:
+            lib = _lib.load()
+            wb = ctypes.c_size_t()
+            check(lib.adlhip_run_length_encode_scratch_bytes(device._h, kb, n, ctypes.byref(wb)), "adlhip_run_length_encode_scratch_bytes")
+            self._scratch(device, 0, wb.value)
+            if uniqueOut is None:
+                uniqueOut = Buffer(device, n, keys.dtype)
+                own.append(uniqueOut)
+            if countOut is None:
+                countOut = Buffer(device, 1, np.uint32)
+                own.append(countOut)
+            check(lib.adlhip_run_length_encode(device._h, kb, keys.ptr(), n, uniqueOut.ptr(), c.ptr() if c is not None else None,
+                                               o.ptr() if o is not None else None, countOut.ptr(), self.m_work.ptr(),
+                                               self.m_work.getSize()), "runLengthEncode")
+        except AdlHipError:
+            for b in own:
+                b.release()
+            raise
+        return UniqueResult(uniqueOut, c, o, None, None, countOut)
 
     def copy(self, device, dst, src, n):
         """Pprims::copy (Pprims.cpp:31-67, commented out in the reference): first n elements of src -> dst."""

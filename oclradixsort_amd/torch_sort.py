@@ -6,6 +6,8 @@ back-end on torch's own stream.
     indices = s.argsort(t, descending=True)
     values, indices = s.topk(t, 10)         # the 10 largest, largest first; ties to the lower index
     values, indices = s.topk_rows(m, 10)    # m: 2-D or more; the same along the last dimension of every row
+    u, inverse, counts = s.unique(t, return_inverse=True, return_counts=True)   # torch.unique(t) on any number of dimensions
+    u, counts = s.unique_consecutive(t, return_counts=True)                      # torch.unique_consecutive(t), 1-D
     s.close()
 
 Always out of place and always stable.  The ONE difference from `torch.sort(t, stable=True)`: floats are ordered by
@@ -145,6 +147,82 @@ class TorchSorter:
                              keysOut=self._wrap(values, npdt), indexOut=self._wrap(idx32, np.uint32))
         self.device.checkFault()
         return values, idx32.to(torch.int64) & 0xffffffff
+
+    def _flat_input(self, t, what, one_dim):
+        """the checks of topk (dtype, device, size, stream) for `what`; returns t flattened, contiguous and 16-byte aligned (a copy only
+        for a strided or oddly placed input; the input is never written)"""
+        if not isinstance(t, torch.Tensor):
+            raise TypeError("TorchSorter: expected a torch.Tensor, got %s" % type(t).__name__)
+        if t.dtype not in _NP_DTYPE:
+            raise TypeError("TorchSorter: dtype %s unsupported (int32, int64, float32, float64)" % t.dtype)
+        if one_dim and t.dim() != 1:
+            raise ValueError("TorchSorter.%s: 1-D tensors only, got %d dimensions" % (what, t.dim()))
+        if t.device != self.torch_device:
+            raise ValueError("TorchSorter: tensor is on %s, the sorter on %s" % (t.device, self.torch_device))
+        if t.numel() >= 1 << 32:
+            raise ValueError("TorchSorter: fewer than 2^32 elements")
+        if torch.cuda.current_stream(self.torch_device).cuda_stream != self.raw_stream:
+            raise RuntimeError("TorchSorter: bound to the stream that was current at construction; another stream is current now")
+        flat = t.contiguous().reshape(-1)
+        if flat.data_ptr() % 16:
+            flat = flat.clone()
+        return flat
+
+    def unique(self, t, return_inverse=False, return_counts=False):
+        """What torch.unique(t, sorted=True, return_inverse=..., return_counts=...) returns (dim=None): t of any number of dimensions is
+        flattened; the distinct values ascending, then -- where asked -- inverse (t's shape, int64) and counts (int64).  Equal to
+        torch's results on inputs without NaN and -0: keys are equal when their bits are, so -0 and +0 count as two values (-0
+        first) and NaNs are grouped by bit pattern (sign bit set: first).  Like torch.unique this makes ONE host read, of the number
+        of distinct values, to size the result tensors: the call waits for the stream."""
+        flat = self._flat_input(t, "unique", False)
+        n = flat.numel()
+        if n == 0:
+            out = (torch.empty(0, dtype=t.dtype, device=t.device),)
+            if return_inverse:
+                out += (torch.empty(t.shape, dtype=torch.int64, device=t.device),)
+            if return_counts:
+                out += (torch.empty(0, dtype=torch.int64, device=t.device),)
+            return out if len(out) > 1 else out[0]
+        npdt = _NP_DTYPE[t.dtype]
+        uniq = torch.empty(n, dtype=t.dtype, device=t.device)
+        count = torch.empty(1, dtype=torch.int32, device=t.device)
+        inv32 = torch.empty(n, dtype=torch.int32, device=t.device) if return_inverse else None   # uint32 in int32 tensors
+        cnt32 = torch.empty(n, dtype=torch.int32, device=t.device) if return_counts else None
+        self.pprims.unique(self.device, self._wrap(flat, npdt), n,
+                           counts=self._wrap(cnt32, np.uint32) if return_counts else False,
+                           inverse=self._wrap(inv32, np.uint32) if return_inverse else False,
+                           uniqueOut=self._wrap(uniq, npdt), countOut=self._wrap(count, np.uint32))
+        self.device.checkFault()
+        r = int(count.item()) & 0xffffffff   # the one host read
+        out = (uniq[:r].clone(),)
+        if return_inverse:
+            out += ((inv32.to(torch.int64) & 0xffffffff).reshape(t.shape),)
+        if return_counts:
+            out += (cnt32[:r].to(torch.int64) & 0xffffffff,)
+        return out if len(out) > 1 else out[0]
+
+    def unique_consecutive(self, t, return_counts=False):
+        """What torch.unique_consecutive(t, return_counts=...) returns for a 1-D tensor: one value per run of adjacent equal elements,
+        in input order, and -- where asked -- the run lengths (int64).  Equal to torch's result on inputs without NaN and -0 (bits
+        decide equality, as in unique).  Like torch.unique_consecutive this makes ONE host read, of the number of runs, to size the
+        result tensors: the call waits for the stream."""
+        flat = self._flat_input(t, "unique_consecutive", True)
+        n = flat.numel()
+        if n == 0:
+            out = torch.empty(0, dtype=t.dtype, device=t.device)
+            return (out, torch.empty(0, dtype=torch.int64, device=t.device)) if return_counts else out
+        npdt = _NP_DTYPE[t.dtype]
+        uniq = torch.empty(n, dtype=t.dtype, device=t.device)
+        count = torch.empty(1, dtype=torch.int32, device=t.device)
+        cnt32 = torch.empty(n, dtype=torch.int32, device=t.device) if return_counts else None
+        self.pprims.runLengthEncode(self.device, self._wrap(flat, npdt), n,
+                                    counts=self._wrap(cnt32, np.uint32) if return_counts else False,
+                                    uniqueOut=self._wrap(uniq, npdt), countOut=self._wrap(count, np.uint32))
+        self.device.checkFault()
+        r = int(count.item()) & 0xffffffff   # the one host read
+        if return_counts:
+            return uniq[:r].clone(), cnt32[:r].to(torch.int64) & 0xffffffff
+        return uniq[:r].clone()
 
     def sort(self, t, descending=False):
         """(values, indices) like torch.sort(t, descending=descending, stable=True); indices are int64."""

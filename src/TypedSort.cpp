@@ -2,7 +2,8 @@
 // u32 bit patterns, ascending: Tahoe/ParallelPrimitives/Pprims.h:38-41).  A TYPE_CL (HIP) device runs adlhip_sort_keys_typed /
 // adlhip_argsort_typed; a TYPE_HOST device sorts on the CPU with std::stable_sort on the same total order, as the reference's
 // host branches do for u32 keys (Pprims.cpp:202-212, :306-316).  Pprims::topK: adlhip_topk_typed, or a partial sort on (ordinal,
-// position) on the host.  Pprims::topKRows: adlhip_topk_rows_typed, or the same partial sort per row.
+// position) on the host.  Pprims::topKRows: adlhip_topk_rows_typed, or the same partial sort per row.  Pprims::unique:
+// adlhip_unique_typed (it waits for the count), or the runs of the host argsort.
 #include <Tahoe/ParallelPrimitives/Pprims.h>
 
 #include <algorithm>
@@ -218,6 +219,56 @@ void Pprims::topKRowsTyped(const adl::Device* device, const adl::Buffer<T>& keys
     ADLASSERT(rc == ADLHIP_SUCCESS);
 }
 
+template <typename T>
+int Pprims::uniqueTyped(const adl::Device* device, const adl::Buffer<T>& keys, adl::Buffer<T>& uniqueOut, adl::Buffer<u32>& countsOut, int n,
+                        bool descending)
+{
+    ADLASSERT(n >= 0);
+    if (n <= 0) return 0;
+    ADLASSERT(device != 0);
+    ADLASSERT((adl::u64)n <= keys.getSize() && (adl::u64)n <= uniqueOut.getSize() && (adl::u64)n <= countsOut.getSize());
+    if (!onDevice(device)) {
+        ADLASSERT(device->getType() == adl::TYPE_HOST);   // a HIP device never falls back to the CPU
+        if (device->getType() != adl::TYPE_HOST) return 0;
+        T* host = keys.getHostPtr(n);
+        T* uout = uniqueOut.getHostPtr(n);
+        u32* cnt = countsOut.getHostPtr(n);
+        adl::DeviceUtils::waitForCompletion(device);
+        std::vector<Ranked<typename KeyTraits<T>::Bits> > order;
+        hostArgsort(host, n, descending, order);
+        int runs = 0;
+        for (int j = 0; j < n; ++j) {   // equal ordinals are equal bits: the ordinal is a bijection
+            if (j == 0 || order[j].ord != order[j - 1].ord) {
+                uout[runs] = host[order[j].idx];
+                cnt[runs] = 0;
+                ++runs;
+            }
+            ++cnt[runs - 1];
+        }
+        keys.returnHostPtr(host);
+        uniqueOut.returnHostPtr(uout);
+        countsOut.returnHostPtr(cnt);
+        adl::DeviceUtils::waitForCompletion(device);
+        return runs;
+    }
+    size_t wb = 0;
+    const int rcq = adlhip_unique_scratch_bytes(device->hip(), KeyTraits<T>::TYPE, (size_t)n, 0, &wb);
+    ADLASSERT(rcq == ADLHIP_SUCCESS);
+    reserve(device, 16, wb);   // m_tmp holds the count word
+    const int rc = adlhip_unique_typed(device->hip(), KeyTraits<T>::TYPE, descending ? ADLHIP_ORDER_DESCENDING : ADLHIP_ORDER_ASCENDING,
+                                       keys.m_ptr, (size_t)n, uniqueOut.m_ptr, (uint32_t*)countsOut.m_ptr, 0, 0, 0, (uint32_t*)m_tmp->m_ptr,
+                                       m_work->m_ptr, (size_t)m_work->getSize());
+    if (rc != ADLHIP_SUCCESS) TH_LOG_ERROR("Pprims::unique: %s\n", adlhip_last_error());
+    ADLASSERT(rc == ADLHIP_SUCCESS);
+    if (rc != ADLHIP_SUCCESS) return 0;
+    unsigned char word[4] = {0, 0, 0, 0};
+    m_tmp->read(word, 4);
+    adl::DeviceUtils::waitForCompletion(device);
+    u32 runs = 0;
+    memcpy(&runs, word, 4);
+    return (int)runs;
+}
+
 #define TAHOE_TYPED(T)                                                                                                              \
     void Pprims::sortKeys(const adl::Device* device, const adl::Buffer<T>& inout, int n, bool descending)                         \
     {                                                                                                                               \
@@ -236,6 +287,11 @@ void Pprims::topKRowsTyped(const adl::Device* device, const adl::Buffer<T>& keys
                           int rows, int cols, int k, bool descending, int rowStride)                                                \
     {                                                                                                                               \
         topKRowsTyped<T>(device, keys, keysOut, indexOut, rows, cols, k, descending, rowStride);                                    \
+    }                                                                                                                               \
+    int Pprims::unique(const adl::Device* device, const adl::Buffer<T>& keys, adl::Buffer<T>& uniqueOut, adl::Buffer<u32>& countsOut, \
+                       int n, bool descending)                                                                                      \
+    {                                                                                                                               \
+        return uniqueTyped<T>(device, keys, uniqueOut, countsOut, n, descending);                                                   \
     }
 TAHOE_TYPED(int)
 TAHOE_TYPED(float)
