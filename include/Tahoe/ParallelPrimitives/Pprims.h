@@ -9,6 +9,7 @@
 //   topK      the first k entries of argsort, by selection           (new: adlhip_topk_typed)
 //   topKRows  topK of every row of a rows x cols matrix              (new: adlhip_topk_rows_typed)
 //   unique    distinct keys in sorted order and their counts         (new: adlhip_unique_typed)
+//   reduceByKey  sum / min / max of the values of every distinct key  (new: adlhip_reduce_by_key_typed)
 // Same argument meaning; differences, all supersets: any n >= 0 (the reference needs n % 256 == 0 for
 // keys), scan has no 1,048,576-element limit, sortBits < 32 also works on 64-bit keys up to 64.
 // Device work is enqueued and the call returns (no sync), as in the reference's GPU branches.
@@ -132,6 +133,16 @@ public:
                bool descending = false);
     int unique(const adl::Device* device, const adl::Buffer<u64>& keys, adl::Buffer<u64>& uniqueOut, adl::Buffer<u32>& countsOut, int n,
                bool descending = false);
+
+    // op (ADLHIP_REDUCE_SUM / _MIN / _MAX) over the values of every distinct key among the first n of keys: uniqueOut[r] in the order
+    // of sortKeys(descending), reducedOut[r] the result for that key, r < R; both hold n elements, those at R and beyond are left alone.
+    // K and V: int, float, long long, double, u32, u64, independently.  Integer sums wrap; float sums are IEEE adds in an unspecified
+    // but reproducible association; min / max follow the ascending order of sortKeys (floats: totalOrder) whatever `descending` says,
+    // and return the bits of an element.  keys and values are left intact.  Like unique this one WAITS and returns R.  A TYPE_HOST
+    // device sorts on the CPU (std::stable_sort on the same order) and reduces in a loop
+    template <typename K, typename V>
+    int reduceByKey(const adl::Device* device, const adl::Buffer<K>& keys, const adl::Buffer<V>& values, adl::Buffer<K>& uniqueOut,
+                    adl::Buffer<V>& reducedOut, int n, int op = ADLHIP_REDUCE_SUM, bool descending = false);
 
 private:
     template <typename T> int uniqueTyped(const adl::Device* device, const adl::Buffer<T>& keys, adl::Buffer<T>& uniqueOut, adl::Buffer<u32>& countsOut,

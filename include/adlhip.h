@@ -370,6 +370,69 @@ int adlhip_unique_typed(adlhip_device* dev, int key_type, int order, const void*
                         uint32_t* d_first_index_out_or_null, uint32_t* d_inverse_out_or_null,
                         uint32_t* d_num_unique_out, void* d_work, size_t work_bytes);
 
+/* ---- reduce values by key: per-run and per-key sum, min, max (no reference counterpart) ------- */
+
+/* The group-by step behind a sort: with the runs of adlhip_run_length_encode (grouped keys) or the groups of adlhip_unique_typed
+ * (unsorted keys), d_reduced_out[r] = op over the values of run / group r -- thrust's reduce_by_key, or torch's
+ * unique(return_inverse = True) followed by index_add_ / scatter_reduce_.  value_type is one of the six ADLHIP_KEY_* codes, used as a
+ * VALUE type; the key width (4 or 8 bytes) and the value width are independent, every combination is served.
+ *
+ * op:
+ *   ADLHIP_REDUCE_SUM, integer values: wrap-around in the value's width -- signed and unsigned of one width are the same arithmetic --;
+ *     the result has the value's type.
+ *   ADLHIP_REDUCE_SUM, float values: IEEE adds of the run's elements only, in an unspecified association.  DETERMINISTIC: the same
+ *     input, device and knobs give the same bits on every call (no float atomics; the association depends on n and the launch grid
+ *     alone).  No identity element stands in for "nothing yet": a run of one element returns that element's bits unchanged (-0,
+ *     signalling NaNs and NaN payloads included), a run of -0 only sums to -0.
+ *   ADLHIP_REDUCE_MIN / _MAX: taken in the ASCENDING order of the typed sorts -- integers by value, floats by IEEE totalOrder:
+ *     -NaN < -inf < ... < -0 < +0 < ... < +inf < +NaN --, independent of the `order` argument, which orders the KEYS only.  The result
+ *     is the bits of an element of the run, so it is bit-exact.  (torch's amin / amax propagate NaNs instead.)
+ */
+#define ADLHIP_REDUCE_SUM 0
+#define ADLHIP_REDUCE_MIN 1
+#define ADLHIP_REDUCE_MAX 2
+
+/* Contract common to adlhip_reduce_runs and adlhip_reduce_by_key_typed, the same as the block above: n < 2^32.  d_keys_in and d_vals_in are
+ * never written.  d_unique_out, d_reduced_out and the count word are required, counts and offsets optional.  unique, reduced and counts
+ * hold n elements, offsets n + 1; with R the number of runs, the elements at R and beyond (offsets: R + 1 and beyond) are NEVER written.
+ * Both inputs, d_work and every output array are 16-byte aligned, the count word 4-byte aligned; no output (the count word included)
+ * may overlap d_keys_in or d_vals_in.  n == 0 enqueues one 4-byte clear of the count word and nothing else.  A NULL required pointer, a
+ * misaligned pointer, an overlap, an unknown key_bytes, key_type, value_type, op or order, and a work buffer one byte short (the
+ * message names the needed size) fail before anything is enqueued.  The calls enqueue and return: nothing data-dependent reaches the
+ * host, nothing is remembered between calls, all state lives in d_work -- whose contents on entry are arbitrary -- and the handle owns
+ * no device word of it.  No kernel of the reduce stage waits on another workgroup or uses an atomic to global memory.
+ *
+ * Work bytes, every part rounded up to 256 bytes, with CUs = adlhip_info.compute_units, kb / vb = bytes per key / value:
+ *   W_reduce(n) = 16 CUs (one head count per workgroup of the largest grid, 4 workgroups per CU) + 16 CUs (one "chunk has a head" flag
+ *                 each) + 32 CUs (one tail aggregate each, 8 bytes whatever vb) + 32 CUs (one carry each) + 4 (n + 1) (offsets, used
+ *                 when counts are asked without offsets)
+ *   adlhip_reduce_runs_scratch_bytes   = W_reduce(n)
+ *   adlhip_reduce_by_key_scratch_bytes = W_reduce(n) + n kb (the sorted keys) + n vb (the values in sorted order) + W_argsort(n)
+ * W_argsort = *work_bytes of adlhip_sort_typed_scratch_bytes, mode 2 (= mode 1).  The value suffices for every n' <= n. */
+
+/* Keys that are already grouped (key_bytes: 4 or 8; runs are maximal stretches of identical key bits, grouped but unsorted keys A A B A
+ * give three runs): unique, counts, offsets and *d_num_runs_out are exactly what adlhip_run_length_encode gives for the same keys, and
+ * d_reduced_out[r] = op over d_vals_in[off[r] .. off[r + 1]).  Three or four launches over tiles of 2048 elements: the workgroups walk
+ * their chunks and write head count, head flag and the aggregate behind their last head; one workgroup scans the counts (R) and, segmented
+ * by the flags, the aggregates, which gives every chunk the part of its first run that lies in front of it; the workgroups walk their
+ * chunks again with a segmented scan per tile -- heads write unique and offsets, run ends write reduced; counts are the differences of
+ * the offsets. */
+int adlhip_reduce_runs_scratch_bytes(adlhip_device* dev, int key_bytes, int value_type, size_t n, size_t* work_bytes);
+int adlhip_reduce_runs(adlhip_device* dev, int key_bytes, const void* d_keys_in, int value_type, int op, const void* d_vals_in, size_t n,
+                       void* d_unique_out, void* d_reduced_out, uint32_t* d_counts_out_or_null, uint32_t* d_offsets_out_or_null,
+                       uint32_t* d_num_runs_out, void* d_work, size_t work_bytes);
+
+/* Unsorted keys: the groups appear in the order of adlhip_sort_keys_typed(key_type, order), key equality by bits; unique, counts,
+ * offsets and *d_num_unique_out are exactly what adlhip_unique_typed gives, and d_reduced_out[r] = op over the values whose key has the
+ * bits of d_unique_out[r].  The stable typed pairs sort (what adlhip_sort_pairs_typed runs) reads the caller's arrays and gathers
+ * sorted keys and values straight into d_work -- the in-place entry point's copy in and copy back are not needed --, then the reduce
+ * stage runs there.  A sort that refuses (knobs changed since the scratch was sized) fails the call with the sort's message. */
+int adlhip_reduce_by_key_scratch_bytes(adlhip_device* dev, int key_type, int value_type, size_t n, size_t* work_bytes);
+int adlhip_reduce_by_key_typed(adlhip_device* dev, int key_type, int order, const void* d_keys_in, int value_type, int op,
+                               const void* d_vals_in, size_t n, void* d_unique_out, void* d_reduced_out,
+                               uint32_t* d_counts_out_or_null, uint32_t* d_offsets_out_or_null,
+                               uint32_t* d_num_unique_out, void* d_work, size_t work_bytes);
+
 /* ---- segments finished in LDS (no reference counterpart) ------------------------------------- */
 
 /* Sorts, stably and in place, every segment [d_seg_start[s], d_seg_start[s + 1]) of an array of u32 keys
@@ -533,6 +596,9 @@ int adlhip_generate_keys(adlhip_device* dev, int elem_kind, void* dptr, size_t n
  *                      offsets bit for bit either way
  *   "debug.unique_grid" workgroups the run stage of adlhip_run_length_encode / adlhip_unique_typed is launched with at most (0 [default]:
  *                      4 per CU; larger values change nothing); tests set it to make few workgroups take many tiles
+ *   "debug.reduce_grid" workgroups the reduce stage of adlhip_reduce_runs / adlhip_reduce_by_key_typed is launched with at most (0
+ *                      [default]: 4 per CU; larger values change nothing); tests set it to make few workgroups take many tiles.  Float
+ *                      sums may differ in the last bits between two values of it (another association), never between two calls
  *   "sort.net_lookback" 1 [default] / 0: the LSD passes of the large sort's safety net on whole keys are look-back passes -- the
  *                      one-sweep path's histogram, tables and tile body, taken in turns by the net's resident workgroups, four
  *                      passes at a time (u64 keys: two rounds) -- instead of count -> scan -> scatter passes with per-workgroup

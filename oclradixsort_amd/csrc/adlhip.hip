@@ -28,6 +28,7 @@
 #include "select_kernels.hpp"
 #include "toprows_kernels.hpp"
 #include "unique_kernels.hpp"
+#include "reduce_kernels.hpp"
 
 // The large sort's kernels and the per-digit passes' are instantiated in kernels_finish.hip / kernels_passes.hip / kernels_perdigit.hip (translation units of
 // their own, compiled beside this one); here they are only declared.  -DADLHIP_SINGLE_TU builds everything in this file (what tools/gen_large_kernels.py reads the list from).
@@ -40,6 +41,7 @@
 #include "select_kernels.inc"
 #include "toprows_kernels.inc"
 #include "unique_kernels.inc"
+#include "reduce_kernels.inc"
 #undef X
 #endif
 
@@ -127,6 +129,7 @@ struct adlhip_device {
     int topk_rows_grid = 0;                 // "debug.topk_rows_grid": workgroups of the row kernel at most (0: kTopkRowsWgsPerCu per CU)
     int unique_algo = -1;                   // "unique.algo": -1 the keys path unless first_index or inverse is asked, 1 always the index path
     int unique_grid = 0;                    // "debug.unique_grid": workgroups of the run stage at most (0: kUniqueWgsPerCu per CU)
+    int reduce_grid = 0;                    // "debug.reduce_grid": workgroups of the reduce stage at most (0: kReduceWgsPerCu per CU)
     adlhip::DictBlock* d_dict = nullptr;    // its dictionary and counters (handle-owned; rebuilt by every net that uses them)
     uint32_t* d_msd2 = nullptr;   // the large sort's handle-owned words, allocated with the handle: cursors of pass 1 (256, one
                                   // 128-byte line each) and pass 2 (65536), overflow flag, done counter, the safety net's barrier
@@ -2477,6 +2480,145 @@ int unique_run(adlhip_device* d, const KeyTypeInfo& t, int order, bool index_pat
     return runs_stage<U>(d, sorted, nullptr, n, unique_out, counts, offsets, nullptr, nullptr, num_out, work);
 }
 
+// ---- reduce by key (reduce_kernels.hpp; no reference counterpart) --------------------------------------------------------------------
+// Work of the reduce stage, per workgroup of the largest grid: [head counts: u32][head flags: u32][tail aggregates: 8 bytes][carries: 8
+// bytes], then [offsets: n + 1 u32, used when the caller wants counts but passes no offsets], each rounded up to 256 bytes.
+constexpr int kReduceWgsPerCu = 4;   // grid of the reduce stage per CU at most ("debug.reduce_grid" lowers it)
+struct ReduceLayout {
+    size_t off_flag, off_agg, off_carry, off_offsets, total;
+};
+ReduceLayout reduce_layout(const adlhip_device* d, size_t n)
+{
+    const size_t cap = (size_t)d->prop.multiProcessorCount * kReduceWgsPerCu;
+    ReduceLayout L;
+    L.off_flag = align_up(cap * 4, 256);
+    L.off_agg = L.off_flag + align_up(cap * 4, 256);
+    L.off_carry = L.off_agg + align_up(cap * 8, 256);
+    L.off_offsets = L.off_carry + align_up(cap * 8, 256);
+    L.total = L.off_offsets + align_up((n + 1) * 4, 256);
+    return L;
+}
+
+// Work of adlhip_reduce_by_key_typed: [reduce stage][the sorted keys, n][the permuted values, n][work of the typed pairs sort]
+struct ReduceByKeyLayout {
+    size_t off_keys, off_vals, off_swork, total;
+};
+ReduceByKeyLayout reduce_by_key_layout(const adlhip_device* d, size_t key_bytes, size_t value_bytes, size_t n)
+{
+    ReduceByKeyLayout L;
+    L.off_keys = reduce_layout(d, n).total;
+    L.off_vals = L.off_keys + align_up(n * key_bytes, 256);
+    L.off_swork = L.off_vals + align_up(n * value_bytes, 256);
+    L.total = L.off_swork + align_up(soa_wide_layout(d, n).total, 256);
+    return L;
+}
+
+struct ValueTypeInfo {
+    int bytes, kind;
+};
+int reduce_value_info(int value_type, int op, ValueTypeInfo* out)
+{
+    if (value_type < ADLHIP_KEY_U32 || value_type > ADLHIP_KEY_F64)
+        return fail("value_type must be one of ADLHIP_KEY_U32 .. ADLHIP_KEY_F64 (0..5), got %d", value_type);
+    if (op != ADLHIP_REDUCE_SUM && op != ADLHIP_REDUCE_MIN && op != ADLHIP_REDUCE_MAX)
+        return fail("op must be ADLHIP_REDUCE_SUM (0), ADLHIP_REDUCE_MIN (1) or ADLHIP_REDUCE_MAX (2), got %d", op);
+    out->bytes = value_type < ADLHIP_KEY_U64 ? 4 : 8;
+    out->kind = value_type % 3;
+    return ADLHIP_SUCCESS;
+}
+
+// the reduce stage on n > 0 grouped keys and their values
+template <typename K, typename W, int OP>
+int reduce_stage_op(adlhip_device* d, const K* keys, const W* vals, size_t n, adlhip::RedCodec codec, K* unique_out, W* reduced_out,
+                    uint32_t* counts, uint32_t* offsets, uint32_t* num_out, void* work)
+{
+    const ReduceLayout L = reduce_layout(d, n);
+    char* w = static_cast<char*>(work);
+    uint32_t* heads = reinterpret_cast<uint32_t*>(w);
+    uint32_t* flag = reinterpret_cast<uint32_t*>(w + L.off_flag);
+    W* agg = reinterpret_cast<W*>(w + L.off_agg);
+    W* carry = reinterpret_cast<W*>(w + L.off_carry);
+    if (counts && !offsets) offsets = reinterpret_cast<uint32_t*>(w + L.off_offsets);
+    // the chunk split of runs_stage, on tiles of kRedTile elements
+    constexpr size_t tile = (size_t)adlhip::kRedTile;
+    const size_t tiles = (n + tile - 1) / tile;
+    size_t cap = (size_t)d->prop.multiProcessorCount * kReduceWgsPerCu;
+    if (d->reduce_grid > 0) cap = std::min(cap, (size_t)d->reduce_grid);
+    const size_t tiles_per_wg = (tiles + cap - 1) / cap;
+    const uint32_t wgs = (uint32_t)((tiles + tiles_per_wg - 1) / tiles_per_wg);
+    const uint32_t nn = (uint32_t)n, nt = (uint32_t)tiles, tpw = (uint32_t)tiles_per_wg;
+    static const char* const kOpName[3] = {"sum", "fsum", "max"};
+    const std::string kv = "_k" + std::to_string(8 * sizeof(K)) + "v" + std::to_string(8 * sizeof(W));
+    int rc = launch(d, intern(std::string("reduce_partial_") + kOpName[OP] + kv), [&] {
+        hipLaunchKernelGGL((adlhip::reduce_partial_kernel<K, W, OP>), dim3(wgs), dim3(adlhip::kSelNT), 0, d->stream, keys, vals, nn, nt, tpw, codec,
+                           heads, flag, agg);
+    });
+    if (rc) return rc;
+    rc = launch(d, intern(std::string("reduce_carry_") + kOpName[OP] + "_v" + std::to_string(8 * sizeof(W))), [&] {   // the head counts in place; their total is the number of runs
+        hipLaunchKernelGGL((adlhip::reduce_carry_kernel<W, OP>), dim3(1), dim3(adlhip::kSelNT), 0, d->stream, heads, (const uint32_t*)flag,
+                           (const W*)agg, carry, wgs, num_out);
+    });
+    if (rc) return rc;
+    rc = launch(d, intern(std::string("reduce_emit_") + kOpName[OP] + kv), [&] {
+        hipLaunchKernelGGL((adlhip::reduce_emit_kernel<K, W, OP>), dim3(wgs), dim3(adlhip::kSelNT), 0, d->stream, keys, vals, nn, nt, tpw, codec,
+                           (const uint32_t*)heads, (const W*)carry, unique_out, reduced_out, offsets);
+    });
+    if (rc || !counts) return rc;
+    const uint32_t cwgs = (uint32_t)((n + adlhip::kRunsCountsPerWg - 1) / adlhip::kRunsCountsPerWg);   // (at most 2^21)
+    return launch(d, "runs_counts", [&] {
+        hipLaunchKernelGGL(adlhip::runs_counts_kernel, dim3(cwgs), dim3(adlhip::kSelNT), 0, d->stream, (const uint32_t*)offsets,
+                           (const uint32_t*)num_out, nn, counts);
+    });
+}
+
+// the kernel's operator from (op, the value's kind): wrapping sum, float sum, or max on codes (min: complemented codes)
+template <typename K, typename W>
+int reduce_stage(adlhip_device* d, const K* keys, const W* vals, size_t n, int value_kind, int op, K* unique_out, W* reduced_out,
+                 uint32_t* counts, uint32_t* offsets, uint32_t* num_out, void* work)
+{
+    adlhip::RedCodec codec = {(uint32_t)value_kind, op == ADLHIP_REDUCE_MIN ? 1u : 0u};
+    if (op != ADLHIP_REDUCE_SUM)
+        return reduce_stage_op<K, W, adlhip::kRedMax>(d, keys, vals, n, codec, unique_out, reduced_out, counts, offsets, num_out, work);
+    if (value_kind == adlhip::kKeyFloat)
+        return reduce_stage_op<K, W, adlhip::kRedFloatSum>(d, keys, vals, n, codec, unique_out, reduced_out, counts, offsets, num_out, work);
+    return reduce_stage_op<K, W, adlhip::kRedSum>(d, keys, vals, n, codec, unique_out, reduced_out, counts, offsets, num_out, work);
+}
+
+// what both entry points refuse about their buffers, before anything is enqueued
+int reduce_check_buffers(const char* what, const void* keys_in, size_t keys_bytes, const void* vals_in, size_t vals_bytes, const RunsOut* outs,
+                         int num_outs, const void* num_out, const void* work)
+{
+    if (!keys_in || !vals_in || !outs[0].p || !outs[1].p || !work) return fail("null buffer passed to %s", what);
+    uintptr_t bits = reinterpret_cast<uintptr_t>(keys_in) | reinterpret_cast<uintptr_t>(vals_in) | reinterpret_cast<uintptr_t>(work);
+    for (int i = 0; i < num_outs; ++i) bits |= reinterpret_cast<uintptr_t>(outs[i].p);
+    if (bits & 15u) return fail("%s buffers must be 16-byte aligned", what);
+    for (int in = 0; in < 2; ++in) {
+        const char* in0 = static_cast<const char*>(in ? vals_in : keys_in);
+        const char* in1 = in0 + (in ? vals_bytes : keys_bytes);
+        for (int i = 0; i <= num_outs; ++i) {
+            const char* o = static_cast<const char*>(i < num_outs ? outs[i].p : num_out);
+            const size_t bytes = i < num_outs ? outs[i].bytes : 4;
+            if (o && o < in1 && in0 < o + bytes)
+                return fail("%s: %s must not overlap %s", what, i < num_outs ? outs[i].name : "the count word", in ? "d_vals_in" : "d_keys_in");
+        }
+    }
+    return ADLHIP_SUCCESS;
+}
+
+// the stable typed pairs sort from the caller's arrays into d_work (no copy: the sort's gather writes there), then the reduce stage
+template <typename K, typename W>
+int reduce_by_key_run(adlhip_device* d, const KeyTypeInfo& t, int order, const K* keys_in, const W* vals_in, size_t n, int value_kind, int op,
+                      K* unique_out, W* reduced_out, uint32_t* counts, uint32_t* offsets, uint32_t* num_out, void* work)
+{
+    const ReduceByKeyLayout L = reduce_by_key_layout(d, sizeof(K), sizeof(W), n);
+    char* w = static_cast<char*>(work);
+    K* skeys = reinterpret_cast<K*>(w + L.off_keys);
+    W* svals = reinterpret_cast<W*>(w + L.off_vals);
+    const int rc = typed_index_sort<K, W>(d, t.kind, order, keys_in, skeys, vals_in, svals, nullptr, w + L.off_swork, n);
+    if (rc) return rc;
+    return reduce_stage<K, W>(d, skeys, svals, n, value_kind, op, unique_out, reduced_out, counts, offsets, num_out, work);
+}
+
 }  // namespace
 
 // ================================================================================================
@@ -3297,6 +3439,95 @@ int adlhip_unique_typed(adlhip_device* d, int key_type, int order, const void* k
                                 first_index_out, inverse_out, num_unique_out, work);
 }
 
+// ---- reduce by key ----------------------------------------------------------------------------------
+
+int adlhip_reduce_runs_scratch_bytes(adlhip_device* d, int key_bytes, int value_type, size_t n, size_t* work_bytes)
+{
+    if (!d) return fail("null device handle");
+    if (key_bytes != 4 && key_bytes != 8) return fail("reduce runs: key_bytes must be 4 or 8, got %d", key_bytes);
+    ValueTypeInfo v;
+    if (reduce_value_info(value_type, ADLHIP_REDUCE_SUM, &v)) return ADLHIP_FAILURE;
+    if (typed_check_n(n)) return ADLHIP_FAILURE;
+    if (work_bytes) *work_bytes = reduce_layout(d, n).total;
+    return ADLHIP_SUCCESS;
+}
+
+#define ADLHIP_REDUCE_WIDTHS(kb_, vb_, CALL)          \
+    do {                                              \
+        if ((kb_) == 4 && (vb_) == 4) CALL(uint32_t, uint32_t); \
+        if ((kb_) == 4) CALL(uint32_t, uint64_t);     \
+        if ((vb_) == 4) CALL(uint64_t, uint32_t);     \
+        CALL(uint64_t, uint64_t);                     \
+    } while (0)
+
+int adlhip_reduce_runs(adlhip_device* d, int key_bytes, const void* keys_in, int value_type, int op, const void* vals_in, size_t n,
+                       void* unique_out, void* reduced_out, uint32_t* counts_out, uint32_t* offsets_out, uint32_t* num_runs_out, void* work,
+                       size_t work_bytes)
+{
+    if (bind(d)) return ADLHIP_FAILURE;
+    if (key_bytes != 4 && key_bytes != 8) return fail("reduce runs: key_bytes must be 4 or 8, got %d", key_bytes);
+    ValueTypeInfo v;
+    if (reduce_value_info(value_type, op, &v)) return ADLHIP_FAILURE;
+    if (typed_check_n(n)) return ADLHIP_FAILURE;
+    if (!num_runs_out) return fail("reduce runs: d_num_runs_out is required");
+    if (reinterpret_cast<uintptr_t>(num_runs_out) & 3u) return fail("reduce runs: d_num_runs_out must be 4-byte aligned");
+    if (n == 0) {
+        HIPCHK(hipMemsetAsync(num_runs_out, 0, 4, d->stream));
+        return ADLHIP_SUCCESS;
+    }
+    const RunsOut outs[] = {{unique_out, n * (size_t)key_bytes, "d_unique_out"}, {reduced_out, n * (size_t)v.bytes, "d_reduced_out"},
+                            {counts_out, n * 4, "d_counts_out"}, {offsets_out, (n + 1) * 4, "d_offsets_out"}};
+    if (reduce_check_buffers("reduce runs", keys_in, n * (size_t)key_bytes, vals_in, n * (size_t)v.bytes, outs, 4, num_runs_out, work))
+        return ADLHIP_FAILURE;
+    const size_t need = reduce_layout(d, n).total;
+    if (work_bytes < need) return fail("work buffer too small: %zu < %zu (adlhip_reduce_runs_scratch_bytes)", work_bytes, need);
+#define ADLHIP_RR(K_, W_) \
+    return reduce_stage<K_, W_>(d, (const K_*)keys_in, (const W_*)vals_in, n, v.kind, op, (K_*)unique_out, (W_*)reduced_out, counts_out, offsets_out, num_runs_out, work)
+    ADLHIP_REDUCE_WIDTHS(key_bytes, v.bytes, ADLHIP_RR);
+#undef ADLHIP_RR
+}
+
+int adlhip_reduce_by_key_scratch_bytes(adlhip_device* d, int key_type, int value_type, size_t n, size_t* work_bytes)
+{
+    if (!d) return fail("null device handle");
+    KeyTypeInfo t;
+    if (key_type_info(key_type, ADLHIP_ORDER_ASCENDING, &t)) return ADLHIP_FAILURE;
+    ValueTypeInfo v;
+    if (reduce_value_info(value_type, ADLHIP_REDUCE_SUM, &v)) return ADLHIP_FAILURE;
+    if (typed_check_n(n)) return ADLHIP_FAILURE;
+    if (work_bytes) *work_bytes = reduce_by_key_layout(d, (size_t)t.bytes, (size_t)v.bytes, n).total;
+    return ADLHIP_SUCCESS;
+}
+
+int adlhip_reduce_by_key_typed(adlhip_device* d, int key_type, int order, const void* keys_in, int value_type, int op, const void* vals_in,
+                               size_t n, void* unique_out, void* reduced_out, uint32_t* counts_out, uint32_t* offsets_out,
+                               uint32_t* num_unique_out, void* work, size_t work_bytes)
+{
+    if (bind(d)) return ADLHIP_FAILURE;
+    KeyTypeInfo t;
+    if (key_type_info(key_type, order, &t)) return ADLHIP_FAILURE;
+    ValueTypeInfo v;
+    if (reduce_value_info(value_type, op, &v)) return ADLHIP_FAILURE;
+    if (typed_check_n(n)) return ADLHIP_FAILURE;
+    if (!num_unique_out) return fail("reduce by key: d_num_unique_out is required");
+    if (reinterpret_cast<uintptr_t>(num_unique_out) & 3u) return fail("reduce by key: d_num_unique_out must be 4-byte aligned");
+    if (n == 0) {
+        HIPCHK(hipMemsetAsync(num_unique_out, 0, 4, d->stream));
+        return ADLHIP_SUCCESS;
+    }
+    const RunsOut outs[] = {{unique_out, n * (size_t)t.bytes, "d_unique_out"}, {reduced_out, n * (size_t)v.bytes, "d_reduced_out"},
+                            {counts_out, n * 4, "d_counts_out"}, {offsets_out, (n + 1) * 4, "d_offsets_out"}};
+    if (reduce_check_buffers("reduce by key", keys_in, n * (size_t)t.bytes, vals_in, n * (size_t)v.bytes, outs, 4, num_unique_out, work))
+        return ADLHIP_FAILURE;
+    const size_t need = reduce_by_key_layout(d, (size_t)t.bytes, (size_t)v.bytes, n).total;
+    if (work_bytes < need) return fail("work buffer too small: %zu < %zu (adlhip_reduce_by_key_scratch_bytes)", work_bytes, need);
+#define ADLHIP_RBK(K_, W_) \
+    return reduce_by_key_run<K_, W_>(d, t, order, (const K_*)keys_in, (const W_*)vals_in, n, v.kind, op, (K_*)unique_out, (W_*)reduced_out, counts_out, offsets_out, num_unique_out, work)
+    ADLHIP_REDUCE_WIDTHS(t.bytes, v.bytes, ADLHIP_RBK);
+#undef ADLHIP_RBK
+}
+#undef ADLHIP_REDUCE_WIDTHS
+
 int adlhip_segment_sort(adlhip_device* d, int elem_kind, void* data, const uint32_t* seg_start, size_t num_segments,
                         size_t max_segment, int low_bits)
 {
@@ -3460,6 +3691,9 @@ int adlhip_set_param(adlhip_device* d, const char* name, int value)
     } else if (!strcmp(name, "debug.unique_grid")) {
         if (value < 0) return fail("debug.unique_grid must be >= 0");
         d->unique_grid = value;
+    } else if (!strcmp(name, "debug.reduce_grid")) {
+        if (value < 0) return fail("debug.reduce_grid must be >= 0");
+        d->reduce_grid = value;
     } else if (!strcmp(name, "debug.finish16_alg")) {
         if (value != -1 && value != 1 && value != 2) return fail("debug.finish16_alg must be -1 (the adopted variant), 1 (the round-4 kernel) or 2");
         d->finish16_alg = value;
@@ -3508,6 +3742,7 @@ int adlhip_get_param(adlhip_device* d, const char* name, int* value)
     else if (!strcmp(name, "debug.topk_rows_grid")) *value = d->topk_rows_grid;
     else if (!strcmp(name, "unique.algo")) *value = d->unique_algo;
     else if (!strcmp(name, "debug.unique_grid")) *value = d->unique_grid;
+    else if (!strcmp(name, "debug.reduce_grid")) *value = d->reduce_grid;
     else if (!strcmp(name, "partition.lookback")) *value = d->partition_lookback;
     else if (!strcmp(name, "sort.net_lookback")) *value = d->net_lookback;
     else if (!strcmp(name, "debug.finish16_alg")) *value = d->finish16_alg;

@@ -12,6 +12,8 @@
     p.topkRows(device, keys, rows, cols, k)                # -> Buffer(uint32): rows x k columns, top-k of every row
     p.unique(device, keys, n, counts=True, inverse=True)   # -> UniqueResult: distinct keys in sorted order, counts, inverse, ...
     p.runLengthEncode(device, keys, n, counts=True)        # -> UniqueResult: the runs of keys that are already grouped
+    p.reduceByKey(device, keys, values, n, op="sum")       # -> ReduceResult: distinct keys in sorted order, sum / min / max of their values
+    p.reduceRuns(device, keys, values, n, op="sum")        # -> ReduceResult: the same per run of keys that are already grouped
 
 Like the reference object it owns lazily grown device scratch (m_u32WorkBuffer[0] = ping-pong data
 buffer, m_u32WorkBuffer[1] = histogram table; Pprims.h:44-45, Pprims.cpp:226-232, :332-337) and must be
@@ -39,6 +41,13 @@ KEY_TYPES = {np.dtype(np.uint32): 0, np.dtype(np.int32): 1, np.dtype(np.float32)
 # What unique / runLengthEncode return: device Buffers (None where not asked).  `count` is a one-element uint32 Buffer that holds R, the
 # number of runs; unique, counts and firstIndex have n elements of which the first R are written, offsets n + 1 (R + 1 written), inverse n.
 UniqueResult = collections.namedtuple("UniqueResult", "unique counts offsets firstIndex inverse count")
+
+# ADLHIP_REDUCE_* by name (include/adlhip.h, "reduce values by key")
+REDUCE_OPS = {"sum": 0, "min": 1, "max": 2}
+
+# What reduceByKey / reduceRuns return: device Buffers (None where not asked).  `count` is a one-element uint32 Buffer that holds R;
+# unique, reduced and counts have n elements of which the first R are written, offsets n + 1 (R + 1 written).
+ReduceResult = collections.namedtuple("ReduceResult", "unique reduced counts offsets count")
 
 
 class Pprims:
@@ -372,6 +381,80 @@ class Pprims:
                 b.release()
             raise
         return UniqueResult(uniqueOut, c, o, None, None, countOut)
+
+    # -- reduce values by key (no reference counterpart; include/adlhip.h adlhip_reduce_by_key_typed)
+    def _reduce(self, what, device, by_key, keys, values, n, op, descending, counts, offsets, uniqueOut, reducedOut, countOut):
+        if device is None:
+            raise AdlHipError("%s needs a device" % what)
+        if op not in REDUCE_OPS:
+            raise AdlHipError("%s: op must be 'sum', 'min' or 'max', got %r" % (what, op))
+        if by_key:
+            kt = self._key_type(keys, what)
+        elif np.dtype(keys.dtype).itemsize not in (4, 8):
+            raise AdlHipError("%s: unsupported key type %s (4 or 8 bytes)" % (what, keys.dtype))
+        vt = KEY_TYPES.get(np.dtype(values.dtype))
+        if vt is None:
+            raise AdlHipError("%s: unsupported value type %s (uint32, int32, float32, uint64, int64, float64)" % (what, values.dtype))
+        n = int(n)
+        if n < 0 or keys.getSize() < n or values.getSize() < n:
+            raise AdlHipError("%s: n = %d outside [0, %d]" % (what, n, min(keys.getSize(), values.getSize())))
+        if uniqueOut is not None and (np.dtype(uniqueOut.dtype) != np.dtype(keys.dtype) or uniqueOut.getSize() < n):
+            raise AdlHipError("%s: uniqueOut must hold n elements of %s" % (what, keys.dtype))
+        if reducedOut is not None and (np.dtype(reducedOut.dtype) != np.dtype(values.dtype) or reducedOut.getSize() < n):
+            raise AdlHipError("%s: reducedOut must hold n elements of %s" % (what, values.dtype))
+        if countOut is not None and (np.dtype(countOut.dtype) != np.uint32 or countOut.getSize() < 1):
+            raise AdlHipError("%s: countOut must hold one uint32 element" % what)
+        (c, o), own = self._runs_outputs(what, device, n, [("counts", counts, n), ("offsets", offsets, n + 1)])
+        try:
+            lib = _lib.load()
+            wb = ctypes.c_size_t()
+            if by_key:
+                check(lib.adlhip_reduce_by_key_scratch_bytes(device._h, kt, vt, n, ctypes.byref(wb)), "adlhip_reduce_by_key_scratch_bytes")
+            else:
+                check(lib.adlhip_reduce_runs_scratch_bytes(device._h, np.dtype(keys.dtype).itemsize, vt, n, ctypes.byref(wb)),
+                      "adlhip_reduce_runs_scratch_bytes")
+            self._scratch(device, 0, wb.value)
+            if uniqueOut is None:
+                uniqueOut = Buffer(device, n, keys.dtype)
+                own.append(uniqueOut)
+            if reducedOut is None:
+                reducedOut = Buffer(device, n, values.dtype)
+                own.append(reducedOut)
+            if countOut is None:
+                countOut = Buffer(device, 1, np.uint32)
+                own.append(countOut)
+
+            def p(b):
+                return b.ptr() if b is not None else None
+            if by_key:
+                check(lib.adlhip_reduce_by_key_typed(device._h, kt, 1 if descending else 0, keys.ptr(), vt, REDUCE_OPS[op], values.ptr(), n,
+                                                     uniqueOut.ptr(), reducedOut.ptr(), p(c), p(o), countOut.ptr(), self.m_work.ptr(),
+                                                     self.m_work.getSize()), what)
+            else:
+                check(lib.adlhip_reduce_runs(device._h, np.dtype(keys.dtype).itemsize, keys.ptr(), vt, REDUCE_OPS[op], values.ptr(), n,
+                                             uniqueOut.ptr(), reducedOut.ptr(), p(c), p(o), countOut.ptr(), self.m_work.ptr(),
+                                             self.m_work.getSize()), what)
+        except AdlHipError:
+            for b in own:
+                b.release()
+            raise
+        return ReduceResult(uniqueOut, reducedOut, c, o, countOut)
+
+    def reduceByKey(self, device, keys, values, n, op="sum", descending=False, counts=False, offsets=False, uniqueOut=None,
+                    reducedOut=None, countOut=None):
+        """op ("sum", "min", "max") over the values of every distinct key among the first n of `keys` -> ReduceResult.  The keys appear
+        in the order of sortKeys(descending) and are equal when their bits are, as in unique(); reduced[r] belongs to unique[r].
+        Values: uint32 / int32 / float32 / uint64 / int64 / float64, whatever the keys' width.  Integer sums wrap; float sums are IEEE
+        adds in an unspecified but reproducible association; min / max follow the order of the typed sorts (floats: totalOrder, so
+        -0 < +0 and NaNs are ordered, not propagated) whatever `descending` says.  counts / offsets / uniqueOut / countOut as in
+        unique(), reducedOut (the values' dtype, n elements) likewise.  `keys` and `values` are left intact.  Enqueues and returns
+        like unique(); read result.count (toHost) to learn R."""
+        return self._reduce("reduceByKey", device, True, keys, values, n, op, descending, counts, offsets, uniqueOut, reducedOut, countOut)
+
+    def reduceRuns(self, device, keys, values, n, op="sum", counts=False, offsets=False, uniqueOut=None, reducedOut=None, countOut=None):
+        """reduceByKey for keys that are already grouped (any element type of 4 or 8 bytes): one result per run of adjacent keys with
+        identical bits, the runs of runLengthEncode() -> ReduceResult."""
+        return self._reduce("reduceRuns", device, False, keys, values, n, op, False, counts, offsets, uniqueOut, reducedOut, countOut)
 
     def copy(self, device, dst, src, n):
         """Pprims::copy (Pprims.cpp:31-67, commented out in the reference): first n elements of src -> dst."""

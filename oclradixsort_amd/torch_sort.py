@@ -8,6 +8,8 @@ back-end on torch's own stream.
     values, indices = s.topk_rows(m, 10)    # m: 2-D or more; the same along the last dimension of every row
     u, inverse, counts = s.unique(t, return_inverse=True, return_counts=True)   # torch.unique(t) on any number of dimensions
     u, counts = s.unique_consecutive(t, return_counts=True)                      # torch.unique_consecutive(t), 1-D
+    u, sums = s.reduce_by_key(keys, values, op="sum")                            # per distinct key: sum / min / max of its values
+    u, sums = s.reduce_consecutive(keys, values, op="sum")                       # the same per run of adjacent equal keys
     s.close()
 
 Always out of place and always stable.  The ONE difference from `torch.sort(t, stable=True)`: floats are ordered by
@@ -223,6 +225,49 @@ class TorchSorter:
         if return_counts:
             return uniq[:r].clone(), cnt32[:r].to(torch.int64) & 0xffffffff
         return uniq[:r].clone()
+
+    def _reduce(self, what, by_key, keys, values, op, descending, return_counts):
+        if op not in ("sum", "min", "max"):
+            raise ValueError("TorchSorter.%s: op must be 'sum', 'min' or 'max', got %r" % (what, op))
+        k = self._flat_input(keys, what, True)
+        v = self._flat_input(values, what, True)
+        n = k.numel()
+        if v.numel() != n:
+            raise ValueError("TorchSorter.%s: %d keys but %d values" % (what, n, v.numel()))
+        if n == 0:
+            out = (torch.empty(0, dtype=keys.dtype, device=keys.device), torch.empty(0, dtype=values.dtype, device=keys.device))
+            return out + (torch.empty(0, dtype=torch.int64, device=keys.device),) if return_counts else out
+        kdt, vdt = _NP_DTYPE[keys.dtype], _NP_DTYPE[values.dtype]
+        uniq = torch.empty(n, dtype=keys.dtype, device=keys.device)
+        red = torch.empty(n, dtype=values.dtype, device=keys.device)
+        count = torch.empty(1, dtype=torch.int32, device=keys.device)
+        cnt32 = torch.empty(n, dtype=torch.int32, device=keys.device) if return_counts else None   # uint32 in an int32 tensor
+        args = dict(op=op, counts=self._wrap(cnt32, np.uint32) if return_counts else False, uniqueOut=self._wrap(uniq, kdt),
+                    reducedOut=self._wrap(red, vdt), countOut=self._wrap(count, np.uint32))
+        if by_key:
+            self.pprims.reduceByKey(self.device, self._wrap(k, kdt), self._wrap(v, vdt), n, descending=bool(descending), **args)
+        else:
+            self.pprims.reduceRuns(self.device, self._wrap(k, kdt), self._wrap(v, vdt), n, **args)
+        self.device.checkFault()
+        r = int(count.item()) & 0xffffffff   # the one host read
+        out = (uniq[:r].clone(), red[:r].clone())
+        return out + (cnt32[:r].to(torch.int64) & 0xffffffff,) if return_counts else out
+
+    def reduce_by_key(self, keys, values, op="sum", descending=False, return_counts=False):
+        """(unique_keys, reduced[, counts]): the distinct keys in sorted order (descending: largest first) and `op` ("sum", "min",
+        "max") over the values of each -- torch.unique(keys, return_inverse=True) followed by index_add_ / scatter_reduce_ -- and,
+        where asked, how often each key occurs (int64).  keys and values: 1-D tensors of the same length on the sorter's device,
+        int32 / int64 / float32 / float64 each, in any combination; reduced has the values' dtype.  Keys are equal when their bits
+        are (as in unique).  Integer sums wrap; float sums are IEEE adds in an unspecified association, the same bits on every call
+        (index_add_'s atomics are not).  min / max are taken in IEEE totalOrder, -NaN < -inf < ... < -0 < +0 < ... < +inf < +NaN:
+        a NaN is the minimum or the maximum by its sign, NOT propagated as torch's amin / amax do, and -0 is below +0; without NaN
+        they give amin / amax.  Like unique this makes ONE host read, of the number of keys: the call waits for the stream."""
+        return self._reduce("reduce_by_key", True, keys, values, op, descending, return_counts)
+
+    def reduce_consecutive(self, keys, values, op="sum", return_counts=False):
+        """reduce_by_key for keys that are already grouped: one (key, reduced[, count]) per run of adjacent keys with identical bits,
+        in input order -- the runs of unique_consecutive.  The same types, operators (min / max in totalOrder) and host read."""
+        return self._reduce("reduce_consecutive", False, keys, values, op, False, return_counts)
 
     def sort(self, t, descending=False):
         """(values, indices) like torch.sort(t, descending=descending, stable=True); indices are int64."""

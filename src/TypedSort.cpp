@@ -3,7 +3,8 @@
 // adlhip_argsort_typed; a TYPE_HOST device sorts on the CPU with std::stable_sort on the same total order, as the reference's
 // host branches do for u32 keys (Pprims.cpp:202-212, :306-316).  Pprims::topK: adlhip_topk_typed, or a partial sort on (ordinal,
 // position) on the host.  Pprims::topKRows: adlhip_topk_rows_typed, or the same partial sort per row.  Pprims::unique:
-// adlhip_unique_typed (it waits for the count), or the runs of the host argsort.
+// adlhip_unique_typed (it waits for the count), or the runs of the host argsort.  Pprims::reduceByKey: adlhip_reduce_by_key_typed (it
+// waits for the count), or a loop over the runs of the host argsort.
 #include <Tahoe/ParallelPrimitives/Pprims.h>
 
 #include <algorithm>
@@ -268,6 +269,101 @@ int Pprims::uniqueTyped(const adl::Device* device, const adl::Buffer<T>& keys, a
     memcpy(&runs, word, 4);
     return (int)runs;
 }
+
+namespace {
+
+// acc = op(acc, v) on the host, with the device's meaning: integer sums wrap (computed on the unsigned bits), float sums are IEEE adds,
+// min / max compare ordinals and keep the winner's bits
+template <typename V>
+inline void hostReduceStep(V& acc, const V& v, int op)
+{
+    typedef typename KeyTraits<V>::Bits B;
+    if (op == ADLHIP_REDUCE_SUM) {
+        if (KeyTraits<V>::FLOAT) {
+            acc = (V)(acc + v);
+        } else {
+            B a, b;
+            memcpy(&a, &acc, sizeof(B));
+            memcpy(&b, &v, sizeof(B));
+            a = (B)(a + b);
+            memcpy(&acc, &a, sizeof(B));
+        }
+        return;
+    }
+    const B oa = ordinal(acc, false), ov = ordinal(v, false);
+    if (op == ADLHIP_REDUCE_MIN ? ov < oa : ov > oa) memcpy(&acc, &v, sizeof(V));
+}
+
+}  // namespace
+
+template <typename K, typename V>
+int Pprims::reduceByKey(const adl::Device* device, const adl::Buffer<K>& keys, const adl::Buffer<V>& values, adl::Buffer<K>& uniqueOut,
+                        adl::Buffer<V>& reducedOut, int n, int op, bool descending)
+{
+    ADLASSERT(n >= 0);
+    ADLASSERT(op == ADLHIP_REDUCE_SUM || op == ADLHIP_REDUCE_MIN || op == ADLHIP_REDUCE_MAX);
+    if (n <= 0) return 0;
+    ADLASSERT(device != 0);
+    ADLASSERT((adl::u64)n <= keys.getSize() && (adl::u64)n <= values.getSize() && (adl::u64)n <= uniqueOut.getSize() &&
+              (adl::u64)n <= reducedOut.getSize());
+    if (!onDevice(device)) {
+        ADLASSERT(device->getType() == adl::TYPE_HOST);   // a HIP device never falls back to the CPU
+        if (device->getType() != adl::TYPE_HOST) return 0;
+        K* host = keys.getHostPtr(n);
+        V* vals = values.getHostPtr(n);
+        K* uout = uniqueOut.getHostPtr(n);
+        V* rout = reducedOut.getHostPtr(n);
+        adl::DeviceUtils::waitForCompletion(device);
+        std::vector<Ranked<typename KeyTraits<K>::Bits> > order;
+        hostArgsort(host, n, descending, order);
+        int runs = 0;
+        for (int j = 0; j < n; ++j) {   // equal ordinals are equal bits: the ordinal is a bijection
+            if (j == 0 || order[j].ord != order[j - 1].ord) {
+                uout[runs] = host[order[j].idx];
+                memcpy(&rout[runs], &vals[order[j].idx], sizeof(V));   // a run of one element keeps its bits
+                ++runs;
+            } else {
+                hostReduceStep(rout[runs - 1], vals[order[j].idx], op);
+            }
+        }
+        keys.returnHostPtr(host);
+        values.returnHostPtr(vals);
+        uniqueOut.returnHostPtr(uout);
+        reducedOut.returnHostPtr(rout);
+        adl::DeviceUtils::waitForCompletion(device);
+        return runs;
+    }
+    size_t wb = 0;
+    const int rcq = adlhip_reduce_by_key_scratch_bytes(device->hip(), KeyTraits<K>::TYPE, KeyTraits<V>::TYPE, (size_t)n, &wb);
+    ADLASSERT(rcq == ADLHIP_SUCCESS);
+    reserve(device, 16, wb);   // m_tmp holds the count word
+    const int rc = adlhip_reduce_by_key_typed(device->hip(), KeyTraits<K>::TYPE, descending ? ADLHIP_ORDER_DESCENDING : ADLHIP_ORDER_ASCENDING,
+                                              keys.m_ptr, KeyTraits<V>::TYPE, op, values.m_ptr, (size_t)n, uniqueOut.m_ptr, reducedOut.m_ptr, 0, 0,
+                                              (uint32_t*)m_tmp->m_ptr, m_work->m_ptr, (size_t)m_work->getSize());
+    if (rc != ADLHIP_SUCCESS) TH_LOG_ERROR("Pprims::reduceByKey: %s\n", adlhip_last_error());
+    ADLASSERT(rc == ADLHIP_SUCCESS);
+    if (rc != ADLHIP_SUCCESS) return 0;
+    unsigned char word[4] = {0, 0, 0, 0};
+    m_tmp->read(word, 4);
+    adl::DeviceUtils::waitForCompletion(device);
+    u32 runs = 0;
+    memcpy(&runs, word, 4);
+    return (int)runs;
+}
+
+#define TAHOE_REDUCE(K, V)                                                                                                          \
+    template int Pprims::reduceByKey<K, V>(const adl::Device*, const adl::Buffer<K>&, const adl::Buffer<V>&, adl::Buffer<K>&,       \
+                                           adl::Buffer<V>&, int, int, bool);
+#define TAHOE_REDUCE_KEY(K)                                                                                                         \
+    TAHOE_REDUCE(K, int) TAHOE_REDUCE(K, float) TAHOE_REDUCE(K, long long) TAHOE_REDUCE(K, double) TAHOE_REDUCE(K, u32) TAHOE_REDUCE(K, u64)
+TAHOE_REDUCE_KEY(int)
+TAHOE_REDUCE_KEY(float)
+TAHOE_REDUCE_KEY(long long)
+TAHOE_REDUCE_KEY(double)
+TAHOE_REDUCE_KEY(u32)
+TAHOE_REDUCE_KEY(u64)
+#undef TAHOE_REDUCE_KEY
+#undef TAHOE_REDUCE
 
 #define TAHOE_TYPED(T)                                                                                                              \
     void Pprims::sortKeys(const adl::Device* device, const adl::Buffer<T>& inout, int n, bool descending)                         \
