@@ -2,21 +2,15 @@
 // Replaces Adl/CL/AdlCL.inl (device, buffers, copies, map/unmap), Adl/CL/AdlKernelUtilsCL.inl
 // (kernel launch + per-launch profiling) and the GPU branches of Tahoe/ParallelPrimitives/Pprims.cpp
 // (pass drivers).  gfx950 only; kernels are compiled ahead of time into this shared object.
-#include "../../include/adlhip.h"
-
-#include <hip/hip_runtime.h>
+#include "adlhip_internal.hpp"
 
 #include <algorithm>
 #include <cmath>
 #include <cstdarg>
-#include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <map>
 #include <mutex>
 #include <utility>
-#include <string>
-#include <vector>
 
 #include "radix_kernels.hpp"
 #include "onesweep_kernels.hpp"
@@ -24,30 +18,27 @@
 #include "persist_kernels.hpp"
 #include "finish16_kernels.hpp"
 #include "soa_wide_kernels.hpp"
-#include "typed_kernels.hpp"
-#include "select_kernels.hpp"
-#include "toprows_kernels.hpp"
-#include "unique_kernels.hpp"
-#include "reduce_kernels.hpp"
 
 // The large sort's kernels and the per-digit passes' are instantiated in kernels_finish.hip / kernels_passes.hip / kernels_perdigit.hip (translation units of
-// their own, compiled beside this one); here they are only declared.  -DADLHIP_SINGLE_TU builds everything in this file (what tools/gen_large_kernels.py reads the list from).
+// their own, compiled beside this one); here they are only declared.  The primitives on top of the sorts are a unit of their own too (primitives.hip).
+// -DADLHIP_SINGLE_TU builds everything in this file, primitives.hip included at its end (what tools/gen_large_kernels.py reads the list from).
 #ifndef ADLHIP_SINGLE_TU
 #define X(...) extern template __global__ __VA_ARGS__;
 #include "finish_kernels.inc"
 #include "wavefinish_kernels.inc"
 #include "passes_kernels.inc"
 #include "perdigit_kernels.inc"
-#include "select_kernels.inc"
-#include "toprows_kernels.inc"
-#include "unique_kernels.inc"
-#include "reduce_kernels.inc"
 #undef X
 #endif
 
-namespace {
+using namespace adlhip_internal;
 
+namespace {
 thread_local char g_err[512] = "";
+constexpr size_t kPinnedPoolMax = size_t(512) << 20;   // pinned staging kept for re-use per device handle
+}  // namespace
+
+namespace adlhip_internal {
 
 int fail(const char* fmt, ...)
 {
@@ -58,103 +49,6 @@ int fail(const char* fmt, ...)
     if (getenv("ADLHIP_VERBOSE")) fprintf(stderr, "[adlhip] error: %s\n", g_err);
     return ADLHIP_FAILURE;
 }
-
-#define HIPCHK(expr)                                                                           \
-    do {                                                                                       \
-        hipError_t _e = (expr);                                                                \
-        if (_e != hipSuccess)                                                                  \
-            return fail("%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
-    } while (0)
-
-struct ProfEntry {
-    uint64_t launches = 0;
-    double total_ms = 0.0;
-};
-struct PendingProf {
-    const char* name;
-    hipEvent_t e0, e1;
-};
-struct Staging {
-    void* hptr;
-    size_t bytes;      // bytes mapped
-    hipEvent_t done;   // null while mapped; set at unmap
-    size_t capacity;   // bytes of pinned memory behind hptr (>= bytes when it came from the pool)
-};
-struct PinnedBlock {
-    void* hptr;
-    size_t capacity;
-};
-constexpr size_t kPinnedPoolMax = size_t(512) << 20;   // pinned staging kept for re-use per device handle
-
-}  // namespace
-
-struct adlhip_event {
-    hipEvent_t ev;
-};
-
-struct adlhip_device {
-    int idx = 0;
-    hipStream_t stream = nullptr;
-    bool own_stream = true;
-    hipDeviceProp_t prop;
-    uint64_t used_bytes = 0;
-    // knobs
-    int sort_algo = -1;       // -1 automatic by size, 0 onesweep, 1 three-kernel pass
-    int digit_bits = 8;       // 8 or 4
-    int profile = 0;
-    int tile_variant = -1;    // index into kVariants; -1 = best known per element size
-    int rank_mode = 1;        // 1 = lane-ordered DS atomic ranking (needs lds_ordered), 0 = ballot match
-    int lds_ordered = 0;      // result of the device self-test at creation
-    int resident_wgs_device = 0;
-    int resident_wgs = 0;     // workgroups of <= 80 KiB LDS / 512 threads that are certainly resident at once (2 per CU); the paths
-                              // whose kernels hold a grid-wide barrier over 256 workgroups are taken only when this is >= 256
-    int mid_path = 1;         // 16 Ki < n <= 2 Mi: MSD pass + LDS finish (three launches) instead of per-digit passes
-    int mid_skip = 0;         // eligible sorts still to be sent down the per-digit passes after a skewed input (see mid_eligible)
-    int mid2_skip = 0;        // keys-only sorts still to take the three-launch form after a slab overflow (see mid_sort_keys)
-    int mid_backoff = 32, mid2_backoff = 64;
-    int bin_finish = 1;       // "sort.binfinish": the large keys-only sort finishes its segments with one counting pass + compares
-                              // (1: u64 keys, 2: u32 keys too, 0: the wave-per-segment LSD finish)
-    int persist = 1;          // "sort.persist": the cursor passes of the large sort as persistent, prefetching kernels + the 16-bit finish
-    int finish16_alg = -1;    // "debug.finish16_alg": the variant of the 16-bit finish (finish16_kernels.hpp ALG); -1 = the adopted one (2:
-                              // plain LDS gathers), 1 = the round-4 kernel (gathers through a volatile pointer); A/B runs and tests
-    int msd2_path = 1;        // "sort.msd2": the large sort (msd2_sort for keys, msd2s_sort for pairs); 2 = forced (tests)
-    int net_lookback = 1;                   // "sort.net_lookback": the large sort's safety net runs look-back passes (0: count-scan-scatter passes)
-    int partition_lookback = 1;             // "partition.lookback": the MSB partition as one look-back pass where it pays (0: always three kernels)
-    int dict_path = 1;                      // "sort.dict": the large sort's safety net first tries the counting sort for keys that take at most
-                                            // 256 values (dict_kernels.hpp); 0 = off
-    int topk_algo = -1;                     // "topk.algo": -1 selection up to kTopkSelectMaxFraction of n, the full argsort above; 0 / 1 force
-                                            // the argsort / the selection
-    int topk_rows_algo = -1;                // "topk.rows_algo": -1 the row kernel while k <= kRowMaxK and cols <= kTopkRowsMaxCols, the per-row
-                                            // loop above; 0 / 1 force the loop / the row kernel
-    int topk_rows_grid = 0;                 // "debug.topk_rows_grid": workgroups of the row kernel at most (0: kTopkRowsWgsPerCu per CU)
-    int unique_algo = -1;                   // "unique.algo": -1 the keys path unless first_index or inverse is asked, 1 always the index path
-    int unique_grid = 0;                    // "debug.unique_grid": workgroups of the run stage at most (0: kUniqueWgsPerCu per CU)
-    int reduce_grid = 0;                    // "debug.reduce_grid": workgroups of the reduce stage at most (0: kReduceWgsPerCu per CU)
-    adlhip::DictBlock* d_dict = nullptr;    // its dictionary and counters (handle-owned; rebuilt by every net that uses them)
-    uint32_t* d_msd2 = nullptr;   // the large sort's handle-owned words, allocated with the handle: cursors of pass 1 (256, one
-                                  // 128-byte line each) and pass 2 (65536), overflow flag, done counter, the safety net's barrier
-                                  // counter, the four sample words, ...; what each holds between sorts: kIdleTable
-    // profiling
-    std::vector<PendingProf> pending;
-    std::vector<hipEvent_t> event_pool;
-    std::map<std::string, ProfEntry> prof;
-    std::vector<std::string> prof_order;
-    // map/unmap staging; released staging blocks are pooled: pinning memory costs ~1 ms per 4 MiB, and the
-    // reference's test maps every buffer two or three times (UnitTest/main.cpp:118-139)
-    std::vector<Staging> staging;
-    std::vector<PinnedBlock> pinned_pool;
-    size_t pinned_pool_bytes = 0;
-    // device-side fault words ([0] live, [1] sticky: onesweep_kernels.hpp raise_fault), checked at sync and by
-    // adlhip_fault_check; [8] is the self-test's result slot
-    uint32_t* d_fault = nullptr;
-    uint32_t* h_fault = nullptr;   // pinned: [0..1] filled by adlhip_sync, [4] by the last adlhip_fault_check snapshot
-    hipEvent_t fault_snap = nullptr;   // recorded behind the last snapshot copy; null = none pending
-    uint32_t* d_mid_hist = nullptr;    // [16][4][256] slice histograms of the mid-size sort + 512 words of bucket cursors / flags
-                                       // of its keys-only form (hybrid_kernels.hpp SegSlab): zero between sorts, but for the
-                                       // barrier counter its first kernel clears (kIdleTable)
-};
-
-namespace {
 
 int bind(adlhip_device* d)
 {
@@ -175,38 +69,26 @@ hipEvent_t take_event(adlhip_device* d)
     return e;
 }
 
-// Launch wrapper: optional hipEvent bracket per launch ("profile" = 1), error check after.
-inline int trace_level()
+int trace_level()
 {
     static const int level = getenv("ADLHIP_TRACE") ? atoi(getenv("ADLHIP_TRACE")) : 0;
     return level;
 }
 
-template <typename F>
-int launch(adlhip_device* d, const char* name, F&& f)
+// Interned kernel names (the profiler keeps the pointer until the events are folded).
+const char* intern(const std::string& s)
 {
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (d->profile) {
-        e0 = take_event(d);
-        e1 = take_event(d);
-        if (!e0 || !e1) return fail("hipEventCreate failed");
-        HIPCHK(hipEventRecord(e0, d->stream));
-    }
-    // ADLHIP_TRACE=1 (debugging aid): name every launch on stderr and wait for it, so that the last line before a GPU fault
-    // names the kernel that raised it
-    // (ADLHIP_TRACE=2: names only, nothing waits)
-    static const int trace = trace_level();
-    if (trace) fprintf(stderr, "[adlhip] launch %s\n", name), fflush(stderr);
-    f();
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail("launch of %s failed: %s", name, hipGetErrorString(e));
-    if (trace == 1 && (e = hipStreamSynchronize(d->stream)) != hipSuccess) return fail("%s: %s", name, hipGetErrorString(e));
-    if (d->profile) {
-        HIPCHK(hipEventRecord(e1, d->stream));
-        d->pending.push_back({name, e0, e1});
-    }
-    return ADLHIP_SUCCESS;
+    static std::mutex mu;
+    static std::map<std::string, std::string*> pool;
+    std::lock_guard<std::mutex> lock(mu);
+    auto it = pool.find(s);
+    if (it == pool.end()) it = pool.emplace(s, new std::string(s)).first;
+    return it->second->c_str();
 }
+
+}  // namespace adlhip_internal
+
+namespace {
 
 int fold_profile(adlhip_device* d)
 {
@@ -248,8 +130,6 @@ void reap_staging(adlhip_device* d, bool all_done)
         }
     }
 }
-
-inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
 // ---- sort configuration -------------------------------------------------------------------
 
@@ -323,8 +203,6 @@ uint32_t current_tile(const adlhip_device* d, size_t elem_bytes, size_t n)
     return (uint32_t)(v.nt * v.k);
 }
 
-constexpr size_t kMaxElems = 0xFFF00000ull;   // 32-bit element indices inside the kernels
-
 // work buffer layout (three-kernel pass): [table 256 x n_wgs u32][totals 256 u32]
 size_t table_bytes(const adlhip_device* d, size_t n, uint32_t tile)
 {
@@ -349,17 +227,6 @@ int ensure_lds(KernelT kernel, size_t bytes)
     HIPCHK(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
     have = bytes;
     return ADLHIP_SUCCESS;
-}
-
-// Interned kernel names (the profiler keeps the pointer until the events are folded).
-const char* intern(const std::string& s)
-{
-    static std::mutex mu;
-    static std::map<std::string, std::string*> pool;
-    std::lock_guard<std::mutex> lock(mu);
-    auto it = pool.find(s);
-    if (it == pool.end()) it = pool.emplace(s, new std::string(s)).first;
-    return it->second->c_str();
 }
 
 // ---- what a sort ping-pongs between ------------------------------------------------------------------
@@ -1776,7 +1643,8 @@ size_t sort_work_bytes_at(const adlhip_device* d, int elem_kind, size_t n, int s
 // input selects a smaller tile, which needs more status rows; from 16 Mi keys the second slab of whole u32 keys moves into the
 // partner array), so a caller that sizes its scratch once for its largest batch must get the maximum over the sizes at which
 // such a choice changes.  Changing "sort.tile", "sort.digit_bits" or "sort.algo" afterwards can raise the requirement.
-size_t sort_work_bytes(const adlhip_device* d, int elem_kind, size_t n, int sort_bits, int level)
+}  // namespace
+size_t adlhip_internal::sort_work_bytes(const adlhip_device* d, int elem_kind, size_t n, int sort_bits, int level)
 {
     const size_t esz = (elem_kind == ADLHIP_ELEM_U32) ? 4 : 8;
     size_t need = sort_work_bytes_at(d, elem_kind, n, sort_bits, level);
@@ -1784,6 +1652,7 @@ size_t sort_work_bytes(const adlhip_device* d, int elem_kind, size_t n, int sort
         if (edge < n) need = std::max(need, sort_work_bytes_at(d, elem_kind, edge, sort_bits, level));
     return need;
 }
+namespace {
 
 // choose the path (shared by the AoS and SoA entry points)
 template <typename Buf>
@@ -1894,6 +1763,19 @@ int sort_entry(adlhip_device* d, int elem_kind, E* data, E* tmp, void* work, siz
     return run_sort<AosBuf<E>>(d, AosBuf<E>{data}, AosBuf<E>{tmp}, work, work_bytes, n, plan);
 }
 
+}  // namespace
+int adlhip_internal::sort_elements(adlhip_device* d, int elem_kind, void* data, void* tmp, void* work, size_t work_bytes, size_t n, int sort_bits)
+{
+    if (elem_kind == ADLHIP_ELEM_U32) return sort_entry<uint32_t>(d, elem_kind, (uint32_t*)data, (uint32_t*)tmp, work, work_bytes, n, sort_bits, 32);
+    return sort_entry<uint64_t>(d, elem_kind, (uint64_t*)data, (uint64_t*)tmp, work, work_bytes, n, sort_bits, elem_kind == ADLHIP_ELEM_U64 ? 64 : 32);
+}
+
+int adlhip_internal::launch_scan_single(adlhip_device* d, const char* name, const uint32_t* src, uint32_t* dst, size_t n, uint32_t* d_total)
+{
+    return launch(d, name, [&] { hipLaunchKernelGGL(adlhip::scan_single_kernel, dim3(1), dim3(adlhip::kScanNT), 0, d->stream, src, dst, n, d_total); });
+}
+namespace {
+
 // ---- MSB partition (multi-GPU send side) -----------------------------------------------------------
 // E = uint32_t (keys) or uint64_t ({key, value} pairs: the key is the low dword, so its top byte is bits 24..31)
 
@@ -1975,10 +1857,8 @@ int partition_top_byte_entry(adlhip_device* d, const E* in, E* out, uint32_t* to
 }
 
 // ---- SoA key-value sort with 4- / 8-byte keys and 4- / 8- / 16-byte values (soa_wide_kernels.hpp) -----------------------------
-struct SoaWideLayout {
-    size_t off_pairs_a, off_pairs_b, off_kv, kv_bytes, total;
-};
-SoaWideLayout soa_wide_layout(const adlhip_device* d, size_t n)
+}  // namespace
+SoaWideLayout adlhip_internal::soa_wide_layout(const adlhip_device* d, size_t n)
 {
     SoaWideLayout L;
     L.off_pairs_a = 0;
@@ -1990,9 +1870,13 @@ SoaWideLayout soa_wide_layout(const adlhip_device* d, size_t n)
     return L;
 }
 
-struct V16 {
-    uint32_t x, y, z, w;
-} __attribute__((aligned(16)));
+int adlhip_internal::soa_check_widths(int key_bytes, int value_bytes)
+{
+    if (key_bytes != 4 && key_bytes != 8) return fail("key_bytes must be 4 or 8, got %d", key_bytes);
+    if (value_bytes != 4 && value_bytes != 8 && value_bytes != 16) return fail("value_bytes must be 4, 8 or 16, got %d", value_bytes);
+    return ADLHIP_SUCCESS;
+}
+namespace {
 
 template <typename K, typename V>
 int soa_wide_sort(adlhip_device* d, K* keys, V* vals, K* tmp_keys, V* tmp_vals, void* work, size_t n, int sort_bits)
@@ -2035,588 +1919,6 @@ int soa_wide_sort(adlhip_device* d, K* keys, V* vals, K* tmp_keys, V* tmp_vals, 
     if (sizeof(K) == 8) HIPCHK(hipMemcpyAsync(keys, tmp_keys, n * sizeof(K), hipMemcpyDeviceToDevice, d->stream));
     HIPCHK(hipMemcpyAsync(vals, tmp_vals, n * sizeof(V), hipMemcpyDeviceToDevice, d->stream));
     return ADLHIP_SUCCESS;
-}
-
-int soa_check_widths(int key_bytes, int value_bytes)
-{
-    if (key_bytes != 4 && key_bytes != 8) return fail("key_bytes must be 4 or 8, got %d", key_bytes);
-    if (value_bytes != 4 && value_bytes != 8 && value_bytes != 16) return fail("value_bytes must be 4, 8 or 16, got %d", value_bytes);
-    return ADLHIP_SUCCESS;
-}
-
-// ---- typed keys, order, argsort (typed_kernels.hpp; no reference counterpart) ---------------------------------------------------
-struct KeyTypeInfo {
-    int bytes, kind;   // kind: adlhip::kKeyUnsigned / kKeySigned / kKeyFloat
-};
-int key_type_info(int key_type, int order, KeyTypeInfo* out)
-{
-    if (key_type < ADLHIP_KEY_U32 || key_type > ADLHIP_KEY_F64)
-        return fail("key_type must be one of ADLHIP_KEY_U32 .. ADLHIP_KEY_F64 (0..5), got %d", key_type);
-    if (order != ADLHIP_ORDER_ASCENDING && order != ADLHIP_ORDER_DESCENDING)
-        return fail("order must be ADLHIP_ORDER_ASCENDING (0) or ADLHIP_ORDER_DESCENDING (1), got %d", order);
-    out->bytes = key_type < ADLHIP_KEY_U64 ? 4 : 8;
-    out->kind = key_type % 3;
-    return ADLHIP_SUCCESS;
-}
-
-// calls F_<KIND, DESC>(...) for the run-time kind and order
-#define ADLHIP_TYPED_DISPATCH(kind_, desc_, CALL)                                    \
-    do {                                                                             \
-        switch ((kind_) * 2 + ((desc_) ? 1 : 0)) {                                   \
-        case 0: CALL(adlhip::kKeyUnsigned, 0); break;                                \
-        case 1: CALL(adlhip::kKeyUnsigned, 1); break;                                \
-        case 2: CALL(adlhip::kKeySigned, 0); break;                                  \
-        case 3: CALL(adlhip::kKeySigned, 1); break;                                  \
-        case 4: CALL(adlhip::kKeyFloat, 0); break;                                   \
-        default: CALL(adlhip::kKeyFloat, 1); break;                                  \
-        }                                                                            \
-    } while (0)
-
-// one streaming sweep: dst[i] = enc(src[i]) or dec(src[i]).  The identity (unsigned, ascending) launches nothing when dst is src.
-template <typename U>
-int key_codec(adlhip_device* d, int kind, int desc, bool decode, U* dst, const U* src, size_t n)
-{
-    if (kind == adlhip::kKeyUnsigned && !desc) {
-        if (dst != src) HIPCHK(hipMemcpyAsync(dst, src, n * sizeof(U), hipMemcpyDeviceToDevice, d->stream));
-        return ADLHIP_SUCCESS;
-    }
-    const size_t nvec = n / (16 / sizeof(U));
-    const uint32_t wgs = (uint32_t)std::min<size_t>(std::max<size_t>((nvec + adlhip::kSoaNT - 1) / adlhip::kSoaNT, 1),
-                                                    (size_t)d->prop.multiProcessorCount * 16);
-    return launch(d, decode ? "key_decode" : "key_encode", [&] {
-#define ADLHIP_CODEC(KIND_, DESC_)                                                                                              \
-    if (decode) hipLaunchKernelGGL((adlhip::key_codec_kernel<U, KIND_, DESC_, 1>), dim3(wgs), dim3(adlhip::kSoaNT), 0, d->stream, dst, src, n); \
-    else hipLaunchKernelGGL((adlhip::key_codec_kernel<U, KIND_, DESC_, 0>), dim3(wgs), dim3(adlhip::kSoaNT), 0, d->stream, dst, src, n)
-        ADLHIP_TYPED_DISPATCH(kind, desc, ADLHIP_CODEC);
-#undef ADLHIP_CODEC
-    });
-}
-
-// The typed sibling of soa_wide_sort: {32 encoded key bits, source index} pairs through the stable pair sort, once per key dword, one
-// gather at the end.  keys_out / vals_out / index_out: whichever the caller wants (null = not written); none of them may be keys_in
-// or vals_in when it is gathered (8-byte keys, values) -- the callers pass partner arrays and copy back.
-template <typename U, typename V>
-int typed_index_sort(adlhip_device* d, int kind, int desc, const U* keys_in, U* keys_out, const V* vals_in, V* vals_out,
-                     uint32_t* index_out, void* work, size_t n)
-{
-    const SoaWideLayout L = soa_wide_layout(d, n);
-    char* w = static_cast<char*>(work);
-    uint64_t* pa = reinterpret_cast<uint64_t*>(w + L.off_pairs_a);
-    uint64_t* pb = reinterpret_cast<uint64_t*>(w + L.off_pairs_b);
-    void* kv = w + L.off_kv;
-    const uint32_t nn = (uint32_t)n;
-    const uint32_t wgs = (uint32_t)std::min<size_t>((n + adlhip::kSoaNT - 1) / adlhip::kSoaNT, (size_t)d->prop.multiProcessorCount * 16);
-    int rc = launch(d, sizeof(U) == 4 ? "typed_pack_index_k32" : "typed_pack_index_k64", [&] {
-#define ADLHIP_PACK(KIND_, DESC_) \
-    hipLaunchKernelGGL((adlhip::typed_pack_index_kernel<U, KIND_, DESC_>), dim3(wgs), dim3(adlhip::kSoaNT), 0, d->stream, keys_in, pa, nn)
-        ADLHIP_TYPED_DISPATCH(kind, desc, ADLHIP_PACK);
-#undef ADLHIP_PACK
-    });
-    if (rc) return rc;
-    rc = sort_entry<uint64_t>(d, ADLHIP_ELEM_KV32, pa, pb, kv, L.kv_bytes, n, 32, 32);
-    if (rc) return rc;
-    const uint64_t* sorted = pa;
-    if constexpr (sizeof(U) == 8) {   // second 32-bit digit; the sort is stable, so equal high dwords keep the order of their low dwords
-        rc = launch(d, "typed_repack_high", [&] {
-#define ADLHIP_REPACK(KIND_, DESC_) \
-    hipLaunchKernelGGL((adlhip::typed_repack_high_kernel<KIND_, DESC_>), dim3(wgs), dim3(adlhip::kSoaNT), 0, d->stream, keys_in, (const uint64_t*)pa, pb, nn)
-            ADLHIP_TYPED_DISPATCH(kind, desc, ADLHIP_REPACK);
-#undef ADLHIP_REPACK
-        });
-        if (rc) return rc;
-        rc = sort_entry<uint64_t>(d, ADLHIP_ELEM_KV32, pb, pa, kv, L.kv_bytes, n, 32, 32);
-        if (rc) return rc;
-        sorted = pb;
-    }
-    return launch(d, "typed_gather", [&] {
-#define ADLHIP_GATHER(KIND_, DESC_) \
-    hipLaunchKernelGGL((adlhip::typed_gather_kernel<U, V, KIND_, DESC_>), dim3(wgs), dim3(adlhip::kSoaNT), 0, d->stream, sorted, keys_in, keys_out, vals_in, vals_out, index_out, nn)
-        if constexpr (sizeof(U) == 8) ADLHIP_GATHER(adlhip::kKeyUnsigned, 0);   // 8-byte keys are fetched, not decoded
-        else ADLHIP_TYPED_DISPATCH(kind, desc, ADLHIP_GATHER);
-#undef ADLHIP_GATHER
-    });
-}
-
-// in-place pairs: gathered arrays land in the partner arrays and are copied back, as soa_wide_sort does
-template <typename U, typename V>
-int typed_pairs_sort(adlhip_device* d, int kind, int desc, U* keys, V* vals, U* tmp_keys, V* tmp_vals, void* work, size_t n)
-{
-    U* kout = sizeof(U) == 4 ? keys : tmp_keys;   // 4-byte keys are the pairs' own low dwords, decoded: keys[] is not read by the gather
-    int rc = typed_index_sort<U, V>(d, kind, desc, keys, kout, vals, tmp_vals, nullptr, work, n);
-    if (rc) return rc;
-    if (sizeof(U) == 8) HIPCHK(hipMemcpyAsync(keys, tmp_keys, n * sizeof(U), hipMemcpyDeviceToDevice, d->stream));
-    HIPCHK(hipMemcpyAsync(vals, tmp_vals, n * sizeof(V), hipMemcpyDeviceToDevice, d->stream));
-    return ADLHIP_SUCCESS;
-}
-
-int typed_check_n(size_t n)
-{
-    if (n > kMaxElems) return fail("n = %zu exceeds the supported maximum %zu", n, (size_t)kMaxElems);   // (< 2^32: indices fit a dword)
-    return ADLHIP_SUCCESS;
-}
-
-// encode in place -> unsigned sort on whole keys -> decode in place.  A sort that refuses after the encode was enqueued (a work buffer
-// that does not fit the one-sweep path the knobs ask for, ...) still gets its decode: the caller's keys come back as they were.
-template <typename U>
-int typed_keys_sort(adlhip_device* d, int elem_kind, int kind, int desc, U* keys, U* tmp, void* work, size_t work_bytes, size_t n)
-{
-    int rc = key_codec<U>(d, kind, desc, false, keys, keys, n);
-    if (rc) return rc;
-    const int bits = 8 * (int)sizeof(U);
-    rc = sort_entry<U>(d, elem_kind, keys, tmp, work, work_bytes, n, bits, bits);
-    if (rc) {
-        char kept[sizeof(g_err)];
-        memcpy(kept, g_err, sizeof(kept));
-        (void)key_codec<U>(d, kind, desc, true, keys, keys, n);
-        memcpy(g_err, kept, sizeof(kept));   // the sort's message, not the decode's
-        return rc;
-    }
-    return key_codec<U>(d, kind, desc, true, keys, keys, n);
-}
-
-// ---- top-k (select_kernels.hpp; no reference counterpart) ----------------------------------------------------------------------
-// Work buffer of adlhip_topk_typed: the larger of
-//   selection   [SelState][result: k positions][X], X = the larger of
-//                 two survivor lists of n {code, position} each (codes and positions in arrays of their own), and
-//                 the finish, which runs when the lists are dead: [partner array of the position sort: k u32][gathered keys: k]
-//                 [work of the position sort / of the k-element typed pair sort, whichever is larger]
-//   fallback    [work of the n-element argsort][its sorted keys: n][its index: n u32]
-// every part 256-byte aligned.
-constexpr size_t kTopkSelectMaxFraction = 8;   // "topk.algo" = -1: selection while k <= n / 8 (unmeasured; tools/topk_bench.py)
-struct TopkLayout {
-    size_t off_result, off_x;                               // selection
-    size_t off_codes[2], off_pos[2];                        //   X as survivor lists
-    size_t off_ptmp, off_keys, off_fwork, fwork_bytes;      //   X as the finish's scratch
-    size_t off_akeys, off_aidx, awork_bytes;                // fallback (its sort's work at offset 0)
-    size_t total;
-};
-TopkLayout topk_layout(const adlhip_device* d, size_t key_bytes, size_t n, size_t k)
-{
-    TopkLayout L;
-    L.off_result = sizeof(adlhip::SelState);
-    L.off_x = L.off_result + align_up(k * 4, 256);
-    size_t o = L.off_x;
-    for (int i = 0; i < 2; ++i) {
-        L.off_codes[i] = o;
-        L.off_pos[i] = o + align_up(n * key_bytes, 256);
-        o = L.off_pos[i] + align_up(n * 4, 256);
-    }
-    const size_t lists_end = o;
-    L.off_ptmp = L.off_x;
-    L.off_keys = L.off_ptmp + align_up(k * 4, 256);
-    L.off_fwork = L.off_keys + align_up(k * key_bytes, 256);
-    L.fwork_bytes = std::max(sort_work_bytes(d, ADLHIP_ELEM_U32, k, 32, 1), soa_wide_layout(d, k).total);
-    const size_t select_total = std::max(lists_end, L.off_fwork + L.fwork_bytes);
-    L.awork_bytes = soa_wide_layout(d, n).total;
-    L.off_akeys = align_up(L.awork_bytes, 256);
-    L.off_aidx = L.off_akeys + align_up(n * key_bytes, 256);
-    L.total = std::max(select_total, L.off_aidx + align_up(n * 4, 256));
-    return L;
-}
-
-// digit `level` of the composite (code of `key_bits` bits, position of `pos_bits` bits), most significant first, 11 bits each but
-// for the last digit of either part
-adlhip::SelDigit topk_digit(int level, int key_bits, int pos_bits)
-{
-    const int key_levels = (key_bits + adlhip::kSelDigitBits - 1) / adlhip::kSelDigitBits;
-    const bool from_pos = level >= key_levels;
-    const int left = from_pos ? pos_bits - adlhip::kSelDigitBits * (level - key_levels) : key_bits - adlhip::kSelDigitBits * level;
-    if (left <= 0) return adlhip::SelDigit{0u, 0u, 0u};   // behind the last digit: everything counts as digit 0
-    const int bits = std::min(left, adlhip::kSelDigitBits);
-    return adlhip::SelDigit{from_pos ? 1u : 0u, (uint32_t)(left - bits), (1u << bits) - 1u};
-}
-
-// the full argsort into the work buffer, its first k entries to the caller
-template <typename U>
-int topk_by_sort(adlhip_device* d, int kind, int desc, const U* keys_in, U* keys_out, uint32_t* index_out, void* work, size_t n, size_t k)
-{
-    const TopkLayout L = topk_layout(d, sizeof(U), n, k);
-    char* w = static_cast<char*>(work);
-    U* akeys = reinterpret_cast<U*>(w + L.off_akeys);
-    uint32_t* aidx = reinterpret_cast<uint32_t*>(w + L.off_aidx);
-    const int rc = typed_index_sort<U, uint32_t>(d, kind, desc, keys_in, keys_out ? akeys : nullptr, nullptr, nullptr, aidx, work, n);
-    if (rc) return rc;
-    if (keys_out) HIPCHK(hipMemcpyAsync(keys_out, akeys, k * sizeof(U), hipMemcpyDeviceToDevice, d->stream));
-    if (index_out) HIPCHK(hipMemcpyAsync(index_out, aidx, k * 4, hipMemcpyDeviceToDevice, d->stream));
-    return ADLHIP_SUCCESS;
-}
-
-// keys_in need not be 16-byte aligned when stage_keys is set: the two kernels that load the keys in 16-byte vectors then read a copy
-// of them in the first survivor list (dead until level 2 writes it, by which time both have run); the gather reads keys_in itself
-template <typename U>
-int topk_by_select(adlhip_device* d, int kind, int desc, const U* keys_in, U* keys_out, uint32_t* index_out, void* work, size_t n, size_t k,
-                   bool stage_keys = false)
-{
-    const TopkLayout L = topk_layout(d, sizeof(U), n, k);
-    char* w = static_cast<char*>(work);
-    adlhip::SelState* st = reinterpret_cast<adlhip::SelState*>(w);
-    uint32_t* result = reinterpret_cast<uint32_t*>(w + L.off_result);
-    U* codes[2] = {reinterpret_cast<U*>(w + L.off_codes[0]), reinterpret_cast<U*>(w + L.off_codes[1])};
-    uint32_t* pos[2] = {reinterpret_cast<uint32_t*>(w + L.off_pos[0]), reinterpret_cast<uint32_t*>(w + L.off_pos[1])};
-    const uint32_t nn = (uint32_t)n, kk = (uint32_t)k;
-    const int key_bits = 8 * (int)sizeof(U);
-    int pos_bits = 1;
-    while (pos_bits < 32 && ((size_t)1 << pos_bits) < n) ++pos_bits;
-    const int key_levels = (key_bits + adlhip::kSelDigitBits - 1) / adlhip::kSelDigitBits;
-    const int levels = key_levels + (pos_bits + adlhip::kSelDigitBits - 1) / adlhip::kSelDigitBits;   // <= kSelMaxLevels
-    constexpr size_t tile = (size_t)adlhip::kSelNT * adlhip::kSelVecs * (16 / sizeof(U));
-    const uint32_t wgs = (uint32_t)std::min<size_t>((n + tile - 1) / tile, (size_t)d->prop.multiProcessorCount * 8);
-
-    HIPCHK(hipMemsetAsync(st, 0, sizeof(adlhip::SelState), d->stream));   // the starting state, whatever the buffer held
-    const U* keys_vec = keys_in;
-    if (stage_keys) {
-        HIPCHK(hipMemcpyAsync(codes[0], keys_in, n * sizeof(U), hipMemcpyDeviceToDevice, d->stream));
-        keys_vec = codes[0];
-    }
-    int rc = launch(d, "select_hist", [&] {
-#define ADLHIP_SELH(KIND_, DESC_) \
-    hipLaunchKernelGGL((adlhip::select_hist_kernel<U, KIND_, DESC_>), dim3(wgs), dim3(adlhip::kSelNT), 0, d->stream, keys_vec, nn, st, topk_digit(0, key_bits, pos_bits))
-        ADLHIP_TYPED_DISPATCH(kind, desc, ADLHIP_SELH);
-#undef ADLHIP_SELH
-    });
-    if (rc) return rc;
-    rc = launch(d, "select_filter_first", [&] {
-#define ADLHIP_SELF(KIND_, DESC_)                                                                                                   \
-    hipLaunchKernelGGL((adlhip::select_filter_kernel<U, KIND_, DESC_, 1>), dim3(wgs), dim3(adlhip::kSelNT), 0, d->stream, keys_vec, \
-                       (const uint32_t*)nullptr, codes[1], pos[1], result, st, 1u, nn, kk, topk_digit(0, key_bits, pos_bits),       \
-                       topk_digit(1, key_bits, pos_bits))
-        ADLHIP_TYPED_DISPATCH(kind, desc, ADLHIP_SELF);
-#undef ADLHIP_SELF
-    });
-    if (rc) return rc;
-    for (int lv = 2; lv <= levels; ++lv) {   // the worst case; a level behind the one that completed the selection leaves at once
-        rc = launch(d, "select_filter", [&] {
-            hipLaunchKernelGGL((adlhip::select_filter_kernel<U, 0, 0, 0>), dim3(wgs), dim3(adlhip::kSelNT), 0, d->stream,
-                               (const U*)codes[(lv - 1) & 1], (const uint32_t*)pos[(lv - 1) & 1], codes[lv & 1], pos[lv & 1], result, st,
-                               (uint32_t)lv, nn, kk, topk_digit(lv - 1, key_bits, pos_bits), topk_digit(lv, key_bits, pos_bits));
-        });
-        if (rc) return rc;
-    }
-
-    // finish: the k positions ascending, their keys, then the stable typed pair sort of (key, position) -- stability and ascending
-    // positions give the tie order of the argsort
-    uint32_t* ptmp = reinterpret_cast<uint32_t*>(w + L.off_ptmp);
-    U* gkeys = reinterpret_cast<U*>(w + L.off_keys);
-    void* fwork = w + L.off_fwork;
-    rc = sort_entry<uint32_t>(d, ADLHIP_ELEM_U32, result, ptmp, fwork, L.fwork_bytes, k, 32, 32);
-    if (rc) return rc;
-    const uint32_t gwgs = (uint32_t)std::min<size_t>((k + adlhip::kSelNT - 1) / adlhip::kSelNT, (size_t)d->prop.multiProcessorCount * 16);
-    rc = launch(d, "select_gather", [&] {
-        hipLaunchKernelGGL((adlhip::select_gather_kernel<U>), dim3(gwgs), dim3(adlhip::kSelNT), 0, d->stream, keys_in, (const uint32_t*)result,
-                           gkeys, kk);
-    });
-    if (rc) return rc;
-    return typed_index_sort<U, uint32_t>(d, kind, desc, gkeys, keys_out, index_out ? result : nullptr, index_out, nullptr, fwork, k);
-}
-
-// ---- row-wise top-k (toprows_kernels.hpp; no reference counterpart) ---------------------------------------------------------------
-// "topk.rows_algo" = -1: the row kernel while k <= kRowMaxK and cols <= kTopkRowsMaxCols.  One workgroup streaming a very long row
-// loses to the per-row loop, which puts the whole device on each row; where has NOT been measured (tools/topk_rows_bench.py measures
-// it): 256 Ki is a placeholder, as kTopkSelectMaxFraction is.
-constexpr size_t kTopkRowsMaxCols = size_t(256) << 10;
-constexpr int kTopkRowsWgsPerCu = 4;   // default grid of the row kernel per CU (its LDS admits 3 workgroups of 4-byte keys, 2 of 8-byte keys)
-
-// the per-row loop: `rows` 1-D top-k calls on the shared work buffer, in stream order
-template <typename U>
-int topk_rows_loop(adlhip_device* d, int kind, int desc, const U* keys_in, size_t rows, size_t cols, size_t row_stride, size_t k,
-                   U* keys_out, uint32_t* index_out, void* work)
-{
-    const bool select = d->topk_algo < 0 ? k <= cols / kTopkSelectMaxFraction : d->topk_algo == 1;
-    for (size_t r = 0; r < rows; ++r) {
-        const U* row = keys_in + r * row_stride;
-        U* ko = keys_out ? keys_out + r * k : nullptr;
-        uint32_t* io = index_out ? index_out + r * k : nullptr;
-        // (the selection loads its keys in 16-byte vectors; a row that starts elsewhere is staged.  The argsort reads key by key.)
-        const int rc = select ? topk_by_select<U>(d, kind, desc, row, ko, io, work, cols, k, (reinterpret_cast<uintptr_t>(row) & 15u) != 0)
-                              : topk_by_sort<U>(d, kind, desc, row, ko, io, work, cols, k);
-        if (rc) return rc;
-    }
-    return ADLHIP_SUCCESS;
-}
-
-template <typename U>
-int topk_rows_kernel_path(adlhip_device* d, int kind, int desc, const U* keys_in, size_t rows, size_t cols, size_t row_stride, size_t k,
-                          U* keys_out, uint32_t* index_out)
-{
-    adlhip::RowPlan plan;
-    const int key_bits = 8 * (int)sizeof(U);
-    int pos_bits = 1;
-    while (pos_bits < 32 && ((size_t)1 << pos_bits) < cols) ++pos_bits;
-    const int key_levels = (key_bits + adlhip::kSelDigitBits - 1) / adlhip::kSelDigitBits;
-    plan.levels = (uint32_t)(key_levels + (pos_bits + adlhip::kSelDigitBits - 1) / adlhip::kSelDigitBits);   // <= kSelMaxLevels
-    for (int lv = 0; lv < adlhip::kSelMaxLevels; ++lv) plan.d[lv] = topk_digit(lv, key_bits, pos_bits);
-    const size_t cap = d->topk_rows_grid > 0 ? (size_t)d->topk_rows_grid : (size_t)d->prop.multiProcessorCount * kTopkRowsWgsPerCu;
-    const uint32_t wgs = (uint32_t)std::min(rows, cap);
-    return launch(d, sizeof(U) == 4 ? "topk_rows_k32" : "topk_rows_k64", [&] {
-#define ADLHIP_ROWS(KIND_, DESC_)                                                                                                   \
-    hipLaunchKernelGGL((adlhip::topk_rows_kernel<U, KIND_, DESC_>), dim3(wgs), dim3(adlhip::kSelNT), 0, d->stream, keys_in, rows,  \
-                       (uint32_t)cols, row_stride, (uint32_t)k, keys_out, index_out, plan)
-        ADLHIP_TYPED_DISPATCH(kind, desc, ADLHIP_ROWS);
-#undef ADLHIP_ROWS
-    });
-}
-
-// ---- unique / run-length encode (unique_kernels.hpp; no reference counterpart) ------------------------------------------------------
-// Work of the run stage: [chunk head counts: one u32 per workgroup of the largest grid][offsets: n + 1 u32, used when the caller wants
-// counts but passes no offsets], each rounded up to 256 bytes.
-constexpr int kUniqueWgsPerCu = 4;   // grid of the run stage per CU at most ("debug.unique_grid" lowers it)
-struct RunsLayout {
-    size_t off_offsets, total;
-};
-RunsLayout runs_layout(const adlhip_device* d, size_t n)
-{
-    RunsLayout L;
-    L.off_offsets = align_up((size_t)d->prop.multiProcessorCount * kUniqueWgsPerCu * 4, 256);
-    L.total = L.off_offsets + align_up((n + 1) * 4, 256);
-    return L;
-}
-
-// Work of adlhip_unique_typed: [run stage][S: the sorted keys, n][the sort's own buffers]
-//   keys path   [tmp: the sort's partner array, n keys][work of the typed keys sort]
-//   index path  [P: the argsort's index, n u32][work of the argsort]
-struct UniqueLayout {
-    size_t off_sorted, off_tmp, off_swork, swork_bytes, keys_total;   // keys path
-    size_t off_perm, off_awork, awork_bytes, index_total;             // index path
-};
-UniqueLayout unique_layout(const adlhip_device* d, size_t key_bytes, size_t n)
-{
-    UniqueLayout L;
-    L.off_sorted = runs_layout(d, n).total;
-    const size_t behind = L.off_sorted + align_up(n * key_bytes, 256);
-    L.off_tmp = behind;
-    L.off_swork = L.off_tmp + align_up(n * key_bytes, 256);
-    L.swork_bytes = sort_work_bytes(d, key_bytes == 4 ? ADLHIP_ELEM_U32 : ADLHIP_ELEM_U64, n, 8 * (int)key_bytes, 1);
-    L.keys_total = L.off_swork + align_up(L.swork_bytes, 256);
-    L.off_perm = behind;
-    L.off_awork = L.off_perm + align_up(n * 4, 256);
-    L.awork_bytes = soa_wide_layout(d, n).total;
-    L.index_total = L.off_awork + align_up(L.awork_bytes, 256);
-    return L;
-}
-
-// the run stage on n > 0 grouped keys; perm (null or the argsort's index) feeds first_index and inverse
-template <typename U>
-int runs_stage(adlhip_device* d, const U* keys, const uint32_t* perm, size_t n, U* unique_out, uint32_t* counts, uint32_t* offsets,
-               uint32_t* first_index, uint32_t* inverse, uint32_t* num_out, void* work)
-{
-    const RunsLayout L = runs_layout(d, n);
-    char* w = static_cast<char*>(work);
-    uint32_t* chunk = reinterpret_cast<uint32_t*>(w);
-    if (counts && !offsets) offsets = reinterpret_cast<uint32_t*>(w + L.off_offsets);
-    // the chunk split: every workgroup owns tiles_per_wg whole tiles (the last one what is left, at least one)
-    constexpr size_t tile = (size_t)adlhip::kSelNT * adlhip::kSelVecs * (16 / sizeof(U));
-    const size_t tiles = (n + tile - 1) / tile;
-    size_t cap = (size_t)d->prop.multiProcessorCount * kUniqueWgsPerCu;
-    if (d->unique_grid > 0) cap = std::min(cap, (size_t)d->unique_grid);
-    const size_t tiles_per_wg = (tiles + cap - 1) / cap;
-    const uint32_t wgs = (uint32_t)((tiles + tiles_per_wg - 1) / tiles_per_wg);
-    const uint32_t nn = (uint32_t)n, nt = (uint32_t)tiles, tpw = (uint32_t)tiles_per_wg;
-    int rc = launch(d, sizeof(U) == 4 ? "runs_count_k32" : "runs_count_k64", [&] {
-        hipLaunchKernelGGL((adlhip::runs_count_kernel<U>), dim3(wgs), dim3(adlhip::kSelNT), 0, d->stream, keys, nn, nt, tpw, chunk);
-    });
-    if (rc) return rc;
-    rc = launch(d, "runs_scan", [&] {   // in place; the total is the number of runs
-        hipLaunchKernelGGL(adlhip::scan_single_kernel, dim3(1), dim3(adlhip::kScanNT), 0, d->stream, (const uint32_t*)chunk, chunk, (size_t)wgs,
-                           num_out);
-    });
-    if (rc) return rc;
-    rc = launch(d, sizeof(U) == 4 ? "runs_emit_k32" : "runs_emit_k64", [&] {
-        if (perm)
-            hipLaunchKernelGGL((adlhip::runs_emit_kernel<U, 1>), dim3(wgs), dim3(adlhip::kSelNT), 0, d->stream, keys, perm, nn, nt, tpw,
-                               (const uint32_t*)chunk, unique_out, offsets, first_index, inverse);
-        else
-            hipLaunchKernelGGL((adlhip::runs_emit_kernel<U, 0>), dim3(wgs), dim3(adlhip::kSelNT), 0, d->stream, keys, (const uint32_t*)nullptr, nn,
-                               nt, tpw, (const uint32_t*)chunk, unique_out, offsets, (uint32_t*)nullptr, (uint32_t*)nullptr);
-    });
-    if (rc || !counts) return rc;
-    const uint32_t cwgs = (uint32_t)((n + adlhip::kRunsCountsPerWg - 1) / adlhip::kRunsCountsPerWg);   // (at most 2^21)
-    return launch(d, "runs_counts", [&] {
-        hipLaunchKernelGGL(adlhip::runs_counts_kernel, dim3(cwgs), dim3(adlhip::kSelNT), 0, d->stream, (const uint32_t*)offsets,
-                           (const uint32_t*)num_out, nn, counts);
-    });
-}
-
-// what both entry points refuse about their buffers, before anything is enqueued
-struct RunsOut {
-    const void* p;
-    size_t bytes;
-    const char* name;
-};
-int runs_check_buffers(const char* what, const void* keys_in, size_t in_bytes, const RunsOut* outs, int num_outs, const void* num_out,
-                       const void* work)
-{
-    if (!keys_in || !outs[0].p || !work) return fail("null buffer passed to %s", what);
-    uintptr_t bits = reinterpret_cast<uintptr_t>(keys_in) | reinterpret_cast<uintptr_t>(work);
-    for (int i = 0; i < num_outs; ++i) bits |= reinterpret_cast<uintptr_t>(outs[i].p);
-    if (bits & 15u) return fail("%s buffers must be 16-byte aligned", what);
-    const char* in0 = static_cast<const char*>(keys_in);
-    const char* in1 = in0 + in_bytes;
-    for (int i = 0; i <= num_outs; ++i) {
-        const char* o = static_cast<const char*>(i < num_outs ? outs[i].p : num_out);
-        const size_t bytes = i < num_outs ? outs[i].bytes : 4;
-        if (o && o < in1 && in0 < o + bytes) return fail("%s: %s must not overlap d_keys_in", what, i < num_outs ? outs[i].name : "the count word");
-    }
-    return ADLHIP_SUCCESS;
-}
-
-// sort (keys path: a copy of the keys, in place; index path: the argsort, which also gives P), then the run stage
-template <typename U>
-int unique_run(adlhip_device* d, const KeyTypeInfo& t, int order, bool index_path, const U* keys_in, size_t n, U* unique_out,
-                      uint32_t* counts, uint32_t* offsets, uint32_t* first_index, uint32_t* inverse, uint32_t* num_out, void* work)
-{
-    const UniqueLayout L = unique_layout(d, sizeof(U), n);
-    char* w = static_cast<char*>(work);
-    U* sorted = reinterpret_cast<U*>(w + L.off_sorted);
-    if (index_path) {
-        uint32_t* perm = reinterpret_cast<uint32_t*>(w + L.off_perm);
-        const int rc = typed_index_sort<U, uint32_t>(d, t.kind, order, keys_in, sorted, nullptr, nullptr, perm, w + L.off_awork, n);
-        if (rc) return rc;
-        return runs_stage<U>(d, sorted, perm, n, unique_out, counts, offsets, first_index, inverse, num_out, work);
-    }
-    HIPCHK(hipMemcpyAsync(sorted, keys_in, n * sizeof(U), hipMemcpyDeviceToDevice, d->stream));
-    const int rc = typed_keys_sort<U>(d, sizeof(U) == 4 ? ADLHIP_ELEM_U32 : ADLHIP_ELEM_U64, t.kind, order, sorted, reinterpret_cast<U*>(w + L.off_tmp),
-                                      w + L.off_swork, L.swork_bytes, n);
-    if (rc) return rc;
-    return runs_stage<U>(d, sorted, nullptr, n, unique_out, counts, offsets, nullptr, nullptr, num_out, work);
-}
-
-// ---- reduce by key (reduce_kernels.hpp; no reference counterpart) --------------------------------------------------------------------
-// Work of the reduce stage, per workgroup of the largest grid: [head counts: u32][head flags: u32][tail aggregates: 8 bytes][carries: 8
-// bytes], then [offsets: n + 1 u32, used when the caller wants counts but passes no offsets], each rounded up to 256 bytes.
-constexpr int kReduceWgsPerCu = 4;   // grid of the reduce stage per CU at most ("debug.reduce_grid" lowers it)
-struct ReduceLayout {
-    size_t off_flag, off_agg, off_carry, off_offsets, total;
-};
-ReduceLayout reduce_layout(const adlhip_device* d, size_t n)
-{
-    const size_t cap = (size_t)d->prop.multiProcessorCount * kReduceWgsPerCu;
-    ReduceLayout L;
-    L.off_flag = align_up(cap * 4, 256);
-    L.off_agg = L.off_flag + align_up(cap * 4, 256);
-    L.off_carry = L.off_agg + align_up(cap * 8, 256);
-    L.off_offsets = L.off_carry + align_up(cap * 8, 256);
-    L.total = L.off_offsets + align_up((n + 1) * 4, 256);
-    return L;
-}
-
-// Work of adlhip_reduce_by_key_typed: [reduce stage][the sorted keys, n][the permuted values, n][work of the typed pairs sort]
-struct ReduceByKeyLayout {
-    size_t off_keys, off_vals, off_swork, total;
-};
-ReduceByKeyLayout reduce_by_key_layout(const adlhip_device* d, size_t key_bytes, size_t value_bytes, size_t n)
-{
-    ReduceByKeyLayout L;
-    L.off_keys = reduce_layout(d, n).total;
-    L.off_vals = L.off_keys + align_up(n * key_bytes, 256);
-    L.off_swork = L.off_vals + align_up(n * value_bytes, 256);
-    L.total = L.off_swork + align_up(soa_wide_layout(d, n).total, 256);
-    return L;
-}
-
-struct ValueTypeInfo {
-    int bytes, kind;
-};
-int reduce_value_info(int value_type, int op, ValueTypeInfo* out)
-{
-    if (value_type < ADLHIP_KEY_U32 || value_type > ADLHIP_KEY_F64)
-        return fail("value_type must be one of ADLHIP_KEY_U32 .. ADLHIP_KEY_F64 (0..5), got %d", value_type);
-    if (op != ADLHIP_REDUCE_SUM && op != ADLHIP_REDUCE_MIN && op != ADLHIP_REDUCE_MAX)
-        return fail("op must be ADLHIP_REDUCE_SUM (0), ADLHIP_REDUCE_MIN (1) or ADLHIP_REDUCE_MAX (2), got %d", op);
-    out->bytes = value_type < ADLHIP_KEY_U64 ? 4 : 8;
-    out->kind = value_type % 3;
-    return ADLHIP_SUCCESS;
-}
-
-// the reduce stage on n > 0 grouped keys and their values
-template <typename K, typename W, int OP>
-int reduce_stage_op(adlhip_device* d, const K* keys, const W* vals, size_t n, adlhip::RedCodec codec, K* unique_out, W* reduced_out,
-                    uint32_t* counts, uint32_t* offsets, uint32_t* num_out, void* work)
-{
-    const ReduceLayout L = reduce_layout(d, n);
-    char* w = static_cast<char*>(work);
-    uint32_t* heads = reinterpret_cast<uint32_t*>(w);
-    uint32_t* flag = reinterpret_cast<uint32_t*>(w + L.off_flag);
-    W* agg = reinterpret_cast<W*>(w + L.off_agg);
-    W* carry = reinterpret_cast<W*>(w + L.off_carry);
-    if (counts && !offsets) offsets = reinterpret_cast<uint32_t*>(w + L.off_offsets);
-    // the chunk split of runs_stage, on tiles of kRedTile elements
-    constexpr size_t tile = (size_t)adlhip::kRedTile;
-    const size_t tiles = (n + tile - 1) / tile;
-    size_t cap = (size_t)d->prop.multiProcessorCount * kReduceWgsPerCu;
-    if (d->reduce_grid > 0) cap = std::min(cap, (size_t)d->reduce_grid);
-    const size_t tiles_per_wg = (tiles + cap - 1) / cap;
-    const uint32_t wgs = (uint32_t)((tiles + tiles_per_wg - 1) / tiles_per_wg);
-    const uint32_t nn = (uint32_t)n, nt = (uint32_t)tiles, tpw = (uint32_t)tiles_per_wg;
-    static const char* const kOpName[3] = {"sum", "fsum", "max"};
-    const std::string kv = "_k" + std::to_string(8 * sizeof(K)) + "v" + std::to_string(8 * sizeof(W));
-    int rc = launch(d, intern(std::string("reduce_partial_") + kOpName[OP] + kv), [&] {
-        hipLaunchKernelGGL((adlhip::reduce_partial_kernel<K, W, OP>), dim3(wgs), dim3(adlhip::kSelNT), 0, d->stream, keys, vals, nn, nt, tpw, codec,
-                           heads, flag, agg);
-    });
-    if (rc) return rc;
-    rc = launch(d, intern(std::string("reduce_carry_") + kOpName[OP] + "_v" + std::to_string(8 * sizeof(W))), [&] {   // the head counts in place; their total is the number of runs
-        hipLaunchKernelGGL((adlhip::reduce_carry_kernel<W, OP>), dim3(1), dim3(adlhip::kSelNT), 0, d->stream, heads, (const uint32_t*)flag,
-                           (const W*)agg, carry, wgs, num_out);
-    });
-    if (rc) return rc;
-    rc = launch(d, intern(std::string("reduce_emit_") + kOpName[OP] + kv), [&] {
-        hipLaunchKernelGGL((adlhip::reduce_emit_kernel<K, W, OP>), dim3(wgs), dim3(adlhip::kSelNT), 0, d->stream, keys, vals, nn, nt, tpw, codec,
-                           (const uint32_t*)heads, (const W*)carry, unique_out, reduced_out, offsets);
-    });
-    if (rc || !counts) return rc;
-    const uint32_t cwgs = (uint32_t)((n + adlhip::kRunsCountsPerWg - 1) / adlhip::kRunsCountsPerWg);   // (at most 2^21)
-    return launch(d, "runs_counts", [&] {
-        hipLaunchKernelGGL(adlhip::runs_counts_kernel, dim3(cwgs), dim3(adlhip::kSelNT), 0, d->stream, (const uint32_t*)offsets,
-                           (const uint32_t*)num_out, nn, counts);
-    });
-}
-
-// the kernel's operator from (op, the value's kind): wrapping sum, float sum, or max on codes (min: complemented codes)
-template <typename K, typename W>
-int reduce_stage(adlhip_device* d, const K* keys, const W* vals, size_t n, int value_kind, int op, K* unique_out, W* reduced_out,
-                 uint32_t* counts, uint32_t* offsets, uint32_t* num_out, void* work)
-{
-    adlhip::RedCodec codec = {(uint32_t)value_kind, op == ADLHIP_REDUCE_MIN ? 1u : 0u};
-    if (op != ADLHIP_REDUCE_SUM)
-        return reduce_stage_op<K, W, adlhip::kRedMax>(d, keys, vals, n, codec, unique_out, reduced_out, counts, offsets, num_out, work);
-    if (value_kind == adlhip::kKeyFloat)
-        return reduce_stage_op<K, W, adlhip::kRedFloatSum>(d, keys, vals, n, codec, unique_out, reduced_out, counts, offsets, num_out, work);
-    return reduce_stage_op<K, W, adlhip::kRedSum>(d, keys, vals, n, codec, unique_out, reduced_out, counts, offsets, num_out, work);
-}
-
-// what both entry points refuse about their buffers, before anything is enqueued
-int reduce_check_buffers(const char* what, const void* keys_in, size_t keys_bytes, const void* vals_in, size_t vals_bytes, const RunsOut* outs,
-                         int num_outs, const void* num_out, const void* work)
-{
-    if (!keys_in || !vals_in || !outs[0].p || !outs[1].p || !work) return fail("null buffer passed to %s", what);
-    uintptr_t bits = reinterpret_cast<uintptr_t>(keys_in) | reinterpret_cast<uintptr_t>(vals_in) | reinterpret_cast<uintptr_t>(work);
-    for (int i = 0; i < num_outs; ++i) bits |= reinterpret_cast<uintptr_t>(outs[i].p);
-    if (bits & 15u) return fail("%s buffers must be 16-byte aligned", what);
-    for (int in = 0; in < 2; ++in) {
-        const char* in0 = static_cast<const char*>(in ? vals_in : keys_in);
-        const char* in1 = in0 + (in ? vals_bytes : keys_bytes);
-        for (int i = 0; i <= num_outs; ++i) {
-            const char* o = static_cast<const char*>(i < num_outs ? outs[i].p : num_out);
-            const size_t bytes = i < num_outs ? outs[i].bytes : 4;
-            if (o && o < in1 && in0 < o + bytes)
-                return fail("%s: %s must not overlap %s", what, i < num_outs ? outs[i].name : "the count word", in ? "d_vals_in" : "d_keys_in");
-        }
-    }
-    return ADLHIP_SUCCESS;
-}
-
-// the stable typed pairs sort from the caller's arrays into d_work (no copy: the sort's gather writes there), then the reduce stage
-template <typename K, typename W>
-int reduce_by_key_run(adlhip_device* d, const KeyTypeInfo& t, int order, const K* keys_in, const W* vals_in, size_t n, int value_kind, int op,
-                      K* unique_out, W* reduced_out, uint32_t* counts, uint32_t* offsets, uint32_t* num_out, void* work)
-{
-    const ReduceByKeyLayout L = reduce_by_key_layout(d, sizeof(K), sizeof(W), n);
-    char* w = static_cast<char*>(work);
-    K* skeys = reinterpret_cast<K*>(w + L.off_keys);
-    W* svals = reinterpret_cast<W*>(w + L.off_vals);
-    const int rc = typed_index_sort<K, W>(d, t.kind, order, keys_in, skeys, vals_in, svals, nullptr, w + L.off_swork, n);
-    if (rc) return rc;
-    return reduce_stage<K, W>(d, skeys, svals, n, value_kind, op, unique_out, reduced_out, counts, offsets, num_out, work);
 }
 
 }  // namespace
@@ -3087,17 +2389,17 @@ int adlhip_radix_sort_scratch_bytes(adlhip_device* d, int elem_kind, size_t n, s
 
 int adlhip_radix_sort_u32(adlhip_device* d, uint32_t* keys, uint32_t* tmp, void* work, size_t work_bytes, size_t n, int sort_bits)
 {
-    return sort_entry<uint32_t>(d, ADLHIP_ELEM_U32, keys, tmp, work, work_bytes, n, sort_bits, 32);
+    return sort_elements(d, ADLHIP_ELEM_U32, keys, tmp, work, work_bytes, n, sort_bits);
 }
 
 int adlhip_radix_sort_kv32(adlhip_device* d, void* pairs, void* tmp, void* work, size_t work_bytes, size_t n, int sort_bits)
 {
-    return sort_entry<uint64_t>(d, ADLHIP_ELEM_KV32, (uint64_t*)pairs, (uint64_t*)tmp, work, work_bytes, n, sort_bits, 32);
+    return sort_elements(d, ADLHIP_ELEM_KV32, pairs, tmp, work, work_bytes, n, sort_bits);
 }
 
 int adlhip_radix_sort_u64(adlhip_device* d, uint64_t* keys, uint64_t* tmp, void* work, size_t work_bytes, size_t n, int sort_bits)
 {
-    return sort_entry<uint64_t>(d, ADLHIP_ELEM_U64, keys, tmp, work, work_bytes, n, sort_bits, 64);
+    return sort_elements(d, ADLHIP_ELEM_U64, keys, tmp, work, work_bytes, n, sort_bits);
 }
 
 int adlhip_radix_sort_soa32(adlhip_device* d, uint32_t* keys, uint32_t* vals, uint32_t* tmp_keys, uint32_t* tmp_vals,
@@ -3162,372 +2464,6 @@ int adlhip_radix_sort_soa(adlhip_device* d, void* keys, int key_bytes, void* val
 #undef ADLHIP_SOA
 }
 
-// ---- typed keys, order, argsort ---------------------------------------------------------------------
-
-static int key_codec_entry(adlhip_device* d, int key_type, int order, bool decode, void* dst, const void* src, size_t n)
-{
-    if (bind(d)) return ADLHIP_FAILURE;
-    KeyTypeInfo t;
-    if (key_type_info(key_type, order, &t)) return ADLHIP_FAILURE;
-    if (n > kMaxElems) return fail("n = %zu exceeds the supported maximum %zu", n, (size_t)kMaxElems);
-    if (n == 0) return ADLHIP_SUCCESS;
-    if (!dst || !src) return fail("null buffer passed to the key codec");
-    if ((reinterpret_cast<uintptr_t>(dst) | reinterpret_cast<uintptr_t>(src)) & 15u) return fail("key buffers must be 16-byte aligned");
-    if (t.bytes == 4) return key_codec<uint32_t>(d, t.kind, order, decode, (uint32_t*)dst, (const uint32_t*)src, n);
-    return key_codec<uint64_t>(d, t.kind, order, decode, (uint64_t*)dst, (const uint64_t*)src, n);
-}
-
-int adlhip_key_encode(adlhip_device* d, int key_type, int order, void* dst, const void* src, size_t n)
-{
-    return key_codec_entry(d, key_type, order, false, dst, src, n);
-}
-
-int adlhip_key_decode(adlhip_device* d, int key_type, int order, void* dst, const void* src, size_t n)
-{
-    return key_codec_entry(d, key_type, order, true, dst, src, n);
-}
-
-int adlhip_sort_typed_scratch_bytes(adlhip_device* d, int key_type, int mode, int value_bytes, size_t n, size_t* tmp_keys_bytes,
-                                    size_t* tmp_vals_bytes, size_t* work_bytes)
-{
-    if (!d) return fail("null device handle");
-    KeyTypeInfo t;
-    if (key_type_info(key_type, ADLHIP_ORDER_ASCENDING, &t)) return ADLHIP_FAILURE;
-    if (mode < 0 || mode > 2) return fail("mode must be 0 (keys only), 1 (pairs) or 2 (argsort), got %d", mode);
-    if (mode == 1 && soa_check_widths(t.bytes, value_bytes)) return ADLHIP_FAILURE;
-    size_t tk = 0, tv = 0, wb = 0;
-    if (mode == 0) {
-        tk = align_up(n * (size_t)t.bytes, 256);
-        wb = sort_work_bytes(d, t.bytes == 4 ? ADLHIP_ELEM_U32 : ADLHIP_ELEM_U64, n, 8 * t.bytes, 1);
-    } else {
-        if (mode == 1) {
-            tk = t.bytes == 8 ? align_up(n * 8, 256) : 0;   // 4-byte keys come out of the sorted pairs themselves
-            tv = align_up(n * (size_t)value_bytes, 256);
-        }
-        wb = soa_wide_layout(d, n).total;
-    }
-    if (tmp_keys_bytes) *tmp_keys_bytes = tk;
-    if (tmp_vals_bytes) *tmp_vals_bytes = tv;
-    if (work_bytes) *work_bytes = wb;
-    return ADLHIP_SUCCESS;
-}
-
-int adlhip_sort_keys_typed(adlhip_device* d, int key_type, int order, void* keys, void* tmp, void* work, size_t work_bytes, size_t n)
-{
-    if (bind(d)) return ADLHIP_FAILURE;
-    KeyTypeInfo t;
-    if (key_type_info(key_type, order, &t)) return ADLHIP_FAILURE;
-    if (typed_check_n(n)) return ADLHIP_FAILURE;
-    if (n == 0) return ADLHIP_SUCCESS;
-    if (!keys || !tmp || !work) return fail("null buffer passed to the typed sort");
-    if ((reinterpret_cast<uintptr_t>(keys) | reinterpret_cast<uintptr_t>(tmp) | reinterpret_cast<uintptr_t>(work)) & 15u)
-        return fail("sort buffers must be 16-byte aligned");
-    const int kind = t.bytes == 4 ? ADLHIP_ELEM_U32 : ADLHIP_ELEM_U64;
-    const size_t need = sort_work_bytes(d, kind, n, 8 * t.bytes, 1);
-    if (work_bytes < need) return fail("work buffer too small: %zu < %zu (adlhip_sort_typed_scratch_bytes)", work_bytes, need);
-    if (t.bytes == 4) return typed_keys_sort<uint32_t>(d, kind, t.kind, order, (uint32_t*)keys, (uint32_t*)tmp, work, work_bytes, n);
-    return typed_keys_sort<uint64_t>(d, kind, t.kind, order, (uint64_t*)keys, (uint64_t*)tmp, work, work_bytes, n);
-}
-
-int adlhip_sort_pairs_typed(adlhip_device* d, int key_type, int order, void* keys, void* vals, int value_bytes, void* tmp_keys,
-                            void* tmp_vals, void* work, size_t work_bytes, size_t n)
-{
-    if (bind(d)) return ADLHIP_FAILURE;
-    KeyTypeInfo t;
-    if (key_type_info(key_type, order, &t)) return ADLHIP_FAILURE;
-    if (soa_check_widths(t.bytes, value_bytes)) return ADLHIP_FAILURE;
-    if (typed_check_n(n)) return ADLHIP_FAILURE;
-    if (n == 0) return ADLHIP_SUCCESS;
-    if (!keys || !vals || !tmp_vals || !work || (t.bytes == 8 && !tmp_keys)) return fail("null buffer passed to the typed sort");
-    if ((reinterpret_cast<uintptr_t>(keys) | reinterpret_cast<uintptr_t>(vals) | reinterpret_cast<uintptr_t>(tmp_keys) |
-         reinterpret_cast<uintptr_t>(tmp_vals) | reinterpret_cast<uintptr_t>(work)) & 15u)
-        return fail("sort buffers must be 16-byte aligned");
-    const size_t need = soa_wide_layout(d, n).total;
-    if (work_bytes < need) return fail("work buffer too small: %zu < %zu (adlhip_sort_typed_scratch_bytes)", work_bytes, need);
-#define ADLHIP_TP(K_, V_) return typed_pairs_sort<K_, V_>(d, t.kind, order, (K_*)keys, (V_*)vals, (K_*)tmp_keys, (V_*)tmp_vals, work, n)
-    if (t.bytes == 4) {
-        if (value_bytes == 4) ADLHIP_TP(uint32_t, uint32_t);
-        if (value_bytes == 8) ADLHIP_TP(uint32_t, uint64_t);
-        ADLHIP_TP(uint32_t, V16);
-    }
-    if (value_bytes == 4) ADLHIP_TP(uint64_t, uint32_t);
-    if (value_bytes == 8) ADLHIP_TP(uint64_t, uint64_t);
-    ADLHIP_TP(uint64_t, V16);
-#undef ADLHIP_TP
-}
-
-int adlhip_argsort_typed(adlhip_device* d, int key_type, int order, const void* keys_in, void* keys_out, uint32_t* index_out, void* work,
-                         size_t work_bytes, size_t n)
-{
-    if (bind(d)) return ADLHIP_FAILURE;
-    KeyTypeInfo t;
-    if (key_type_info(key_type, order, &t)) return ADLHIP_FAILURE;
-    if (typed_check_n(n)) return ADLHIP_FAILURE;
-    if (n == 0) return ADLHIP_SUCCESS;
-    if (!keys_in || !index_out || !work) return fail("null buffer passed to the typed argsort");
-    if (keys_out == keys_in) return fail("argsort: d_keys_out must not be d_keys_in (adlhip_sort_pairs_typed sorts in place)");
-    if ((reinterpret_cast<uintptr_t>(keys_in) | reinterpret_cast<uintptr_t>(keys_out) | reinterpret_cast<uintptr_t>(index_out) |
-         reinterpret_cast<uintptr_t>(work)) & 15u)
-        return fail("sort buffers must be 16-byte aligned");
-    const size_t need = soa_wide_layout(d, n).total;
-    if (work_bytes < need) return fail("work buffer too small: %zu < %zu (adlhip_sort_typed_scratch_bytes)", work_bytes, need);
-    // (no values: the gather's value pointers are null, V only names an instantiation that exists anyway)
-    if (t.bytes == 4)
-        return typed_index_sort<uint32_t, uint32_t>(d, t.kind, order, (const uint32_t*)keys_in, (uint32_t*)keys_out, nullptr, nullptr, index_out, work, n);
-    return typed_index_sort<uint64_t, uint32_t>(d, t.kind, order, (const uint64_t*)keys_in, (uint64_t*)keys_out, nullptr, nullptr, index_out, work, n);
-}
-
-int adlhip_topk_scratch_bytes(adlhip_device* d, int key_type, size_t n, size_t k, size_t* work_bytes)
-{
-    if (!d) return fail("null device handle");
-    KeyTypeInfo t;
-    if (key_type_info(key_type, ADLHIP_ORDER_ASCENDING, &t)) return ADLHIP_FAILURE;
-    if (typed_check_n(n)) return ADLHIP_FAILURE;
-    if (k > n) return fail("top-k: k = %zu exceeds n = %zu", k, n);
-    if (work_bytes) *work_bytes = topk_layout(d, (size_t)t.bytes, n, k).total;
-    return ADLHIP_SUCCESS;
-}
-
-int adlhip_topk_typed(adlhip_device* d, int key_type, int order, const void* keys_in, size_t n, size_t k, void* keys_out,
-                      uint32_t* index_out, void* work, size_t work_bytes)
-{
-    if (bind(d)) return ADLHIP_FAILURE;
-    KeyTypeInfo t;
-    if (key_type_info(key_type, order, &t)) return ADLHIP_FAILURE;
-    if (typed_check_n(n)) return ADLHIP_FAILURE;
-    if (k > n) return fail("top-k: k = %zu exceeds n = %zu", k, n);
-    if (k == 0) return ADLHIP_SUCCESS;   // (n == 0 included)
-    if (!keys_out && !index_out) return fail("top-k: at least one of d_keys_out and d_index_out must be given");
-    if (!keys_in || !work) return fail("null buffer passed to top-k");
-    if ((reinterpret_cast<uintptr_t>(keys_in) | reinterpret_cast<uintptr_t>(keys_out) | reinterpret_cast<uintptr_t>(index_out) |
-         reinterpret_cast<uintptr_t>(work)) & 15u)
-        return fail("top-k buffers must be 16-byte aligned");
-    const char* in0 = static_cast<const char*>(keys_in);
-    const char* in1 = in0 + n * (size_t)t.bytes;
-    const char* ko = static_cast<const char*>(keys_out);
-    const char* io = reinterpret_cast<const char*>(index_out);
-    if ((ko && ko < in1 && in0 < ko + k * (size_t)t.bytes) || (io && io < in1 && in0 < io + k * 4))
-        return fail("top-k: the outputs must not overlap d_keys_in");
-    const size_t need = topk_layout(d, (size_t)t.bytes, n, k).total;
-    if (work_bytes < need) return fail("work buffer too small: %zu < %zu (adlhip_topk_scratch_bytes)", work_bytes, need);
-    const bool select = d->topk_algo < 0 ? k <= n / kTopkSelectMaxFraction : d->topk_algo == 1;
-#define ADLHIP_TOPK(U_)                                                                                                             \
-    return select ? topk_by_select<U_>(d, t.kind, order, (const U_*)keys_in, (U_*)keys_out, index_out, work, n, k)                  \
-                  : topk_by_sort<U_>(d, t.kind, order, (const U_*)keys_in, (U_*)keys_out, index_out, work, n, k)
-    if (t.bytes == 4) ADLHIP_TOPK(uint32_t);
-    ADLHIP_TOPK(uint64_t);
-#undef ADLHIP_TOPK
-}
-
-int adlhip_topk_rows_scratch_bytes(adlhip_device* d, int key_type, size_t rows, size_t cols, size_t k, size_t* work_bytes)
-{
-    (void)rows;   // the rows share one work buffer
-    return adlhip_topk_scratch_bytes(d, key_type, cols, k, work_bytes);
-}
-
-int adlhip_topk_rows_typed(adlhip_device* d, int key_type, int order, const void* keys_in, size_t rows, size_t cols, size_t row_stride,
-                           size_t k, void* keys_out, uint32_t* index_out, void* work, size_t work_bytes)
-{
-    if (bind(d)) return ADLHIP_FAILURE;
-    KeyTypeInfo t;
-    if (key_type_info(key_type, order, &t)) return ADLHIP_FAILURE;
-    if (typed_check_n(cols)) return ADLHIP_FAILURE;
-    if (k > cols) return fail("top-k of rows: k = %zu exceeds cols = %zu", k, cols);
-    if (row_stride < cols) return fail("top-k of rows: row_stride = %zu is below cols = %zu", row_stride, cols);
-    if (k == 0 || rows == 0) return ADLHIP_SUCCESS;   // (cols == 0 included)
-    if (!keys_out && !index_out) return fail("top-k of rows: at least one of d_keys_out and d_index_out must be given");
-    if (!keys_in || !work) return fail("null buffer passed to top-k of rows");
-    if ((reinterpret_cast<uintptr_t>(keys_in) | reinterpret_cast<uintptr_t>(keys_out) | reinterpret_cast<uintptr_t>(index_out) |
-         reinterpret_cast<uintptr_t>(work)) & 15u)
-        return fail("top-k buffers must be 16-byte aligned");
-    size_t in_elems = 0, out_elems = 0;
-    if (__builtin_mul_overflow(rows - 1, row_stride, &in_elems) || __builtin_add_overflow(in_elems, cols, &in_elems) ||
-        in_elems > (SIZE_MAX >> 4) || __builtin_mul_overflow(rows, k, &out_elems) || out_elems > (SIZE_MAX >> 4))
-        return fail("top-k of rows: rows = %zu with row_stride = %zu, k = %zu is beyond the address space", rows, row_stride, k);
-    const char* in0 = static_cast<const char*>(keys_in);
-    const char* in1 = in0 + in_elems * (size_t)t.bytes;
-    const char* ko = static_cast<const char*>(keys_out);
-    const char* io = reinterpret_cast<const char*>(index_out);
-    if ((ko && ko < in1 && in0 < ko + out_elems * (size_t)t.bytes) || (io && io < in1 && in0 < io + out_elems * 4))
-        return fail("top-k of rows: the outputs must not overlap d_keys_in");
-    const size_t need = topk_layout(d, (size_t)t.bytes, cols, k).total;
-    if (work_bytes < need) return fail("work buffer too small: %zu < %zu (adlhip_topk_rows_scratch_bytes)", work_bytes, need);
-    if (d->topk_rows_algo == 1 && k > (size_t)adlhip::kRowMaxK)
-        return fail("top-k of rows: the row kernel (\"topk.rows_algo\" = 1) serves k <= %d, got %zu", adlhip::kRowMaxK, k);
-    const bool kernel = d->topk_rows_algo < 0 ? k <= (size_t)adlhip::kRowMaxK && cols <= kTopkRowsMaxCols : d->topk_rows_algo == 1;
-#define ADLHIP_TOPK_ROWS(U_)                                                                                                        \
-    return kernel ? topk_rows_kernel_path<U_>(d, t.kind, order, (const U_*)keys_in, rows, cols, row_stride, k, (U_*)keys_out, index_out) \
-                  : topk_rows_loop<U_>(d, t.kind, order, (const U_*)keys_in, rows, cols, row_stride, k, (U_*)keys_out, index_out, work)
-    if (t.bytes == 4) ADLHIP_TOPK_ROWS(uint32_t);
-    ADLHIP_TOPK_ROWS(uint64_t);
-#undef ADLHIP_TOPK_ROWS
-}
-
-// ---- unique / run-length encode ---------------------------------------------------------------------
-
-int adlhip_run_length_encode_scratch_bytes(adlhip_device* d, int key_bytes, size_t n, size_t* work_bytes)
-{
-    if (!d) return fail("null device handle");
-    if (key_bytes != 4 && key_bytes != 8) return fail("run-length encode: key_bytes must be 4 or 8, got %d", key_bytes);
-    if (typed_check_n(n)) return ADLHIP_FAILURE;
-    if (work_bytes) *work_bytes = runs_layout(d, n).total;
-    return ADLHIP_SUCCESS;
-}
-
-int adlhip_run_length_encode(adlhip_device* d, int key_bytes, const void* keys_in, size_t n, void* unique_out, uint32_t* counts_out,
-                             uint32_t* offsets_out, uint32_t* num_runs_out, void* work, size_t work_bytes)
-{
-    if (bind(d)) return ADLHIP_FAILURE;
-    if (key_bytes != 4 && key_bytes != 8) return fail("run-length encode: key_bytes must be 4 or 8, got %d", key_bytes);
-    if (typed_check_n(n)) return ADLHIP_FAILURE;
-    if (!num_runs_out) return fail("run-length encode: d_num_runs_out is required");
-    if (reinterpret_cast<uintptr_t>(num_runs_out) & 3u) return fail("run-length encode: d_num_runs_out must be 4-byte aligned");
-    if (n == 0) {
-        HIPCHK(hipMemsetAsync(num_runs_out, 0, 4, d->stream));
-        return ADLHIP_SUCCESS;
-    }
-    const RunsOut outs[] = {{unique_out, n * (size_t)key_bytes, "d_unique_out"}, {counts_out, n * 4, "d_counts_out"},
-                            {offsets_out, (n + 1) * 4, "d_offsets_out"}};
-    if (runs_check_buffers("run-length encode", keys_in, n * (size_t)key_bytes, outs, 3, num_runs_out, work)) return ADLHIP_FAILURE;
-    const size_t need = runs_layout(d, n).total;
-    if (work_bytes < need) return fail("work buffer too small: %zu < %zu (adlhip_run_length_encode_scratch_bytes)", work_bytes, need);
-    if (key_bytes == 4)
-        return runs_stage<uint32_t>(d, (const uint32_t*)keys_in, nullptr, n, (uint32_t*)unique_out, counts_out, offsets_out, nullptr, nullptr,
-                                    num_runs_out, work);
-    return runs_stage<uint64_t>(d, (const uint64_t*)keys_in, nullptr, n, (uint64_t*)unique_out, counts_out, offsets_out, nullptr, nullptr,
-                                num_runs_out, work);
-}
-
-int adlhip_unique_scratch_bytes(adlhip_device* d, int key_type, size_t n, int want_index, size_t* work_bytes)
-{
-    if (!d) return fail("null device handle");
-    KeyTypeInfo t;
-    if (key_type_info(key_type, ADLHIP_ORDER_ASCENDING, &t)) return ADLHIP_FAILURE;
-    if (typed_check_n(n)) return ADLHIP_FAILURE;
-    const UniqueLayout L = unique_layout(d, (size_t)t.bytes, n);
-    if (work_bytes) *work_bytes = want_index ? std::max(L.keys_total, L.index_total) : L.keys_total;
-    return ADLHIP_SUCCESS;
-}
-
-int adlhip_unique_typed(adlhip_device* d, int key_type, int order, const void* keys_in, size_t n, void* unique_out, uint32_t* counts_out,
-                        uint32_t* offsets_out, uint32_t* first_index_out, uint32_t* inverse_out, uint32_t* num_unique_out, void* work,
-                        size_t work_bytes)
-{
-    if (bind(d)) return ADLHIP_FAILURE;
-    KeyTypeInfo t;
-    if (key_type_info(key_type, order, &t)) return ADLHIP_FAILURE;
-    if (typed_check_n(n)) return ADLHIP_FAILURE;
-    if (!num_unique_out) return fail("unique: d_num_unique_out is required");
-    if (reinterpret_cast<uintptr_t>(num_unique_out) & 3u) return fail("unique: d_num_unique_out must be 4-byte aligned");
-    if (n == 0) {
-        HIPCHK(hipMemsetAsync(num_unique_out, 0, 4, d->stream));
-        return ADLHIP_SUCCESS;
-    }
-    const RunsOut outs[] = {{unique_out, n * (size_t)t.bytes, "d_unique_out"}, {counts_out, n * 4, "d_counts_out"},
-                            {offsets_out, (n + 1) * 4, "d_offsets_out"}, {first_index_out, n * 4, "d_first_index_out"},
-                            {inverse_out, n * 4, "d_inverse_out"}};
-    if (runs_check_buffers("unique", keys_in, n * (size_t)t.bytes, outs, 5, num_unique_out, work)) return ADLHIP_FAILURE;
-    const bool index_path = d->unique_algo == 1 || first_index_out || inverse_out;
-    const UniqueLayout L = unique_layout(d, (size_t)t.bytes, n);
-    const size_t need = index_path ? L.index_total : L.keys_total;
-    if (work_bytes < need)
-        return fail("work buffer too small: %zu < %zu (adlhip_unique_scratch_bytes, want_index = %d)", work_bytes, need, index_path ? 1 : 0);
-    if (t.bytes == 4)
-        return unique_run<uint32_t>(d, t, order, index_path, (const uint32_t*)keys_in, n, (uint32_t*)unique_out, counts_out, offsets_out,
-                                    first_index_out, inverse_out, num_unique_out, work);
-    return unique_run<uint64_t>(d, t, order, index_path, (const uint64_t*)keys_in, n, (uint64_t*)unique_out, counts_out, offsets_out,
-                                first_index_out, inverse_out, num_unique_out, work);
-}
-
-// ---- reduce by key ----------------------------------------------------------------------------------
-
-int adlhip_reduce_runs_scratch_bytes(adlhip_device* d, int key_bytes, int value_type, size_t n, size_t* work_bytes)
-{
-    if (!d) return fail("null device handle");
-    if (key_bytes != 4 && key_bytes != 8) return fail("reduce runs: key_bytes must be 4 or 8, got %d", key_bytes);
-    ValueTypeInfo v;
-    if (reduce_value_info(value_type, ADLHIP_REDUCE_SUM, &v)) return ADLHIP_FAILURE;
-    if (typed_check_n(n)) return ADLHIP_FAILURE;
-    if (work_bytes) *work_bytes = reduce_layout(d, n).total;
-    return ADLHIP_SUCCESS;
-}
-
-#define ADLHIP_REDUCE_WIDTHS(kb_, vb_, CALL)          \
-    do {                                              \
-        if ((kb_) == 4 && (vb_) == 4) CALL(uint32_t, uint32_t); \
-        if ((kb_) == 4) CALL(uint32_t, uint64_t);     \
-        if ((vb_) == 4) CALL(uint64_t, uint32_t);     \
-        CALL(uint64_t, uint64_t);                     \
-    } while (0)
-
-int adlhip_reduce_runs(adlhip_device* d, int key_bytes, const void* keys_in, int value_type, int op, const void* vals_in, size_t n,
-                       void* unique_out, void* reduced_out, uint32_t* counts_out, uint32_t* offsets_out, uint32_t* num_runs_out, void* work,
-                       size_t work_bytes)
-{
-    if (bind(d)) return ADLHIP_FAILURE;
-    if (key_bytes != 4 && key_bytes != 8) return fail("reduce runs: key_bytes must be 4 or 8, got %d", key_bytes);
-    ValueTypeInfo v;
-    if (reduce_value_info(value_type, op, &v)) return ADLHIP_FAILURE;
-    if (typed_check_n(n)) return ADLHIP_FAILURE;
-    if (!num_runs_out) return fail("reduce runs: d_num_runs_out is required");
-    if (reinterpret_cast<uintptr_t>(num_runs_out) & 3u) return fail("reduce runs: d_num_runs_out must be 4-byte aligned");
-    if (n == 0) {
-        HIPCHK(hipMemsetAsync(num_runs_out, 0, 4, d->stream));
-        return ADLHIP_SUCCESS;
-    }
-    const RunsOut outs[] = {{unique_out, n * (size_t)key_bytes, "d_unique_out"}, {reduced_out, n * (size_t)v.bytes, "d_reduced_out"},
-                            {counts_out, n * 4, "d_counts_out"}, {offsets_out, (n + 1) * 4, "d_offsets_out"}};
-    if (reduce_check_buffers("reduce runs", keys_in, n * (size_t)key_bytes, vals_in, n * (size_t)v.bytes, outs, 4, num_runs_out, work))
-        return ADLHIP_FAILURE;
-    const size_t need = reduce_layout(d, n).total;
-    if (work_bytes < need) return fail("work buffer too small: %zu < %zu (adlhip_reduce_runs_scratch_bytes)", work_bytes, need);
-#define ADLHIP_RR(K_, W_) \
-    return reduce_stage<K_, W_>(d, (const K_*)keys_in, (const W_*)vals_in, n, v.kind, op, (K_*)unique_out, (W_*)reduced_out, counts_out, offsets_out, num_runs_out, work)
-    ADLHIP_REDUCE_WIDTHS(key_bytes, v.bytes, ADLHIP_RR);
-#undef ADLHIP_RR
-}
-
-int adlhip_reduce_by_key_scratch_bytes(adlhip_device* d, int key_type, int value_type, size_t n, size_t* work_bytes)
-{
-    if (!d) return fail("null device handle");
-    KeyTypeInfo t;
-    if (key_type_info(key_type, ADLHIP_ORDER_ASCENDING, &t)) return ADLHIP_FAILURE;
-    ValueTypeInfo v;
-    if (reduce_value_info(value_type, ADLHIP_REDUCE_SUM, &v)) return ADLHIP_FAILURE;
-    if (typed_check_n(n)) return ADLHIP_FAILURE;
-    if (work_bytes) *work_bytes = reduce_by_key_layout(d, (size_t)t.bytes, (size_t)v.bytes, n).total;
-    return ADLHIP_SUCCESS;
-}
-
-int adlhip_reduce_by_key_typed(adlhip_device* d, int key_type, int order, const void* keys_in, int value_type, int op, const void* vals_in,
-                               size_t n, void* unique_out, void* reduced_out, uint32_t* counts_out, uint32_t* offsets_out,
-                               uint32_t* num_unique_out, void* work, size_t work_bytes)
-{
-    if (bind(d)) return ADLHIP_FAILURE;
-    KeyTypeInfo t;
-    if (key_type_info(key_type, order, &t)) return ADLHIP_FAILURE;
-    ValueTypeInfo v;
-    if (reduce_value_info(value_type, op, &v)) return ADLHIP_FAILURE;
-    if (typed_check_n(n)) return ADLHIP_FAILURE;
-    if (!num_unique_out) return fail("reduce by key: d_num_unique_out is required");
-    if (reinterpret_cast<uintptr_t>(num_unique_out) & 3u) return fail("reduce by key: d_num_unique_out must be 4-byte aligned");
-    if (n == 0) {
-        HIPCHK(hipMemsetAsync(num_unique_out, 0, 4, d->stream));
-        return ADLHIP_SUCCESS;
-    }
-    const RunsOut outs[] = {{unique_out, n * (size_t)t.bytes, "d_unique_out"}, {reduced_out, n * (size_t)v.bytes, "d_reduced_out"},
-                            {counts_out, n * 4, "d_counts_out"}, {offsets_out, (n + 1) * 4, "d_offsets_out"}};
-    if (reduce_check_buffers("reduce by key", keys_in, n * (size_t)t.bytes, vals_in, n * (size_t)v.bytes, outs, 4, num_unique_out, work))
-        return ADLHIP_FAILURE;
-    const size_t need = reduce_by_key_layout(d, (size_t)t.bytes, (size_t)v.bytes, n).total;
-    if (work_bytes < need) return fail("work buffer too small: %zu < %zu (adlhip_reduce_by_key_scratch_bytes)", work_bytes, need);
-#define ADLHIP_RBK(K_, W_) \
-    return reduce_by_key_run<K_, W_>(d, t, order, (const K_*)keys_in, (const W_*)vals_in, n, v.kind, op, (K_*)unique_out, (W_*)reduced_out, counts_out, offsets_out, num_unique_out, work)
-    ADLHIP_REDUCE_WIDTHS(t.bytes, v.bytes, ADLHIP_RBK);
-#undef ADLHIP_RBK
-}
-#undef ADLHIP_REDUCE_WIDTHS
-
 int adlhip_segment_sort(adlhip_device* d, int elem_kind, void* data, const uint32_t* seg_start, size_t num_segments,
                         size_t max_segment, int low_bits)
 {
@@ -3573,19 +2509,14 @@ int adlhip_exclusive_scan_u32(adlhip_device* d, uint32_t* dst, const uint32_t* s
     uint32_t* d_total = partial + blocks;   // grand total lives behind the block sums
     int rc;
     if (blocks <= 8) {
-        rc = launch(d, "scan_single", [&] {
-            hipLaunchKernelGGL(adlhip::scan_single_kernel, dim3(1), dim3(adlhip::kScanNT), 0, d->stream, src, dst, n, d_total);
-        });
+        rc = launch_scan_single(d, "scan_single", src, dst, n, d_total);
         if (rc) return rc;
     } else {
         rc = launch(d, "scan_reduce", [&] {
             hipLaunchKernelGGL(adlhip::scan_reduce_kernel, dim3((uint32_t)blocks), dim3(adlhip::kScanNT), 0, d->stream, src, partial, n);
         });
         if (rc) return rc;
-        rc = launch(d, "scan_partials", [&] {
-            hipLaunchKernelGGL(adlhip::scan_single_kernel, dim3(1), dim3(adlhip::kScanNT), 0, d->stream,
-                               (const uint32_t*)partial, partial, blocks, d_total);
-        });
+        rc = launch_scan_single(d, "scan_partials", partial, partial, blocks, d_total);
         if (rc) return rc;
         rc = launch(d, "scan_apply", [&] {
             hipLaunchKernelGGL(adlhip::scan_apply_kernel, dim3((uint32_t)blocks), dim3(adlhip::kScanNT), 0, d->stream,
@@ -3949,3 +2880,7 @@ int adlhip_probe_read(adlhip_device* d, const void* src, size_t bytes, void* sin
 }
 
 }  // extern "C"
+
+#ifdef ADLHIP_SINGLE_TU
+#include "primitives.hip"
+#endif

@@ -1,8 +1,8 @@
 // kernels_select.hip -- the device code of the top-k selection (select_kernels.hpp) for every key type and order, instantiated here so
-// that it compiles beside adlhip.hip (see kernels_perdigit.hip).
+// that it compiles beside primitives.hip (see kernels_perdigit.hip).
 #include <hip/hip_runtime.h>
 
-#define ADLHIP_KERNEL static   // the headers' non-template kernels belong to adlhip.hip
+#define ADLHIP_KERNEL static   // the headers' non-template kernels belong to primitives.hip
 #include "select_kernels.hpp"
 
 #define X(...) template __global__ __VA_ARGS__;

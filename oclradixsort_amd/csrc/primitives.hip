@@ -1,0 +1,890 @@
+// primitives.hip -- the host side of what is built on top of the sorts: typed keys and argsort, top-k, row-wise top-k, unique /
+// run-length encode, reduce by key.  No reference counterpart.  It reaches the sorts through adlhip_internal.hpp alone (sort_elements,
+// sort_work_bytes, soa_wide_layout) and never sees their kernels.
+#include "adlhip_internal.hpp"
+
+#include <algorithm>
+#include <initializer_list>
+
+// non-template kernels of the headers: runs_counts_kernel (unique_kernels.hpp) belongs to this unit, soa_repack_high_kernel
+// (soa_wide_kernels.hpp, which typed_kernels.hpp builds on) to adlhip.hip.  A kernel is emitted whether it is launched or not, a static
+// one too, so here that one becomes a template that nothing instantiates
+#undef ADLHIP_KERNEL
+#define ADLHIP_KERNEL template <int = 0>
+#include "typed_kernels.hpp"
+#undef ADLHIP_KERNEL
+#define ADLHIP_KERNEL
+#include "select_kernels.hpp"
+#include "toprows_kernels.hpp"
+#include "unique_kernels.hpp"
+#include "reduce_kernels.hpp"
+
+// instantiated in kernels_select.hip / kernels_toprows.hip / kernels_unique.hip / kernels_reduce.hip; here they are only declared
+#ifndef ADLHIP_SINGLE_TU
+#define X(...) extern template __global__ __VA_ARGS__;
+#include "select_kernels.inc"
+#include "toprows_kernels.inc"
+#include "unique_kernels.inc"
+#include "reduce_kernels.inc"
+#undef X
+#endif
+
+using namespace adlhip_internal;
+
+namespace {
+// ---- what the entry points share ------------------------------------------------------------------------------------------------
+struct TypeInfo {
+    int bytes, kind;   // kind: adlhip::kKeyUnsigned / kKeySigned / kKeyFloat
+};
+// ADLHIP_KEY_* as (bytes, kind); `name` is the parameter that carries it
+int type_info(const char* name, int type, TypeInfo* out)
+{
+    if (type < ADLHIP_KEY_U32 || type > ADLHIP_KEY_F64) return fail("%s must be one of ADLHIP_KEY_U32 .. ADLHIP_KEY_F64 (0..5), got %d", name, type);
+    out->bytes = type < ADLHIP_KEY_U64 ? 4 : 8;
+    out->kind = type % 3;
+    return ADLHIP_SUCCESS;
+}
+int key_type_info(int key_type, int order, TypeInfo* out)
+{
+    if (type_info("key_type", key_type, out)) return ADLHIP_FAILURE;
+    if (order != ADLHIP_ORDER_ASCENDING && order != ADLHIP_ORDER_DESCENDING)
+        return fail("order must be ADLHIP_ORDER_ASCENDING (0) or ADLHIP_ORDER_DESCENDING (1), got %d", order);
+    return ADLHIP_SUCCESS;
+}
+int reduce_value_info(int value_type, int op, TypeInfo* out)
+{
+    if (type_info("value_type", value_type, out)) return ADLHIP_FAILURE;
+    if (op != ADLHIP_REDUCE_SUM && op != ADLHIP_REDUCE_MIN && op != ADLHIP_REDUCE_MAX)
+        return fail("op must be ADLHIP_REDUCE_SUM (0), ADLHIP_REDUCE_MIN (1) or ADLHIP_REDUCE_MAX (2), got %d", op);
+    return ADLHIP_SUCCESS;
+}
+int typed_check_n(size_t n)
+{
+    if (n > kMaxElems) return fail("n = %zu exceeds the supported maximum %zu", n, (size_t)kMaxElems);   // (< 2^32: indices fit a dword)
+    return ADLHIP_SUCCESS;
+}
+
+int check_aligned16(const char* what, std::initializer_list<const void*> ptrs)
+{
+    uintptr_t bits = 0;
+    for (const void* p : ptrs) bits |= reinterpret_cast<uintptr_t>(p);
+    return (bits & 15u) ? fail("%s buffers must be 16-byte aligned", what) : ADLHIP_SUCCESS;
+}
+
+// do [p, p + bytes) and [q, q + qbytes) share a byte?  A null p shares none.
+bool overlaps(const void* p, size_t bytes, const void* q, size_t qbytes)
+{
+    const char* a = static_cast<const char*>(p);
+    const char* b = static_cast<const char*>(q);
+    return a && a < b + qbytes && b < a + bytes;
+}
+
+// the word that takes the number of runs: required, 4-byte aligned, cleared by an empty input (the caller returns on failure or n == 0)
+int count_word(adlhip_device* d, const char* what, const char* name, uint32_t* word, size_t n)
+{
+    if (!word) return fail("%s: %s is required", what, name);
+    if (reinterpret_cast<uintptr_t>(word) & 3u) return fail("%s: %s must be 4-byte aligned", what, name);
+    if (n == 0) HIPCHK(hipMemsetAsync(word, 0, 4, d->stream));
+    return ADLHIP_SUCCESS;
+}
+
+// what the run-length, unique and reduce entry points refuse about their buffers, before anything is enqueued
+struct Buf {
+    const void* p;
+    size_t bytes;
+    const char* name;
+    bool required = true;   // (an input always is)
+};
+int check_buffers(const char* what, std::initializer_list<Buf> ins, std::initializer_list<Buf> outs, const void* count, const void* work)
+{
+    bool null = !work;
+    for (const auto& list : {ins, outs})
+        for (const Buf& b : list) null |= b.required && !b.p;
+    if (null) return fail("null buffer passed to %s", what);
+    for (const auto& list : {ins, outs})
+        for (const Buf& b : list)
+            if (check_aligned16(what, {b.p, work})) return ADLHIP_FAILURE;
+    for (const Buf& in : ins) {
+        for (const Buf& b : outs)
+            if (overlaps(b.p, b.bytes, in.p, in.bytes)) return fail("%s: %s must not overlap %s", what, b.name, in.name);
+        if (overlaps(count, 4, in.p, in.bytes)) return fail("%s: the count word must not overlap %s", what, in.name);
+    }
+    return ADLHIP_SUCCESS;
+}
+
+// the expression ... with U_ naming uint32_t (bytes_ == 4) or uint64_t (anything else); nests for a key and a value width
+#define ADLHIP_BY_WIDTH(bytes_, U_, ...) \
+    ((bytes_) == 4 ? [&] { using U_ = uint32_t; return __VA_ARGS__; }() : [&] { using U_ = uint64_t; return __VA_ARGS__; }())
+
+// The chunk split of the run and reduce stages: every workgroup owns tiles_per_wg whole tiles (the last one what is left, at least
+// one); at most wgs_per_cu workgroups per CU, fewer when the grid knob says so.
+struct ChunkSplit {
+    uint32_t wgs, tiles, tiles_per_wg;
+};
+ChunkSplit chunk_split(const adlhip_device* d, size_t n, size_t tile, int wgs_per_cu, int grid_knob)
+{
+    const size_t tiles = (n + tile - 1) / tile;
+    size_t cap = (size_t)d->prop.multiProcessorCount * wgs_per_cu;
+    if (grid_knob > 0) cap = std::min(cap, (size_t)grid_knob);
+    const size_t tiles_per_wg = (tiles + cap - 1) / cap;
+    return ChunkSplit{(uint32_t)((tiles + tiles_per_wg - 1) / tiles_per_wg), (uint32_t)tiles, (uint32_t)tiles_per_wg};
+}
+
+// counts[r] = offsets[r + 1] - offsets[r] for the *num_out runs of n elements
+int launch_runs_counts(adlhip_device* d, const uint32_t* offsets, const uint32_t* num_out, size_t n, uint32_t* counts)
+{
+    const uint32_t cwgs = (uint32_t)((n + adlhip::kRunsCountsPerWg - 1) / adlhip::kRunsCountsPerWg);   // (at most 2^21)
+    return launch(d, "runs_counts", [&] {
+        hipLaunchKernelGGL(adlhip::runs_counts_kernel, dim3(cwgs), dim3(adlhip::kSelNT), 0, d->stream, offsets, num_out, (uint32_t)n, counts);
+    });
+}
+
+// ---- typed keys, order, argsort (typed_kernels.hpp) -------------------------------------------------------------------------------
+// calls F_<KIND, DESC>(...) for the run-time kind and order
+#define ADLHIP_TYPED_DISPATCH(kind_, desc_, CALL)                                    \
+    do {                                                                             \
+        switch ((kind_) * 2 + ((desc_) ? 1 : 0)) {                                   \
+        case 0: CALL(adlhip::kKeyUnsigned, 0); break;                                \
+        case 1: CALL(adlhip::kKeyUnsigned, 1); break;                                \
+        case 2: CALL(adlhip::kKeySigned, 0); break;                                  \
+        case 3: CALL(adlhip::kKeySigned, 1); break;                                  \
+        case 4: CALL(adlhip::kKeyFloat, 0); break;                                   \
+        default: CALL(adlhip::kKeyFloat, 1); break;                                  \
+        }                                                                            \
+    } while (0)
+
+// one streaming sweep: dst[i] = enc(src[i]) or dec(src[i]).  The identity (unsigned, ascending) launches nothing when dst is src.
+template <typename U>
+int key_codec(adlhip_device* d, int kind, int desc, bool decode, U* dst, const U* src, size_t n)
+{
+    if (kind == adlhip::kKeyUnsigned && !desc) {
+        if (dst != src) HIPCHK(hipMemcpyAsync(dst, src, n * sizeof(U), hipMemcpyDeviceToDevice, d->stream));
+        return ADLHIP_SUCCESS;
+    }
+    const size_t nvec = n / (16 / sizeof(U));
+    const uint32_t wgs = (uint32_t)std::min<size_t>(std::max<size_t>((nvec + adlhip::kSoaNT - 1) / adlhip::kSoaNT, 1),
+                                                    (size_t)d->prop.multiProcessorCount * 16);
+    return launch(d, decode ? "key_decode" : "key_encode", [&] {
+#define ADLHIP_CODEC(KIND_, DESC_)                                                                                              \
+    if (decode) hipLaunchKernelGGL((adlhip::key_codec_kernel<U, KIND_, DESC_, 1>), dim3(wgs), dim3(adlhip::kSoaNT), 0, d->stream, dst, src, n); \
+    else hipLaunchKernelGGL((adlhip::key_codec_kernel<U, KIND_, DESC_, 0>), dim3(wgs), dim3(adlhip::kSoaNT), 0, d->stream, dst, src, n)
+        ADLHIP_TYPED_DISPATCH(kind, desc, ADLHIP_CODEC);
+#undef ADLHIP_CODEC
+    });
+}
+
+// The typed sibling of soa_wide_sort: {32 encoded key bits, source index} pairs through the stable pair sort, once per key dword, one
+// gather at the end.  keys_out / vals_out / index_out: whichever the caller wants (null = not written); none of them may be keys_in
+// or vals_in when it is gathered (8-byte keys, values) -- the callers pass partner arrays and copy back.
+template <typename U, typename V>
+int typed_index_sort(adlhip_device* d, int kind, int desc, const U* keys_in, U* keys_out, const V* vals_in, V* vals_out,
+                     uint32_t* index_out, void* work, size_t n)
+{
+    const SoaWideLayout L = soa_wide_layout(d, n);
+    char* w = static_cast<char*>(work);
+    uint64_t* pa = reinterpret_cast<uint64_t*>(w + L.off_pairs_a);
+    uint64_t* pb = reinterpret_cast<uint64_t*>(w + L.off_pairs_b);
+    void* kv = w + L.off_kv;
+    const uint32_t nn = (uint32_t)n;
+    const uint32_t wgs = (uint32_t)std::min<size_t>((n + adlhip::kSoaNT - 1) / adlhip::kSoaNT, (size_t)d->prop.multiProcessorCount * 16);
+    int rc = launch(d, sizeof(U) == 4 ? "typed_pack_index_k32" : "typed_pack_index_k64", [&] {
+#define ADLHIP_PACK(KIND_, DESC_) \
+    hipLaunchKernelGGL((adlhip::typed_pack_index_kernel<U, KIND_, DESC_>), dim3(wgs), dim3(adlhip::kSoaNT), 0, d->stream, keys_in, pa, nn)
+        ADLHIP_TYPED_DISPATCH(kind, desc, ADLHIP_PACK);
+#undef ADLHIP_PACK
+    });
+    if (rc) return rc;
+    rc = sort_elements(d, ADLHIP_ELEM_KV32, pa, pb, kv, L.kv_bytes, n, 32);
+    if (rc) return rc;
+    const uint64_t* sorted = pa;
+    if constexpr (sizeof(U) == 8) {   // second 32-bit digit; the sort is stable, so equal high dwords keep the order of their low dwords
+        rc = launch(d, "typed_repack_high", [&] {
+#define ADLHIP_REPACK(KIND_, DESC_) \
+    hipLaunchKernelGGL((adlhip::typed_repack_high_kernel<KIND_, DESC_>), dim3(wgs), dim3(adlhip::kSoaNT), 0, d->stream, keys_in, (const uint64_t*)pa, pb, nn)
+            ADLHIP_TYPED_DISPATCH(kind, desc, ADLHIP_REPACK);
+#undef ADLHIP_REPACK
+        });
+        if (rc) return rc;
+        rc = sort_elements(d, ADLHIP_ELEM_KV32, pb, pa, kv, L.kv_bytes, n, 32);
+        if (rc) return rc;
+        sorted = pb;
+    }
+    return launch(d, "typed_gather", [&] {
+#define ADLHIP_GATHER(KIND_, DESC_) \
+    hipLaunchKernelGGL((adlhip::typed_gather_kernel<U, V, KIND_, DESC_>), dim3(wgs), dim3(adlhip::kSoaNT), 0, d->stream, sorted, keys_in, keys_out, vals_in, vals_out, index_out, nn)
+        if constexpr (sizeof(U) == 8) ADLHIP_GATHER(adlhip::kKeyUnsigned, 0);   // 8-byte keys are fetched, not decoded
+        else ADLHIP_TYPED_DISPATCH(kind, desc, ADLHIP_GATHER);
+#undef ADLHIP_GATHER
+    });
+}
+
+// in-place pairs: gathered arrays land in the partner arrays and are copied back, as soa_wide_sort does
+template <typename U, typename V>
+int typed_pairs_sort(adlhip_device* d, int kind, int desc, U* keys, V* vals, U* tmp_keys, V* tmp_vals, void* work, size_t n)
+{
+    U* kout = sizeof(U) == 4 ? keys : tmp_keys;   // 4-byte keys are the pairs' own low dwords, decoded: keys[] is not read by the gather
+    int rc = typed_index_sort<U, V>(d, kind, desc, keys, kout, vals, tmp_vals, nullptr, work, n);
+    if (rc) return rc;
+    if (sizeof(U) == 8) HIPCHK(hipMemcpyAsync(keys, tmp_keys, n * sizeof(U), hipMemcpyDeviceToDevice, d->stream));
+    HIPCHK(hipMemcpyAsync(vals, tmp_vals, n * sizeof(V), hipMemcpyDeviceToDevice, d->stream));
+    return ADLHIP_SUCCESS;
+}
+
+// encode in place -> unsigned sort on whole keys -> decode in place.  A sort that refuses after the encode was enqueued (a work buffer
+// that does not fit the one-sweep path the knobs ask for, ...) still gets its decode: the caller's keys come back as they were.
+template <typename U>
+int typed_keys_sort(adlhip_device* d, int elem_kind, int kind, int desc, U* keys, U* tmp, void* work, size_t work_bytes, size_t n)
+{
+    int rc = key_codec<U>(d, kind, desc, false, keys, keys, n);
+    if (rc) return rc;
+    rc = sort_elements(d, elem_kind, keys, tmp, work, work_bytes, n, 8 * (int)sizeof(U));
+    if (rc) {
+        const std::string kept = adlhip_last_error();
+        (void)key_codec<U>(d, kind, desc, true, keys, keys, n);
+        adlhip_set_last_error(kept.c_str());   // the sort's message, not the decode's
+        return rc;
+    }
+    return key_codec<U>(d, kind, desc, true, keys, keys, n);
+}
+
+// ---- top-k (select_kernels.hpp) ----------------------------------------------------------------------
+// Work buffer of adlhip_topk_typed: the larger of
+//   selection   [SelState][result: k positions][X], X = the larger of
+//                 two survivor lists of n {code, position} each (codes and positions in arrays of their own), and
+//                 the finish, which runs when the lists are dead: [partner array of the position sort: k u32][gathered keys: k]
+//                 [work of the position sort / of the k-element typed pair sort, whichever is larger]
+//   fallback    [work of the n-element argsort][its sorted keys: n][its index: n u32]
+// every part 256-byte aligned.
+constexpr size_t kTopkSelectMaxFraction = 8;   // "topk.algo" = -1: selection while k <= n / 8 (unmeasured; tools/topk_bench.py)
+struct TopkLayout {
+    size_t off_result, off_x;                               // selection
+    size_t off_codes[2], off_pos[2];                        //   X as survivor lists
+    size_t off_ptmp, off_keys, off_fwork, fwork_bytes;      //   X as the finish's scratch
+    size_t off_akeys, off_aidx, awork_bytes;                // fallback (its sort's work at offset 0)
+    size_t total;
+};
+TopkLayout topk_layout(const adlhip_device* d, size_t key_bytes, size_t n, size_t k)
+{
+    TopkLayout L;
+    L.off_result = sizeof(adlhip::SelState);
+    L.off_x = L.off_result + align_up(k * 4, 256);
+    size_t o = L.off_x;
+    for (int i = 0; i < 2; ++i) {
+        L.off_codes[i] = o;
+        L.off_pos[i] = o + align_up(n * key_bytes, 256);
+        o = L.off_pos[i] + align_up(n * 4, 256);
+    }
+    const size_t lists_end = o;
+    L.off_ptmp = L.off_x;
+    L.off_keys = L.off_ptmp + align_up(k * 4, 256);
+    L.off_fwork = L.off_keys + align_up(k * key_bytes, 256);
+    L.fwork_bytes = std::max(sort_work_bytes(d, ADLHIP_ELEM_U32, k, 32, 1), soa_wide_layout(d, k).total);
+    const size_t select_total = std::max(lists_end, L.off_fwork + L.fwork_bytes);
+    L.awork_bytes = soa_wide_layout(d, n).total;
+    L.off_akeys = align_up(L.awork_bytes, 256);
+    L.off_aidx = L.off_akeys + align_up(n * key_bytes, 256);
+    L.total = std::max(select_total, L.off_aidx + align_up(n * 4, 256));
+    return L;
+}
+
+// digit `level` of the composite (code of `key_bits` bits, position of `pos_bits` bits), most significant first, 11 bits each but
+// for the last digit of either part
+adlhip::SelDigit topk_digit(int level, int key_bits, int pos_bits)
+{
+    const int key_levels = (key_bits + adlhip::kSelDigitBits - 1) / adlhip::kSelDigitBits;
+    const bool from_pos = level >= key_levels;
+    const int left = from_pos ? pos_bits - adlhip::kSelDigitBits * (level - key_levels) : key_bits - adlhip::kSelDigitBits * level;
+    if (left <= 0) return adlhip::SelDigit{0u, 0u, 0u};   // behind the last digit: everything counts as digit 0
+    const int bits = std::min(left, adlhip::kSelDigitBits);
+    return adlhip::SelDigit{from_pos ? 1u : 0u, (uint32_t)(left - bits), (1u << bits) - 1u};
+}
+
+// the composite of n positions: bits of the position part, digits in all (<= kSelMaxLevels)
+struct SelectPlan {
+    int pos_bits, levels;
+};
+SelectPlan select_plan(int key_bits, size_t n)
+{
+    int pos_bits = 1;
+    while (pos_bits < 32 && ((size_t)1 << pos_bits) < n) ++pos_bits;
+    const int digit = adlhip::kSelDigitBits;
+    return SelectPlan{pos_bits, (key_bits + digit - 1) / digit + (pos_bits + digit - 1) / digit};
+}
+
+// the full argsort into the work buffer, its first k entries to the caller
+template <typename U>
+int topk_by_sort(adlhip_device* d, int kind, int desc, const U* keys_in, U* keys_out, uint32_t* index_out, void* work, size_t n, size_t k)
+{
+    const TopkLayout L = topk_layout(d, sizeof(U), n, k);
+    char* w = static_cast<char*>(work);
+    U* akeys = reinterpret_cast<U*>(w + L.off_akeys);
+    uint32_t* aidx = reinterpret_cast<uint32_t*>(w + L.off_aidx);
+    const int rc = typed_index_sort<U, uint32_t>(d, kind, desc, keys_in, keys_out ? akeys : nullptr, nullptr, nullptr, aidx, work, n);
+    if (rc) return rc;
+    if (keys_out) HIPCHK(hipMemcpyAsync(keys_out, akeys, k * sizeof(U), hipMemcpyDeviceToDevice, d->stream));
+    if (index_out) HIPCHK(hipMemcpyAsync(index_out, aidx, k * 4, hipMemcpyDeviceToDevice, d->stream));
+    return ADLHIP_SUCCESS;
+}
+
+// keys_in need not be 16-byte aligned when stage_keys is set: the two kernels that load the keys in 16-byte vectors then read a copy
+// of them in the first survivor list (dead until level 2 writes it, by which time both have run); the gather reads keys_in itself
+template <typename U>
+int topk_by_select(adlhip_device* d, int kind, int desc, const U* keys_in, U* keys_out, uint32_t* index_out, void* work, size_t n, size_t k,
+                   bool stage_keys = false)
+{
+    const TopkLayout L = topk_layout(d, sizeof(U), n, k);
+    char* w = static_cast<char*>(work);
+    adlhip::SelState* st = reinterpret_cast<adlhip::SelState*>(w);
+    uint32_t* result = reinterpret_cast<uint32_t*>(w + L.off_result);
+    U* codes[2] = {reinterpret_cast<U*>(w + L.off_codes[0]), reinterpret_cast<U*>(w + L.off_codes[1])};
+    uint32_t* pos[2] = {reinterpret_cast<uint32_t*>(w + L.off_pos[0]), reinterpret_cast<uint32_t*>(w + L.off_pos[1])};
+    const uint32_t nn = (uint32_t)n, kk = (uint32_t)k;
+    const int key_bits = 8 * (int)sizeof(U);
+    const SelectPlan sp = select_plan(key_bits, n);
+    const int pos_bits = sp.pos_bits, levels = sp.levels;
+    constexpr size_t tile = (size_t)adlhip::kSelNT * adlhip::kSelVecs * (16 / sizeof(U));
+    const uint32_t wgs = (uint32_t)std::min<size_t>((n + tile - 1) / tile, (size_t)d->prop.multiProcessorCount * 8);
+
+    HIPCHK(hipMemsetAsync(st, 0, sizeof(adlhip::SelState), d->stream));   // the starting state, whatever the buffer held
+    const U* keys_vec = keys_in;
+    if (stage_keys) {
+        HIPCHK(hipMemcpyAsync(codes[0], keys_in, n * sizeof(U), hipMemcpyDeviceToDevice, d->stream));
+        keys_vec = codes[0];
+    }
+    int rc = launch(d, "select_hist", [&] {
+#define ADLHIP_SELH(KIND_, DESC_) \
+    hipLaunchKernelGGL((adlhip::select_hist_kernel<U, KIND_, DESC_>), dim3(wgs), dim3(adlhip::kSelNT), 0, d->stream, keys_vec, nn, st, topk_digit(0, key_bits, pos_bits))
+        ADLHIP_TYPED_DISPATCH(kind, desc, ADLHIP_SELH);
+#undef ADLHIP_SELH
+    });
+    if (rc) return rc;
+    rc = launch(d, "select_filter_first", [&] {
+#define ADLHIP_SELF(KIND_, DESC_)                                                                                                   \
+    hipLaunchKernelGGL((adlhip::select_filter_kernel<U, KIND_, DESC_, 1>), dim3(wgs), dim3(adlhip::kSelNT), 0, d->stream, keys_vec, \
+                       (const uint32_t*)nullptr, codes[1], pos[1], result, st, 1u, nn, kk, topk_digit(0, key_bits, pos_bits),       \
+                       topk_digit(1, key_bits, pos_bits))
+        ADLHIP_TYPED_DISPATCH(kind, desc, ADLHIP_SELF);
+#undef ADLHIP_SELF
+    });
+    if (rc) return rc;
+    for (int lv = 2; lv <= levels; ++lv) {   // the worst case; a level behind the one that completed the selection leaves at once
+        rc = launch(d, "select_filter", [&] {
+            hipLaunchKernelGGL((adlhip::select_filter_kernel<U, 0, 0, 0>), dim3(wgs), dim3(adlhip::kSelNT), 0, d->stream,
+                               (const U*)codes[(lv - 1) & 1], (const uint32_t*)pos[(lv - 1) & 1], codes[lv & 1], pos[lv & 1], result, st,
+                               (uint32_t)lv, nn, kk, topk_digit(lv - 1, key_bits, pos_bits), topk_digit(lv, key_bits, pos_bits));
+        });
+        if (rc) return rc;
+    }
+
+    // finish: the k positions ascending, their keys, then the stable typed pair sort of (key, position) -- stability and ascending
+    // positions give the tie order of the argsort
+    uint32_t* ptmp = reinterpret_cast<uint32_t*>(w + L.off_ptmp);
+    U* gkeys = reinterpret_cast<U*>(w + L.off_keys);
+    void* fwork = w + L.off_fwork;
+    rc = sort_elements(d, ADLHIP_ELEM_U32, result, ptmp, fwork, L.fwork_bytes, k, 32);
+    if (rc) return rc;
+    const uint32_t gwgs = (uint32_t)std::min<size_t>((k + adlhip::kSelNT - 1) / adlhip::kSelNT, (size_t)d->prop.multiProcessorCount * 16);
+    rc = launch(d, "select_gather", [&] {
+        hipLaunchKernelGGL((adlhip::select_gather_kernel<U>), dim3(gwgs), dim3(adlhip::kSelNT), 0, d->stream, keys_in, (const uint32_t*)result,
+                           gkeys, kk);
+    });
+    if (rc) return rc;
+    return typed_index_sort<U, uint32_t>(d, kind, desc, gkeys, keys_out, index_out ? result : nullptr, index_out, nullptr, fwork, k);
+}
+
+// ---- row-wise top-k (toprows_kernels.hpp) ---------------------------------------------------------------
+// "topk.rows_algo" = -1: the row kernel while k <= kRowMaxK and cols <= kTopkRowsMaxCols.  One workgroup streaming a very long row
+// loses to the per-row loop, which puts the whole device on each row; where has NOT been measured (tools/topk_rows_bench.py measures
+// it): 256 Ki is a placeholder, as kTopkSelectMaxFraction is.
+constexpr size_t kTopkRowsMaxCols = size_t(256) << 10;
+constexpr int kTopkRowsWgsPerCu = 4;   // default grid of the row kernel per CU (its LDS admits 3 workgroups of 4-byte keys, 2 of 8-byte keys)
+
+// the per-row loop: `rows` 1-D top-k calls on the shared work buffer, in stream order
+template <typename U>
+int topk_rows_loop(adlhip_device* d, int kind, int desc, const U* keys_in, size_t rows, size_t cols, size_t row_stride, size_t k,
+                   U* keys_out, uint32_t* index_out, void* work)
+{
+    const bool select = d->topk_algo < 0 ? k <= cols / kTopkSelectMaxFraction : d->topk_algo == 1;
+    for (size_t r = 0; r < rows; ++r) {
+        const U* row = keys_in + r * row_stride;
+        U* ko = keys_out ? keys_out + r * k : nullptr;
+        uint32_t* io = index_out ? index_out + r * k : nullptr;
+        // (the selection loads its keys in 16-byte vectors; a row that starts elsewhere is staged.  The argsort reads key by key.)
+        const int rc = select ? topk_by_select<U>(d, kind, desc, row, ko, io, work, cols, k, (reinterpret_cast<uintptr_t>(row) & 15u) != 0)
+                              : topk_by_sort<U>(d, kind, desc, row, ko, io, work, cols, k);
+        if (rc) return rc;
+    }
+    return ADLHIP_SUCCESS;
+}
+
+template <typename U>
+int topk_rows_kernel_path(adlhip_device* d, int kind, int desc, const U* keys_in, size_t rows, size_t cols, size_t row_stride, size_t k,
+                          U* keys_out, uint32_t* index_out)
+{
+    adlhip::RowPlan plan;
+    const int key_bits = 8 * (int)sizeof(U);
+    const SelectPlan sp = select_plan(key_bits, cols);
+    plan.levels = (uint32_t)sp.levels;
+    for (int lv = 0; lv < adlhip::kSelMaxLevels; ++lv) plan.d[lv] = topk_digit(lv, key_bits, sp.pos_bits);
+    const size_t cap = d->topk_rows_grid > 0 ? (size_t)d->topk_rows_grid : (size_t)d->prop.multiProcessorCount * kTopkRowsWgsPerCu;
+    const uint32_t wgs = (uint32_t)std::min(rows, cap);
+    return launch(d, sizeof(U) == 4 ? "topk_rows_k32" : "topk_rows_k64", [&] {
+#define ADLHIP_ROWS(KIND_, DESC_)                                                                                                   \
+    hipLaunchKernelGGL((adlhip::topk_rows_kernel<U, KIND_, DESC_>), dim3(wgs), dim3(adlhip::kSelNT), 0, d->stream, keys_in, rows,  \
+                       (uint32_t)cols, row_stride, (uint32_t)k, keys_out, index_out, plan)
+        ADLHIP_TYPED_DISPATCH(kind, desc, ADLHIP_ROWS);
+#undef ADLHIP_ROWS
+    });
+}
+
+// ---- unique / run-length encode (unique_kernels.hpp) ------------------------------------------------------
+// Work of the run stage: [chunk head counts: one u32 per workgroup of the largest grid][offsets: n + 1 u32, used when the caller wants
+// counts but passes no offsets], each rounded up to 256 bytes.
+constexpr int kUniqueWgsPerCu = 4;   // grid of the run stage per CU at most ("debug.unique_grid" lowers it)
+struct RunsLayout {
+    size_t off_offsets, total;
+};
+RunsLayout runs_layout(const adlhip_device* d, size_t n)
+{
+    RunsLayout L;
+    L.off_offsets = align_up((size_t)d->prop.multiProcessorCount * kUniqueWgsPerCu * 4, 256);
+    L.total = L.off_offsets + align_up((n + 1) * 4, 256);
+    return L;
+}
+
+// Work of adlhip_unique_typed: [run stage][S: the sorted keys, n][the sort's own buffers]
+//   keys path   [tmp: the sort's partner array, n keys][work of the typed keys sort]
+//   index path  [P: the argsort's index, n u32][work of the argsort]
+struct UniqueLayout {
+    size_t off_sorted, off_tmp, off_swork, swork_bytes, keys_total;   // keys path
+    size_t off_perm, off_awork, awork_bytes, index_total;             // index path
+};
+UniqueLayout unique_layout(const adlhip_device* d, size_t key_bytes, size_t n)
+{
+    UniqueLayout L;
+    L.off_sorted = runs_layout(d, n).total;
+    const size_t behind = L.off_sorted + align_up(n * key_bytes, 256);
+    L.off_tmp = behind;
+    L.off_swork = L.off_tmp + align_up(n * key_bytes, 256);
+    L.swork_bytes = sort_work_bytes(d, key_bytes == 4 ? ADLHIP_ELEM_U32 : ADLHIP_ELEM_U64, n, 8 * (int)key_bytes, 1);
+    L.keys_total = L.off_swork + align_up(L.swork_bytes, 256);
+    L.off_perm = behind;
+    L.off_awork = L.off_perm + align_up(n * 4, 256);
+    L.awork_bytes = soa_wide_layout(d, n).total;
+    L.index_total = L.off_awork + align_up(L.awork_bytes, 256);
+    return L;
+}
+
+// the run stage on n > 0 grouped keys; perm (null or the argsort's index) feeds first_index and inverse
+template <typename U>
+int runs_stage(adlhip_device* d, const U* keys, const uint32_t* perm, size_t n, U* unique_out, uint32_t* counts, uint32_t* offsets,
+               uint32_t* first_index, uint32_t* inverse, uint32_t* num_out, void* work)
+{
+    const RunsLayout L = runs_layout(d, n);
+    char* w = static_cast<char*>(work);
+    uint32_t* chunk = reinterpret_cast<uint32_t*>(w);
+    if (counts && !offsets) offsets = reinterpret_cast<uint32_t*>(w + L.off_offsets);
+    const ChunkSplit cs = chunk_split(d, n, (size_t)adlhip::kSelNT * adlhip::kSelVecs * (16 / sizeof(U)), kUniqueWgsPerCu, d->unique_grid);
+    const uint32_t wgs = cs.wgs, nn = (uint32_t)n, nt = cs.tiles, tpw = cs.tiles_per_wg;
+    int rc = launch(d, sizeof(U) == 4 ? "runs_count_k32" : "runs_count_k64", [&] {
+        hipLaunchKernelGGL((adlhip::runs_count_kernel<U>), dim3(wgs), dim3(adlhip::kSelNT), 0, d->stream, keys, nn, nt, tpw, chunk);
+    });
+    if (rc) return rc;
+    rc = launch_scan_single(d, "runs_scan", chunk, chunk, wgs, num_out);   // in place; the total is the number of runs
+    if (rc) return rc;
+    rc = launch(d, sizeof(U) == 4 ? "runs_emit_k32" : "runs_emit_k64", [&] {
+        if (perm)
+            hipLaunchKernelGGL((adlhip::runs_emit_kernel<U, 1>), dim3(wgs), dim3(adlhip::kSelNT), 0, d->stream, keys, perm, nn, nt, tpw,
+                               (const uint32_t*)chunk, unique_out, offsets, first_index, inverse);
+        else
+            hipLaunchKernelGGL((adlhip::runs_emit_kernel<U, 0>), dim3(wgs), dim3(adlhip::kSelNT), 0, d->stream, keys, (const uint32_t*)nullptr, nn,
+                               nt, tpw, (const uint32_t*)chunk, unique_out, offsets, (uint32_t*)nullptr, (uint32_t*)nullptr);
+    });
+    if (rc || !counts) return rc;
+    return launch_runs_counts(d, offsets, num_out, n, counts);
+}
+
+// sort (keys path: a copy of the keys, in place; index path: the argsort, which also gives P), then the run stage
+template <typename U>
+int unique_run(adlhip_device* d, const TypeInfo& t, int order, bool index_path, const U* keys_in, size_t n, U* unique_out,
+                      uint32_t* counts, uint32_t* offsets, uint32_t* first_index, uint32_t* inverse, uint32_t* num_out, void* work)
+{
+    const UniqueLayout L = unique_layout(d, sizeof(U), n);
+    char* w = static_cast<char*>(work);
+    U* sorted = reinterpret_cast<U*>(w + L.off_sorted);
+    if (index_path) {
+        uint32_t* perm = reinterpret_cast<uint32_t*>(w + L.off_perm);
+        const int rc = typed_index_sort<U, uint32_t>(d, t.kind, order, keys_in, sorted, nullptr, nullptr, perm, w + L.off_awork, n);
+        if (rc) return rc;
+        return runs_stage<U>(d, sorted, perm, n, unique_out, counts, offsets, first_index, inverse, num_out, work);
+    }
+    HIPCHK(hipMemcpyAsync(sorted, keys_in, n * sizeof(U), hipMemcpyDeviceToDevice, d->stream));
+    const int rc = typed_keys_sort<U>(d, sizeof(U) == 4 ? ADLHIP_ELEM_U32 : ADLHIP_ELEM_U64, t.kind, order, sorted, reinterpret_cast<U*>(w + L.off_tmp),
+                                      w + L.off_swork, L.swork_bytes, n);
+    if (rc) return rc;
+    return runs_stage<U>(d, sorted, nullptr, n, unique_out, counts, offsets, nullptr, nullptr, num_out, work);
+}
+
+// ---- reduce by key (reduce_kernels.hpp) --------------------------------------------------------------------
+// Work of the reduce stage, per workgroup of the largest grid: [head counts: u32][head flags: u32][tail aggregates: 8 bytes][carries: 8
+// bytes], then [offsets: n + 1 u32, used when the caller wants counts but passes no offsets], each rounded up to 256 bytes.
+constexpr int kReduceWgsPerCu = 4;   // grid of the reduce stage per CU at most ("debug.reduce_grid" lowers it)
+struct ReduceLayout {
+    size_t off_flag, off_agg, off_carry, off_offsets, total;
+};
+ReduceLayout reduce_layout(const adlhip_device* d, size_t n)
+{
+    const size_t cap = (size_t)d->prop.multiProcessorCount * kReduceWgsPerCu;
+    ReduceLayout L;
+    L.off_flag = align_up(cap * 4, 256);
+    L.off_agg = L.off_flag + align_up(cap * 4, 256);
+    L.off_carry = L.off_agg + align_up(cap * 8, 256);
+    L.off_offsets = L.off_carry + align_up(cap * 8, 256);
+    L.total = L.off_offsets + align_up((n + 1) * 4, 256);
+    return L;
+}
+
+// Work of adlhip_reduce_by_key_typed: [reduce stage][the sorted keys, n][the permuted values, n][work of the typed pairs sort]
+struct ReduceByKeyLayout {
+    size_t off_keys, off_vals, off_swork, total;
+};
+ReduceByKeyLayout reduce_by_key_layout(const adlhip_device* d, size_t key_bytes, size_t value_bytes, size_t n)
+{
+    ReduceByKeyLayout L;
+    L.off_keys = reduce_layout(d, n).total;
+    L.off_vals = L.off_keys + align_up(n * key_bytes, 256);
+    L.off_swork = L.off_vals + align_up(n * value_bytes, 256);
+    L.total = L.off_swork + align_up(soa_wide_layout(d, n).total, 256);
+    return L;
+}
+
+// the reduce stage on n > 0 grouped keys and their values
+template <typename K, typename W, int OP>
+int reduce_stage_op(adlhip_device* d, const K* keys, const W* vals, size_t n, adlhip::RedCodec codec, K* unique_out, W* reduced_out,
+                    uint32_t* counts, uint32_t* offsets, uint32_t* num_out, void* work)
+{
+    const ReduceLayout L = reduce_layout(d, n);
+    char* w = static_cast<char*>(work);
+    uint32_t* heads = reinterpret_cast<uint32_t*>(w);
+    uint32_t* flag = reinterpret_cast<uint32_t*>(w + L.off_flag);
+    W* agg = reinterpret_cast<W*>(w + L.off_agg);
+    W* carry = reinterpret_cast<W*>(w + L.off_carry);
+    if (counts && !offsets) offsets = reinterpret_cast<uint32_t*>(w + L.off_offsets);
+    const ChunkSplit cs = chunk_split(d, n, (size_t)adlhip::kRedTile, kReduceWgsPerCu, d->reduce_grid);
+    const uint32_t wgs = cs.wgs, nn = (uint32_t)n, nt = cs.tiles, tpw = cs.tiles_per_wg;
+    static const char* const kOpName[3] = {"sum", "fsum", "max"};
+    const std::string kv = "_k" + std::to_string(8 * sizeof(K)) + "v" + std::to_string(8 * sizeof(W));
+    int rc = launch(d, intern(std::string("reduce_partial_") + kOpName[OP] + kv), [&] {
+        hipLaunchKernelGGL((adlhip::reduce_partial_kernel<K, W, OP>), dim3(wgs), dim3(adlhip::kSelNT), 0, d->stream, keys, vals, nn, nt, tpw, codec,
+                           heads, flag, agg);
+    });
+    if (rc) return rc;
+    rc = launch(d, intern(std::string("reduce_carry_") + kOpName[OP] + "_v" + std::to_string(8 * sizeof(W))), [&] {   // the head counts in place; their total is the number of runs
+        hipLaunchKernelGGL((adlhip::reduce_carry_kernel<W, OP>), dim3(1), dim3(adlhip::kSelNT), 0, d->stream, heads, (const uint32_t*)flag,
+                           (const W*)agg, carry, wgs, num_out);
+    });
+    if (rc) return rc;
+    rc = launch(d, intern(std::string("reduce_emit_") + kOpName[OP] + kv), [&] {
+        hipLaunchKernelGGL((adlhip::reduce_emit_kernel<K, W, OP>), dim3(wgs), dim3(adlhip::kSelNT), 0, d->stream, keys, vals, nn, nt, tpw, codec,
+                           (const uint32_t*)heads, (const W*)carry, unique_out, reduced_out, offsets);
+    });
+    if (rc || !counts) return rc;
+    return launch_runs_counts(d, offsets, num_out, n, counts);
+}
+
+// the kernel's operator from (op, the value's kind): wrapping sum, float sum, or max on codes (min: complemented codes)
+template <typename K, typename W>
+int reduce_stage(adlhip_device* d, const K* keys, const W* vals, size_t n, int value_kind, int op, K* unique_out, W* reduced_out,
+                 uint32_t* counts, uint32_t* offsets, uint32_t* num_out, void* work)
+{
+    adlhip::RedCodec codec = {(uint32_t)value_kind, op == ADLHIP_REDUCE_MIN ? 1u : 0u};
+    if (op != ADLHIP_REDUCE_SUM)
+        return reduce_stage_op<K, W, adlhip::kRedMax>(d, keys, vals, n, codec, unique_out, reduced_out, counts, offsets, num_out, work);
+    if (value_kind == adlhip::kKeyFloat)
+        return reduce_stage_op<K, W, adlhip::kRedFloatSum>(d, keys, vals, n, codec, unique_out, reduced_out, counts, offsets, num_out, work);
+    return reduce_stage_op<K, W, adlhip::kRedSum>(d, keys, vals, n, codec, unique_out, reduced_out, counts, offsets, num_out, work);
+}
+
+// the stable typed pairs sort from the caller's arrays into d_work (no copy: the sort's gather writes there), then the reduce stage
+template <typename K, typename W>
+int reduce_by_key_run(adlhip_device* d, const TypeInfo& t, int order, const K* keys_in, const W* vals_in, size_t n, int value_kind, int op,
+                      K* unique_out, W* reduced_out, uint32_t* counts, uint32_t* offsets, uint32_t* num_out, void* work)
+{
+    const ReduceByKeyLayout L = reduce_by_key_layout(d, sizeof(K), sizeof(W), n);
+    char* w = static_cast<char*>(work);
+    K* skeys = reinterpret_cast<K*>(w + L.off_keys);
+    W* svals = reinterpret_cast<W*>(w + L.off_vals);
+    const int rc = typed_index_sort<K, W>(d, t.kind, order, keys_in, skeys, vals_in, svals, nullptr, w + L.off_swork, n);
+    if (rc) return rc;
+    return reduce_stage<K, W>(d, skeys, svals, n, value_kind, op, unique_out, reduced_out, counts, offsets, num_out, work);
+}
+
+}  // namespace
+
+extern "C" {
+
+// ---- typed keys, order, argsort ---------------------------------------------------------------------
+static int key_codec_entry(adlhip_device* d, int key_type, int order, bool decode, void* dst, const void* src, size_t n)
+{
+    TypeInfo t;
+    if (bind(d) || key_type_info(key_type, order, &t) || typed_check_n(n)) return ADLHIP_FAILURE;
+    if (n == 0) return ADLHIP_SUCCESS;
+    if (!dst || !src) return fail("null buffer passed to the key codec");
+    if (check_aligned16("key", {dst, src})) return ADLHIP_FAILURE;
+    return ADLHIP_BY_WIDTH(t.bytes, U, key_codec<U>(d, t.kind, order, decode, (U*)dst, (const U*)src, n));
+}
+
+int adlhip_key_encode(adlhip_device* d, int key_type, int order, void* dst, const void* src, size_t n)
+{
+    return key_codec_entry(d, key_type, order, false, dst, src, n);
+}
+
+int adlhip_key_decode(adlhip_device* d, int key_type, int order, void* dst, const void* src, size_t n)
+{
+    return key_codec_entry(d, key_type, order, true, dst, src, n);
+}
+
+int adlhip_sort_typed_scratch_bytes(adlhip_device* d, int key_type, int mode, int value_bytes, size_t n, size_t* tmp_keys_bytes,
+                                    size_t* tmp_vals_bytes, size_t* work_bytes)
+{
+    if (!d) return fail("null device handle");
+    TypeInfo t;
+    if (key_type_info(key_type, ADLHIP_ORDER_ASCENDING, &t)) return ADLHIP_FAILURE;
+    if (mode < 0 || mode > 2) return fail("mode must be 0 (keys only), 1 (pairs) or 2 (argsort), got %d", mode);
+    if (mode == 1 && soa_check_widths(t.bytes, value_bytes)) return ADLHIP_FAILURE;
+    const bool partner_keys = mode == 0 || (mode == 1 && t.bytes == 8);   // (4-byte keys of pairs come out of the sorted pairs themselves)
+    if (tmp_keys_bytes) *tmp_keys_bytes = partner_keys ? align_up(n * (size_t)t.bytes, 256) : 0;
+    if (tmp_vals_bytes) *tmp_vals_bytes = mode == 1 ? align_up(n * (size_t)value_bytes, 256) : 0;
+    if (work_bytes) *work_bytes = mode ? soa_wide_layout(d, n).total : sort_work_bytes(d, t.bytes == 4 ? ADLHIP_ELEM_U32 : ADLHIP_ELEM_U64, n, 8 * t.bytes, 1);
+    return ADLHIP_SUCCESS;
+}
+
+int adlhip_sort_keys_typed(adlhip_device* d, int key_type, int order, void* keys, void* tmp, void* work, size_t work_bytes, size_t n)
+{
+    TypeInfo t;
+    if (bind(d) || key_type_info(key_type, order, &t) || typed_check_n(n)) return ADLHIP_FAILURE;
+    if (n == 0) return ADLHIP_SUCCESS;
+    if (!keys || !tmp || !work) return fail("null buffer passed to the typed sort");
+    if (check_aligned16("sort", {keys, tmp, work})) return ADLHIP_FAILURE;
+    const int kind = t.bytes == 4 ? ADLHIP_ELEM_U32 : ADLHIP_ELEM_U64;
+    const size_t need = sort_work_bytes(d, kind, n, 8 * t.bytes, 1);
+    if (work_bytes < need) return fail("work buffer too small: %zu < %zu (adlhip_sort_typed_scratch_bytes)", work_bytes, need);
+    return ADLHIP_BY_WIDTH(t.bytes, U, typed_keys_sort<U>(d, kind, t.kind, order, (U*)keys, (U*)tmp, work, work_bytes, n));
+}
+
+int adlhip_sort_pairs_typed(adlhip_device* d, int key_type, int order, void* keys, void* vals, int value_bytes, void* tmp_keys,
+                            void* tmp_vals, void* work, size_t work_bytes, size_t n)
+{
+    TypeInfo t;
+    if (bind(d) || key_type_info(key_type, order, &t) || soa_check_widths(t.bytes, value_bytes) || typed_check_n(n)) return ADLHIP_FAILURE;
+    if (n == 0) return ADLHIP_SUCCESS;
+    if (!keys || !vals || !tmp_vals || !work || (t.bytes == 8 && !tmp_keys)) return fail("null buffer passed to the typed sort");
+    if (check_aligned16("sort", {keys, vals, tmp_keys, tmp_vals, work})) return ADLHIP_FAILURE;
+    const size_t need = soa_wide_layout(d, n).total;
+    if (work_bytes < need) return fail("work buffer too small: %zu < %zu (adlhip_sort_typed_scratch_bytes)", work_bytes, need);
+#define ADLHIP_TP(K_, V_) typed_pairs_sort<K_, V_>(d, t.kind, order, (K_*)keys, (V_*)vals, (K_*)tmp_keys, (V_*)tmp_vals, work, n)
+    return ADLHIP_BY_WIDTH(t.bytes, K, value_bytes == 16 ? ADLHIP_TP(K, V16) : ADLHIP_BY_WIDTH(value_bytes, V, ADLHIP_TP(K, V)));
+#undef ADLHIP_TP
+}
+
+int adlhip_argsort_typed(adlhip_device* d, int key_type, int order, const void* keys_in, void* keys_out, uint32_t* index_out, void* work,
+                         size_t work_bytes, size_t n)
+{
+    TypeInfo t;
+    if (bind(d) || key_type_info(key_type, order, &t) || typed_check_n(n)) return ADLHIP_FAILURE;
+    if (n == 0) return ADLHIP_SUCCESS;
+    if (!keys_in || !index_out || !work) return fail("null buffer passed to the typed argsort");
+    if (keys_out == keys_in) return fail("argsort: d_keys_out must not be d_keys_in (adlhip_sort_pairs_typed sorts in place)");
+    if (check_aligned16("sort", {keys_in, keys_out, index_out, work})) return ADLHIP_FAILURE;
+    const size_t need = soa_wide_layout(d, n).total;
+    if (work_bytes < need) return fail("work buffer too small: %zu < %zu (adlhip_sort_typed_scratch_bytes)", work_bytes, need);
+    // (no values: the gather's value pointers are null, V only names an instantiation that exists anyway)
+    return ADLHIP_BY_WIDTH(t.bytes, U, typed_index_sort<U, uint32_t>(d, t.kind, order, (const U*)keys_in, (U*)keys_out, nullptr, nullptr, index_out, work, n));
+}
+
+// ---- top-k --------------------------------------------------------------------------------------------
+int adlhip_topk_scratch_bytes(adlhip_device* d, int key_type, size_t n, size_t k, size_t* work_bytes)
+{
+    if (!d) return fail("null device handle");
+    TypeInfo t;
+    if (key_type_info(key_type, ADLHIP_ORDER_ASCENDING, &t) || typed_check_n(n)) return ADLHIP_FAILURE;
+    if (k > n) return fail("top-k: k = %zu exceeds n = %zu", k, n);
+    if (work_bytes) *work_bytes = topk_layout(d, (size_t)t.bytes, n, k).total;
+    return ADLHIP_SUCCESS;
+}
+
+int adlhip_topk_typed(adlhip_device* d, int key_type, int order, const void* keys_in, size_t n, size_t k, void* keys_out,
+                      uint32_t* index_out, void* work, size_t work_bytes)
+{
+    TypeInfo t;
+    if (bind(d) || key_type_info(key_type, order, &t) || typed_check_n(n)) return ADLHIP_FAILURE;
+    if (k > n) return fail("top-k: k = %zu exceeds n = %zu", k, n);
+    if (k == 0) return ADLHIP_SUCCESS;   // (n == 0 included)
+    if (!keys_out && !index_out) return fail("top-k: at least one of d_keys_out and d_index_out must be given");
+    if (!keys_in || !work) return fail("null buffer passed to top-k");
+    if (check_aligned16("top-k", {keys_in, keys_out, index_out, work})) return ADLHIP_FAILURE;
+    const size_t in_bytes = n * (size_t)t.bytes;
+    if (overlaps(keys_out, k * (size_t)t.bytes, keys_in, in_bytes) || overlaps(index_out, k * 4, keys_in, in_bytes))
+        return fail("top-k: the outputs must not overlap d_keys_in");
+    const size_t need = topk_layout(d, (size_t)t.bytes, n, k).total;
+    if (work_bytes < need) return fail("work buffer too small: %zu < %zu (adlhip_topk_scratch_bytes)", work_bytes, need);
+    const bool select = d->topk_algo < 0 ? k <= n / kTopkSelectMaxFraction : d->topk_algo == 1;
+    return ADLHIP_BY_WIDTH(t.bytes, U, select ? topk_by_select<U>(d, t.kind, order, (const U*)keys_in, (U*)keys_out, index_out, work, n, k)
+                                              : topk_by_sort<U>(d, t.kind, order, (const U*)keys_in, (U*)keys_out, index_out, work, n, k));
+}
+
+int adlhip_topk_rows_scratch_bytes(adlhip_device* d, int key_type, size_t rows, size_t cols, size_t k, size_t* work_bytes)
+{
+    (void)rows;   // the rows share one work buffer
+    return adlhip_topk_scratch_bytes(d, key_type, cols, k, work_bytes);
+}
+
+int adlhip_topk_rows_typed(adlhip_device* d, int key_type, int order, const void* keys_in, size_t rows, size_t cols, size_t row_stride,
+                           size_t k, void* keys_out, uint32_t* index_out, void* work, size_t work_bytes)
+{
+    TypeInfo t;
+    if (bind(d) || key_type_info(key_type, order, &t) || typed_check_n(cols)) return ADLHIP_FAILURE;
+    if (k > cols) return fail("top-k of rows: k = %zu exceeds cols = %zu", k, cols);
+    if (row_stride < cols) return fail("top-k of rows: row_stride = %zu is below cols = %zu", row_stride, cols);
+    if (k == 0 || rows == 0) return ADLHIP_SUCCESS;   // (cols == 0 included)
+    if (!keys_out && !index_out) return fail("top-k of rows: at least one of d_keys_out and d_index_out must be given");
+    if (!keys_in || !work) return fail("null buffer passed to top-k of rows");
+    if (check_aligned16("top-k", {keys_in, keys_out, index_out, work})) return ADLHIP_FAILURE;
+    size_t in_elems = 0, out_elems = 0;
+    if (__builtin_mul_overflow(rows - 1, row_stride, &in_elems) || __builtin_add_overflow(in_elems, cols, &in_elems) ||
+        in_elems > (SIZE_MAX >> 4) || __builtin_mul_overflow(rows, k, &out_elems) || out_elems > (SIZE_MAX >> 4))
+        return fail("top-k of rows: rows = %zu with row_stride = %zu, k = %zu is beyond the address space", rows, row_stride, k);
+    const size_t in_bytes = in_elems * (size_t)t.bytes;
+    if (overlaps(keys_out, out_elems * (size_t)t.bytes, keys_in, in_bytes) || overlaps(index_out, out_elems * 4, keys_in, in_bytes))
+        return fail("top-k of rows: the outputs must not overlap d_keys_in");
+    const size_t need = topk_layout(d, (size_t)t.bytes, cols, k).total;
+    if (work_bytes < need) return fail("work buffer too small: %zu < %zu (adlhip_topk_rows_scratch_bytes)", work_bytes, need);
+    if (d->topk_rows_algo == 1 && k > (size_t)adlhip::kRowMaxK)
+        return fail("top-k of rows: the row kernel (\"topk.rows_algo\" = 1) serves k <= %d, got %zu", adlhip::kRowMaxK, k);
+    const bool kernel = d->topk_rows_algo < 0 ? k <= (size_t)adlhip::kRowMaxK && cols <= kTopkRowsMaxCols : d->topk_rows_algo == 1;
+    return ADLHIP_BY_WIDTH(
+        t.bytes, U, kernel ? topk_rows_kernel_path<U>(d, t.kind, order, (const U*)keys_in, rows, cols, row_stride, k, (U*)keys_out, index_out)
+                           : topk_rows_loop<U>(d, t.kind, order, (const U*)keys_in, rows, cols, row_stride, k, (U*)keys_out, index_out, work));
+}
+
+// ---- unique / run-length encode ---------------------------------------------------------------------
+static int check_key_bytes(const char* what, int key_bytes)
+{
+    if (key_bytes != 4 && key_bytes != 8) return fail("%s: key_bytes must be 4 or 8, got %d", what, key_bytes);
+    return ADLHIP_SUCCESS;
+}
+
+int adlhip_run_length_encode_scratch_bytes(adlhip_device* d, int key_bytes, size_t n, size_t* work_bytes)
+{
+    if (!d) return fail("null device handle");
+    if (check_key_bytes("run-length encode", key_bytes) || typed_check_n(n)) return ADLHIP_FAILURE;
+    if (work_bytes) *work_bytes = runs_layout(d, n).total;
+    return ADLHIP_SUCCESS;
+}
+
+int adlhip_run_length_encode(adlhip_device* d, int key_bytes, const void* keys_in, size_t n, void* unique_out, uint32_t* counts_out,
+                             uint32_t* offsets_out, uint32_t* num_runs_out, void* work, size_t work_bytes)
+{
+    if (bind(d) || check_key_bytes("run-length encode", key_bytes) || typed_check_n(n)) return ADLHIP_FAILURE;
+    if (const int rc = count_word(d, "run-length encode", "d_num_runs_out", num_runs_out, n); rc || n == 0) return rc;
+    if (check_buffers("run-length encode", {{keys_in, n * (size_t)key_bytes, "d_keys_in"}},
+                      {{unique_out, n * (size_t)key_bytes, "d_unique_out"}, {counts_out, n * 4, "d_counts_out", false},
+                       {offsets_out, (n + 1) * 4, "d_offsets_out", false}},
+                      num_runs_out, work))
+        return ADLHIP_FAILURE;
+    const size_t need = runs_layout(d, n).total;
+    if (work_bytes < need) return fail("work buffer too small: %zu < %zu (adlhip_run_length_encode_scratch_bytes)", work_bytes, need);
+    return ADLHIP_BY_WIDTH(key_bytes, U, runs_stage<U>(d, (const U*)keys_in, nullptr, n, (U*)unique_out, counts_out, offsets_out, nullptr,
+                                                       nullptr, num_runs_out, work));
+}
+
+int adlhip_unique_scratch_bytes(adlhip_device* d, int key_type, size_t n, int want_index, size_t* work_bytes)
+{
+    if (!d) return fail("null device handle");
+    TypeInfo t;
+    if (key_type_info(key_type, ADLHIP_ORDER_ASCENDING, &t) || typed_check_n(n)) return ADLHIP_FAILURE;
+    const UniqueLayout L = unique_layout(d, (size_t)t.bytes, n);
+    if (work_bytes) *work_bytes = want_index ? std::max(L.keys_total, L.index_total) : L.keys_total;
+    return ADLHIP_SUCCESS;
+}
+
+int adlhip_unique_typed(adlhip_device* d, int key_type, int order, const void* keys_in, size_t n, void* unique_out, uint32_t* counts_out,
+                        uint32_t* offsets_out, uint32_t* first_index_out, uint32_t* inverse_out, uint32_t* num_unique_out, void* work,
+                        size_t work_bytes)
+{
+    TypeInfo t;
+    if (bind(d) || key_type_info(key_type, order, &t) || typed_check_n(n)) return ADLHIP_FAILURE;
+    if (const int rc = count_word(d, "unique", "d_num_unique_out", num_unique_out, n); rc || n == 0) return rc;
+    if (check_buffers("unique", {{keys_in, n * (size_t)t.bytes, "d_keys_in"}},
+                      {{unique_out, n * (size_t)t.bytes, "d_unique_out"}, {counts_out, n * 4, "d_counts_out", false},
+                       {offsets_out, (n + 1) * 4, "d_offsets_out", false}, {first_index_out, n * 4, "d_first_index_out", false},
+                       {inverse_out, n * 4, "d_inverse_out", false}},
+                      num_unique_out, work))
+        return ADLHIP_FAILURE;
+    const bool index_path = d->unique_algo == 1 || first_index_out || inverse_out;
+    const UniqueLayout L = unique_layout(d, (size_t)t.bytes, n);
+    const size_t need = index_path ? L.index_total : L.keys_total;
+    if (work_bytes < need)
+        return fail("work buffer too small: %zu < %zu (adlhip_unique_scratch_bytes, want_index = %d)", work_bytes, need, index_path ? 1 : 0);
+    return ADLHIP_BY_WIDTH(t.bytes, U, unique_run<U>(d, t, order, index_path, (const U*)keys_in, n, (U*)unique_out, counts_out, offsets_out,
+                                                     first_index_out, inverse_out, num_unique_out, work));
+}
+
+// ---- reduce by key ----------------------------------------------------------------------------------
+int adlhip_reduce_runs_scratch_bytes(adlhip_device* d, int key_bytes, int value_type, size_t n, size_t* work_bytes)
+{
+    if (!d) return fail("null device handle");
+    TypeInfo v;
+    if (check_key_bytes("reduce runs", key_bytes) || reduce_value_info(value_type, ADLHIP_REDUCE_SUM, &v) || typed_check_n(n))
+        return ADLHIP_FAILURE;
+    if (work_bytes) *work_bytes = reduce_layout(d, n).total;
+    return ADLHIP_SUCCESS;
+}
+
+int adlhip_reduce_runs(adlhip_device* d, int key_bytes, const void* keys_in, int value_type, int op, const void* vals_in, size_t n,
+                       void* unique_out, void* reduced_out, uint32_t* counts_out, uint32_t* offsets_out, uint32_t* num_runs_out, void* work,
+                       size_t work_bytes)
+{
+    TypeInfo v;
+    if (bind(d) || check_key_bytes("reduce runs", key_bytes) || reduce_value_info(value_type, op, &v) || typed_check_n(n)) return ADLHIP_FAILURE;
+    if (const int rc = count_word(d, "reduce runs", "d_num_runs_out", num_runs_out, n); rc || n == 0) return rc;
+    if (check_buffers("reduce runs", {{keys_in, n * (size_t)key_bytes, "d_keys_in"}, {vals_in, n * (size_t)v.bytes, "d_vals_in"}},
+                      {{unique_out, n * (size_t)key_bytes, "d_unique_out"}, {reduced_out, n * (size_t)v.bytes, "d_reduced_out"},
+                       {counts_out, n * 4, "d_counts_out", false}, {offsets_out, (n + 1) * 4, "d_offsets_out", false}},
+                      num_runs_out, work))
+        return ADLHIP_FAILURE;
+    const size_t need = reduce_layout(d, n).total;
+    if (work_bytes < need) return fail("work buffer too small: %zu < %zu (adlhip_reduce_runs_scratch_bytes)", work_bytes, need);
+    return ADLHIP_BY_WIDTH(key_bytes, K, ADLHIP_BY_WIDTH(v.bytes, W, reduce_stage<K, W>(d, (const K*)keys_in, (const W*)vals_in, n, v.kind, op,
+                           (K*)unique_out, (W*)reduced_out, counts_out, offsets_out, num_runs_out, work)));
+}
+
+int adlhip_reduce_by_key_scratch_bytes(adlhip_device* d, int key_type, int value_type, size_t n, size_t* work_bytes)
+{
+    if (!d) return fail("null device handle");
+    TypeInfo t, v;
+    if (key_type_info(key_type, ADLHIP_ORDER_ASCENDING, &t) || reduce_value_info(value_type, ADLHIP_REDUCE_SUM, &v) || typed_check_n(n))
+        return ADLHIP_FAILURE;
+    if (work_bytes) *work_bytes = reduce_by_key_layout(d, (size_t)t.bytes, (size_t)v.bytes, n).total;
+    return ADLHIP_SUCCESS;
+}
+
+int adlhip_reduce_by_key_typed(adlhip_device* d, int key_type, int order, const void* keys_in, int value_type, int op, const void* vals_in,
+                               size_t n, void* unique_out, void* reduced_out, uint32_t* counts_out, uint32_t* offsets_out,
+                               uint32_t* num_unique_out, void* work, size_t work_bytes)
+{
+    TypeInfo t, v;
+    if (bind(d) || key_type_info(key_type, order, &t) || reduce_value_info(value_type, op, &v) || typed_check_n(n)) return ADLHIP_FAILURE;
+    if (const int rc = count_word(d, "reduce by key", "d_num_unique_out", num_unique_out, n); rc || n == 0) return rc;
+    if (check_buffers("reduce by key", {{keys_in, n * (size_t)t.bytes, "d_keys_in"}, {vals_in, n * (size_t)v.bytes, "d_vals_in"}},
+                      {{unique_out, n * (size_t)t.bytes, "d_unique_out"}, {reduced_out, n * (size_t)v.bytes, "d_reduced_out"},
+                       {counts_out, n * 4, "d_counts_out", false}, {offsets_out, (n + 1) * 4, "d_offsets_out", false}},
+                      num_unique_out, work))
+        return ADLHIP_FAILURE;
+    const size_t need = reduce_by_key_layout(d, (size_t)t.bytes, (size_t)v.bytes, n).total;
+    if (work_bytes < need) return fail("work buffer too small: %zu < %zu (adlhip_reduce_by_key_scratch_bytes)", work_bytes, need);
+    return ADLHIP_BY_WIDTH(t.bytes, K, ADLHIP_BY_WIDTH(v.bytes, W, reduce_by_key_run<K, W>(d, t, order, (const K*)keys_in, (const W*)vals_in, n,
+                           v.kind, op, (K*)unique_out, (W*)reduced_out, counts_out, offsets_out, num_unique_out, work)));
+}
+
+}  // extern "C"

@@ -1,5 +1,5 @@
 // reduce_kernels.inc -- the instantiations of reduce_kernels.hpp (reduce stage of reduce_runs / reduce_by_key), compiled in a
-// translation unit of their own (kernels_reduce.hip) beside adlhip.hip.  X(signature): `extern template` in adlhip.hip, explicit
+// translation unit of their own (kernels_reduce.hip) beside primitives.hip.  X(signature): `extern template` in primitives.hip, explicit
 // instantiation in kernels_reduce.hip.  Per (key width, value width): wrapping sum (signed and unsigned share it), float sum, max on
 // codes (min, and the value's kind, at run time).
 #define RED_CARRY(W, OP)                                                                                                              \

@@ -1,5 +1,5 @@
 // select_kernels.inc -- the instantiations of select_kernels.hpp (top-k selection), compiled in a translation unit of their own
-// (kernels_select.hip) beside adlhip.hip.  X(signature): `extern template` in adlhip.hip, explicit instantiation in kernels_select.hip.
+// (kernels_select.hip) beside primitives.hip.  X(signature): `extern template` in primitives.hip, explicit instantiation in kernels_select.hip.
 #define SEL_TYPED(U, KIND, DESC)                                                                                                      \
     X(void adlhip::select_hist_kernel<U, KIND, DESC>(U const*, unsigned int, adlhip::SelState*, adlhip::SelDigit))                    \
     X(void adlhip::select_filter_kernel<U, KIND, DESC, 1>(U const*, unsigned int const*, U*, unsigned int*, unsigned int*,           \

@@ -13,7 +13,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-// non-template kernels: external linkage in adlhip.hip, internal in the units that only instantiate kernel templates (radix_kernels.hpp)
+// non-template kernels: external linkage in adlhip.hip, internal in the units that only instantiate kernel templates (radix_kernels.hpp),
+// absent from primitives.hip
 #ifndef ADLHIP_KERNEL
 #define ADLHIP_KERNEL
 #endif

@@ -1,5 +1,5 @@
 // unique_kernels.inc -- the instantiations of unique_kernels.hpp (run stage of unique / run-length encode), compiled in a translation
-// unit of their own (kernels_unique.hip) beside adlhip.hip.  X(signature): `extern template` in adlhip.hip, explicit instantiation in
+// unit of their own (kernels_unique.hip) beside primitives.hip.  X(signature): `extern template` in primitives.hip, explicit instantiation in
 // kernels_unique.hip.
 #define RUNS_EMIT(U, HAS_INDEX)                                                                                                      \
     X(void adlhip::runs_emit_kernel<U, HAS_INDEX>(U const*, unsigned int const*, unsigned int, unsigned int, unsigned int,            \

@@ -3,7 +3,7 @@
 import re, subprocess, sys, os
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 src = os.path.join(root, "oclradixsort_amd", "csrc", "adlhip.hip")
-cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-w",
+cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-DADLHIP_SINGLE_TU", "-fPIC", "-shared", "-w",
        "-Rpass-analysis=kernel-resource-usage", "-o", "/tmp/libadlhip_res.so", src] + sys.argv[1:]
 out = subprocess.run(cmd, capture_output=True, text=True).stderr
 cur = None; rows = {}
