@@ -144,6 +144,20 @@ public:
     int reduceByKey(const adl::Device* device, const adl::Buffer<K>& keys, const adl::Buffer<V>& values, adl::Buffer<K>& uniqueOut,
                     adl::Buffer<V>& reducedOut, int n, int op = ADLHIP_REDUCE_SUM, bool descending = false);
 
+    // dst[i] = op (ADLHIP_REDUCE_SUM / _MIN / _MAX) over src[0 .. i] (exclusive: over src[0 .. i - 1]; dst[0] = the operator's identity
+    // pattern: zero bits, the last / first pattern of V in the ascending order of sortKeys for MIN / MAX) for the first n elements.  V:
+    // int, float, long long, double, u32, u64.  Integer sums wrap; float sums are IEEE adds in an unspecified but reproducible
+    // association; min / max follow the order of sortKeys (floats: totalOrder) and return the bits of an element; the first element
+    // comes back bit for bit.  dst may be src.  Enqueues and returns.  A TYPE_HOST device runs a plain loop, left to right
+    template <typename V>
+    void scanTyped(const adl::Device* device, const adl::Buffer<V>& src, adl::Buffer<V>& dst, int n, int op = ADLHIP_REDUCE_SUM,
+                   bool exclusive = false);
+    // scanTyped within every run of adjacent keys with identical bits (keys already grouped; A A B A is three runs): the scan starts
+    // again at every run's first element.  K and V independently of the six types.  dst may be src, not keys
+    template <typename K, typename V>
+    void scanByKey(const adl::Device* device, const adl::Buffer<K>& keys, const adl::Buffer<V>& src, adl::Buffer<V>& dst, int n,
+                   int op = ADLHIP_REDUCE_SUM, bool exclusive = false);
+
 private:
     template <typename T> int uniqueTyped(const adl::Device* device, const adl::Buffer<T>& keys, adl::Buffer<T>& uniqueOut, adl::Buffer<u32>& countsOut,
                                           int n, bool descending);

@@ -433,6 +433,53 @@ int adlhip_reduce_by_key_typed(adlhip_device* dev, int key_type, int order, cons
                                uint32_t* d_counts_out_or_null, uint32_t* d_offsets_out_or_null,
                                uint32_t* d_num_unique_out, void* d_work, size_t work_bytes);
 
+/* ---- typed scans: prefix sum, min and max, plain and by key (no reference counterpart) --------- */
+
+/* thrust's inclusive_scan / exclusive_scan and their _by_key forms; torch's cumsum / cummax / cummin (values only), which has no by-key
+ * form.  value_type is one of the six ADLHIP_KEY_* codes, used as a VALUE type; op is ADLHIP_REDUCE_SUM / _MIN / _MAX with the
+ * semantics of the reduce block above: integer sums wrap in the value's width; float sums are IEEE adds of the segment's elements only,
+ * in an association that depends on n and the launch grid alone, so the same input, device and knobs give the same bits on every call;
+ * min and max are taken in ascending totalOrder and return the bits of an element.  key_bytes is 4 or 8; a SEGMENT is a run of
+ * identical key bits -- the runs of adlhip_run_length_encode, so grouped but unsorted keys A A B A give three segments.  The plain scan
+ * is one segment.  A HEAD is the first element of a segment.
+ *
+ * Inclusive (exclusive == 0; h_init_or_null must be NULL, an init is refused): d_out[i] = op over the segment's elements up to and
+ *   including i.  A segment's first element comes back bit for bit (-0, signalling NaNs and NaN payloads included): no identity element
+ *   is ever combined with it.
+ * Exclusive (exclusive == 1): with inc[] what the inclusive call writes for the same input, device and knobs,
+ *   at a head      d_out[i] = init, bits unchanged; with h_init_or_null == NULL the operator's identity pattern: zero bits for sums, the
+ *                  last pattern of the type in ascending order for MIN (+NaN with an all-ones payload for floats, the largest
+ *                  integer), the first for MAX;
+ *   elsewhere      d_out[i] = inc[i - 1] bit for bit (NULL init), or op(init, inc[i - 1]): ONE operation, init the left operand.
+ *   h_init_or_null points to one value of the value type in HOST memory, read at call time, as adlhip_fill_pattern reads its pattern.
+ *
+ * Contract common to both entry points, as in the reduce block: n < 2^32.  The inputs are never written, except through d_out ==
+ * d_vals_in.  d_out holds n elements.  d_keys_in, d_vals_in, d_out and d_work are 16-byte aligned.  d_out may BE d_vals_in (the scan
+ * then runs in place and gives the bits of the out-of-place call); it must not overlap d_keys_in and must not partially overlap
+ * d_vals_in.  n == 0 succeeds and enqueues nothing (NULL arrays are accepted then).  A NULL or misaligned pointer, a partial overlap,
+ * an unknown key_bytes, value_type, op or exclusive, an init with an inclusive scan, and a work buffer one byte short (the message names
+ * the needed size) fail before anything is enqueued.  The calls enqueue and return: nothing data-dependent reaches the host, nothing is
+ * remembered between calls, all state lives in d_work -- whose contents on entry are arbitrary -- and the handle owns no device word
+ * of it.  No kernel of the scan stage waits on another workgroup or uses an atomic to global memory.
+ *
+ * Work bytes, every part rounded up to 256 bytes, with CUs = adlhip_info.compute_units:
+ *   W_scan = 16 CUs (one head count per workgroup of the largest grid, 4 workgroups per CU; written, not used) + 16 CUs (one "chunk has
+ *            a head" flag each) + 32 CUs (one aggregate each, 8 bytes whatever the value width) + 32 CUs (one carry each) + 256 (one
+ *            word the carry launch writes)
+ *   adlhip_scan_typed_scratch_bytes = adlhip_scan_by_key_scratch_bytes = W_scan
+ * Nothing is proportional to n: the value suffices for every n' <= n (and beyond).
+ *
+ * Three launches over tiles of 2048 elements, the reduce stage's structure: the workgroups walk their chunks and write head flag and
+ * the aggregate behind their last head; one workgroup scans these, segmented by the flags, which gives every chunk the part of its
+ * first segment that lies in front of it; the workgroups walk their chunks again with a segmented scan per tile and write every
+ * element.  The values are read twice and written once, the keys read twice. */
+int adlhip_scan_typed_scratch_bytes(adlhip_device* dev, int value_type, size_t n, size_t* work_bytes);
+int adlhip_scan_typed(adlhip_device* dev, int value_type, int op, int exclusive, const void* h_init_or_null, const void* d_vals_in,
+                      void* d_out, size_t n, void* d_work, size_t work_bytes);
+int adlhip_scan_by_key_scratch_bytes(adlhip_device* dev, int key_bytes, int value_type, size_t n, size_t* work_bytes);
+int adlhip_scan_by_key(adlhip_device* dev, int key_bytes, const void* d_keys_in, int value_type, int op, int exclusive,
+                       const void* h_init_or_null, const void* d_vals_in, void* d_out, size_t n, void* d_work, size_t work_bytes);
+
 /* ---- segments finished in LDS (no reference counterpart) ------------------------------------- */
 
 /* Sorts, stably and in place, every segment [d_seg_start[s], d_seg_start[s + 1]) of an array of u32 keys
@@ -599,6 +646,9 @@ int adlhip_generate_keys(adlhip_device* dev, int elem_kind, void* dptr, size_t n
  *   "debug.reduce_grid" workgroups the reduce stage of adlhip_reduce_runs / adlhip_reduce_by_key_typed is launched with at most (0
  *                      [default]: 4 per CU; larger values change nothing); tests set it to make few workgroups take many tiles.  Float
  *                      sums may differ in the last bits between two values of it (another association), never between two calls
+ *   "debug.scan_grid"  workgroups the scan stage of adlhip_scan_typed / adlhip_scan_by_key is launched with at most (0 [default]: 4 per
+ *                      CU; larger values change nothing); tests set it to make few workgroups take many tiles.  Float sums may differ
+ *                      in the last bits between two values of it (another association), never between two calls
  *   "sort.net_lookback" 1 [default] / 0: the LSD passes of the large sort's safety net on whole keys are look-back passes -- the
  *                      one-sweep path's histogram, tables and tile body, taken in turns by the net's resident workgroups, four
  *                      passes at a time (u64 keys: two rounds) -- instead of count -> scan -> scatter passes with per-workgroup

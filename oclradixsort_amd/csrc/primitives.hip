@@ -1,5 +1,5 @@
 // primitives.hip -- the host side of what is built on top of the sorts: typed keys and argsort, top-k, row-wise top-k, unique /
-// run-length encode, reduce by key.  No reference counterpart.  It reaches the sorts through adlhip_internal.hpp alone (sort_elements,
+// run-length encode, reduce by key, typed scans.  No reference counterpart.  It reaches the sorts through adlhip_internal.hpp alone (sort_elements,
 // sort_work_bytes, soa_wide_layout) and never sees their kernels.
 #include "adlhip_internal.hpp"
 
@@ -18,14 +18,17 @@
 #include "toprows_kernels.hpp"
 #include "unique_kernels.hpp"
 #include "reduce_kernels.hpp"
+#include "scan_kernels.hpp"
 
-// instantiated in kernels_select.hip / kernels_toprows.hip / kernels_unique.hip / kernels_reduce.hip; here they are only declared
+// instantiated in kernels_select.hip / kernels_toprows.hip / kernels_unique.hip / kernels_reduce.hip / kernels_scan.hip; here they are
+// only declared
 #ifndef ADLHIP_SINGLE_TU
 #define X(...) extern template __global__ __VA_ARGS__;
 #include "select_kernels.inc"
 #include "toprows_kernels.inc"
 #include "unique_kernels.inc"
 #include "reduce_kernels.inc"
+#include "scan_kernels.inc"
 #undef X
 #endif
 
@@ -619,6 +622,99 @@ int reduce_by_key_run(adlhip_device* d, const TypeInfo& t, int order, const K* k
     return reduce_stage<K, W>(d, skeys, svals, n, value_kind, op, unique_out, reduced_out, counts, offsets, num_out, work);
 }
 
+// ---- typed scans (scan_kernels.hpp) ---------------------------------------------------------------------------
+// Work of the scan stage, per workgroup of the largest grid: [head counts: u32, written and not used][head flags: u32][chunk
+// aggregates: 8 bytes][carries: 8 bytes], each rounded up to 256 bytes, then 256 bytes for the word reduce_carry_kernel puts its
+// number of runs in.  Nothing proportional to n.
+constexpr int kScanWgsPerCu = 4;   // grid of the scan stage per CU at most ("debug.scan_grid" lowers it)
+struct ScanLayout {
+    size_t off_flag, off_agg, off_carry, off_count, total;
+};
+ScanLayout scan_layout(const adlhip_device* d)
+{
+    const size_t cap = (size_t)d->prop.multiProcessorCount * kScanWgsPerCu;
+    ScanLayout L;
+    L.off_flag = align_up(cap * 4, 256);
+    L.off_agg = L.off_flag + align_up(cap * 4, 256);
+    L.off_carry = L.off_agg + align_up(cap * 8, 256);
+    L.off_count = L.off_carry + align_up(cap * 8, 256);
+    L.total = L.off_count + 256;
+    return L;
+}
+
+// the scan stage on n > 0 values; K = adlhip::ScanNoKey (keys null): one segment
+template <typename K, typename W, int OP>
+int scan_stage_op(adlhip_device* d, const K* keys, const W* vals, W* out, size_t n, adlhip::RedCodec codec, uint32_t mode, W init, void* work)
+{
+    constexpr bool keyed = !std::is_same<K, adlhip::ScanNoKey>::value;
+    const ScanLayout L = scan_layout(d);
+    char* w = static_cast<char*>(work);
+    uint32_t* heads = reinterpret_cast<uint32_t*>(w);
+    uint32_t* flag = reinterpret_cast<uint32_t*>(w + L.off_flag);
+    W* agg = reinterpret_cast<W*>(w + L.off_agg);
+    W* carry = reinterpret_cast<W*>(w + L.off_carry);
+    uint32_t* count = reinterpret_cast<uint32_t*>(w + L.off_count);
+    const ChunkSplit cs = chunk_split(d, n, (size_t)adlhip::kRedTile, kScanWgsPerCu, d->scan_grid);
+    const uint32_t wgs = cs.wgs, nn = (uint32_t)n, nt = cs.tiles, tpw = cs.tiles_per_wg;
+    static const char* const kOpName[3] = {"sum", "fsum", "max"};
+    const std::string kv = (keyed ? "_k" + std::to_string(8 * sizeof(K)) : std::string("_k0")) + "v" + std::to_string(8 * sizeof(W));
+    int rc = launch(d, intern(std::string("scan_partial_") + kOpName[OP] + kv), [&] {
+        if constexpr (keyed)
+            hipLaunchKernelGGL((adlhip::reduce_partial_kernel<K, W, OP>), dim3(wgs), dim3(adlhip::kSelNT), 0, d->stream, keys, vals, nn, nt, tpw,
+                               codec, heads, flag, agg);
+        else
+            hipLaunchKernelGGL((adlhip::scan_partial_kernel<W, OP>), dim3(wgs), dim3(adlhip::kSelNT), 0, d->stream, vals, nn, nt, tpw, codec,
+                               heads, flag, agg);
+    });
+    if (rc) return rc;
+    rc = launch(d, intern(std::string("scan_carry_") + kOpName[OP] + "_v" + std::to_string(8 * sizeof(W))), [&] {
+        hipLaunchKernelGGL((adlhip::reduce_carry_kernel<W, OP>), dim3(1), dim3(adlhip::kSelNT), 0, d->stream, heads, (const uint32_t*)flag,
+                           (const W*)agg, carry, wgs, count);
+    });
+    if (rc) return rc;
+    return launch(d, intern(std::string("scan_emit_") + kOpName[OP] + kv), [&] {
+        hipLaunchKernelGGL((adlhip::scan_emit_kernel<K, W, OP>), dim3(wgs), dim3(adlhip::kSelNT), 0, d->stream, keys, vals, nn, nt, tpw, codec,
+                           (const uint32_t*)flag, (const W*)agg, (const W*)carry, mode, init, out);
+    });
+}
+
+// the kernel's operator from (op, the value's kind), as reduce_stage; the init's bits from host memory
+template <typename K, typename W>
+int scan_stage(adlhip_device* d, const K* keys, const W* vals, W* out, size_t n, int value_kind, int op, int exclusive, const void* h_init,
+               void* work)
+{
+    const adlhip::RedCodec codec = {(uint32_t)value_kind, op == ADLHIP_REDUCE_MIN ? 1u : 0u};
+    const uint32_t mode = !exclusive ? adlhip::kScanInclusive : h_init ? adlhip::kScanExclusiveInit : adlhip::kScanExclusive;
+    W init = (W)0;
+    if (h_init) __builtin_memcpy(&init, h_init, sizeof(W));
+    if (op != ADLHIP_REDUCE_SUM) return scan_stage_op<K, W, adlhip::kRedMax>(d, keys, vals, out, n, codec, mode, init, work);
+    if (value_kind == adlhip::kKeyFloat) return scan_stage_op<K, W, adlhip::kRedFloatSum>(d, keys, vals, out, n, codec, mode, init, work);
+    return scan_stage_op<K, W, adlhip::kRedSum>(d, keys, vals, out, n, codec, mode, init, work);
+}
+
+// what both scan entry points refuse, before anything is enqueued; keys_in is null for the plain scan.  *done: nothing is left to do
+int scan_check(adlhip_device* d, const char* what, const char* sizer, int key_bytes, const void* keys_in, const TypeInfo& v, int exclusive,
+               const void* h_init, const void* vals_in, const void* out, size_t n, const void* work, size_t work_bytes, bool* done)
+{
+    *done = false;
+    if (exclusive != 0 && exclusive != 1) return fail("%s: exclusive must be 0 or 1, got %d", what, exclusive);
+    if (!exclusive && h_init) return fail("%s: an inclusive scan takes no init (h_init_or_null must be NULL)", what);
+    if (typed_check_n(n)) return ADLHIP_FAILURE;
+    if (n == 0) {
+        *done = true;
+        return ADLHIP_SUCCESS;
+    }
+    if ((key_bytes && !keys_in) || !vals_in || !out || !work) return fail("null buffer passed to %s", what);
+    if (check_aligned16(what, {keys_in, vals_in, out, work})) return ADLHIP_FAILURE;
+    const size_t vbytes = n * (size_t)v.bytes;
+    if (key_bytes && overlaps(out, vbytes, keys_in, n * (size_t)key_bytes)) return fail("%s: d_out must not overlap d_keys_in", what);
+    if (out != vals_in && overlaps(out, vbytes, vals_in, vbytes))
+        return fail("%s: d_out must be d_vals_in itself or not overlap it", what);
+    const size_t need = scan_layout(d).total;
+    if (work_bytes < need) return fail("work buffer too small: %zu < %zu (%s)", work_bytes, need, sizer);
+    return ADLHIP_SUCCESS;
+}
+
 }  // namespace
 
 extern "C" {
@@ -885,6 +981,51 @@ int adlhip_reduce_by_key_typed(adlhip_device* d, int key_type, int order, const 
     if (work_bytes < need) return fail("work buffer too small: %zu < %zu (adlhip_reduce_by_key_scratch_bytes)", work_bytes, need);
     return ADLHIP_BY_WIDTH(t.bytes, K, ADLHIP_BY_WIDTH(v.bytes, W, reduce_by_key_run<K, W>(d, t, order, (const K*)keys_in, (const W*)vals_in, n,
                            v.kind, op, (K*)unique_out, (W*)reduced_out, counts_out, offsets_out, num_unique_out, work)));
+}
+
+// ---- typed scans ------------------------------------------------------------------------------------
+int adlhip_scan_typed_scratch_bytes(adlhip_device* d, int value_type, size_t n, size_t* work_bytes)
+{
+    if (!d) return fail("null device handle");
+    TypeInfo v;
+    if (reduce_value_info(value_type, ADLHIP_REDUCE_SUM, &v) || typed_check_n(n)) return ADLHIP_FAILURE;
+    if (work_bytes) *work_bytes = scan_layout(d).total;
+    return ADLHIP_SUCCESS;
+}
+
+int adlhip_scan_typed(adlhip_device* d, int value_type, int op, int exclusive, const void* h_init, const void* vals_in, void* out, size_t n,
+                      void* work, size_t work_bytes)
+{
+    TypeInfo v;
+    bool done;
+    if (bind(d) || reduce_value_info(value_type, op, &v)) return ADLHIP_FAILURE;
+    if (const int rc = scan_check(d, "scan", "adlhip_scan_typed_scratch_bytes", 0, nullptr, v, exclusive, h_init, vals_in, out, n, work,
+                                  work_bytes, &done); rc || done)
+        return rc;
+    return ADLHIP_BY_WIDTH(v.bytes, W, scan_stage<adlhip::ScanNoKey, W>(d, nullptr, (const W*)vals_in, (W*)out, n, v.kind, op, exclusive, h_init, work));
+}
+
+int adlhip_scan_by_key_scratch_bytes(adlhip_device* d, int key_bytes, int value_type, size_t n, size_t* work_bytes)
+{
+    if (!d) return fail("null device handle");
+    TypeInfo v;
+    if (check_key_bytes("scan by key", key_bytes) || reduce_value_info(value_type, ADLHIP_REDUCE_SUM, &v) || typed_check_n(n))
+        return ADLHIP_FAILURE;
+    if (work_bytes) *work_bytes = scan_layout(d).total;
+    return ADLHIP_SUCCESS;
+}
+
+int adlhip_scan_by_key(adlhip_device* d, int key_bytes, const void* keys_in, int value_type, int op, int exclusive, const void* h_init,
+                       const void* vals_in, void* out, size_t n, void* work, size_t work_bytes)
+{
+    TypeInfo v;
+    bool done;
+    if (bind(d) || check_key_bytes("scan by key", key_bytes) || reduce_value_info(value_type, op, &v)) return ADLHIP_FAILURE;
+    if (const int rc = scan_check(d, "scan by key", "adlhip_scan_by_key_scratch_bytes", key_bytes, keys_in, v, exclusive, h_init, vals_in, out,
+                                  n, work, work_bytes, &done); rc || done)
+        return rc;
+    return ADLHIP_BY_WIDTH(key_bytes, K, ADLHIP_BY_WIDTH(v.bytes, W, scan_stage<K, W>(d, (const K*)keys_in, (const W*)vals_in, (W*)out, n, v.kind,
+                           op, exclusive, h_init, work)));
 }
 
 }  // extern "C"

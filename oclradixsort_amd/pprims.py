@@ -14,6 +14,8 @@
     p.runLengthEncode(device, keys, n, counts=True)        # -> UniqueResult: the runs of keys that are already grouped
     p.reduceByKey(device, keys, values, n, op="sum")       # -> ReduceResult: distinct keys in sorted order, sum / min / max of their values
     p.reduceRuns(device, keys, values, n, op="sum")        # -> ReduceResult: the same per run of keys that are already grouped
+    p.scanTyped(device, dst, src, n, op="sum")             # inclusive / exclusive prefix sum, min or max of typed values
+    p.scanByKey(device, keys, dst, src, n, op="sum")       # the same within every run of keys that are already grouped
 
 Like the reference object it owns lazily grown device scratch (m_u32WorkBuffer[0] = ping-pong data
 buffer, m_u32WorkBuffer[1] = histogram table; Pprims.h:44-45, Pprims.cpp:226-232, :332-337) and must be
@@ -455,6 +457,59 @@ class Pprims:
         """reduceByKey for keys that are already grouped (any element type of 4 or 8 bytes): one result per run of adjacent keys with
         identical bits, the runs of runLengthEncode() -> ReduceResult."""
         return self._reduce("reduceRuns", device, False, keys, values, n, op, False, counts, offsets, uniqueOut, reducedOut, countOut)
+
+    # -- typed scans, plain and by key (no reference counterpart; include/adlhip.h adlhip_scan_typed / adlhip_scan_by_key)
+    def _scan(self, what, device, keys, dst, src, n, op, exclusive, init):
+        if device is None:
+            raise AdlHipError("%s needs a device" % what)
+        if op not in REDUCE_OPS:
+            raise AdlHipError("%s: op must be 'sum', 'min' or 'max', got %r" % (what, op))
+        if keys is not None and np.dtype(keys.dtype).itemsize not in (4, 8):
+            raise AdlHipError("%s: unsupported key type %s (4 or 8 bytes)" % (what, keys.dtype))
+        vt = KEY_TYPES.get(np.dtype(src.dtype))
+        if vt is None:
+            raise AdlHipError("%s: unsupported value type %s (uint32, int32, float32, uint64, int64, float64)" % (what, src.dtype))
+        if np.dtype(dst.dtype) != np.dtype(src.dtype):
+            raise AdlHipError("%s: dst must have the values' type %s, got %s" % (what, src.dtype, dst.dtype))
+        n = int(n)
+        room = min(b.getSize() for b in (keys, dst, src) if b is not None)
+        if n < 0 or room < n:
+            raise AdlHipError("%s: n = %d outside [0, %d]" % (what, n, room))
+        if init is not None and not exclusive:
+            raise AdlHipError("%s: an inclusive scan takes no init" % what)
+        hp = None
+        if init is not None:
+            pat = np.array(init, dtype=src.dtype).reshape(1)
+            hp = pat.ctypes.data_as(ctypes.c_void_p)   # (read during the call)
+        lib = _lib.load()
+        wb = ctypes.c_size_t()
+        if keys is None:
+            check(lib.adlhip_scan_typed_scratch_bytes(device._h, vt, n, ctypes.byref(wb)), "adlhip_scan_typed_scratch_bytes")
+        else:
+            check(lib.adlhip_scan_by_key_scratch_bytes(device._h, np.dtype(keys.dtype).itemsize, vt, n, ctypes.byref(wb)),
+                  "adlhip_scan_by_key_scratch_bytes")
+        self._scratch(device, 0, wb.value)
+        if keys is None:
+            check(lib.adlhip_scan_typed(device._h, vt, REDUCE_OPS[op], 1 if exclusive else 0, hp, src.ptr(), dst.ptr(), n,
+                                        self.m_work.ptr(), self.m_work.getSize()), what)
+        else:
+            check(lib.adlhip_scan_by_key(device._h, np.dtype(keys.dtype).itemsize, keys.ptr(), vt, REDUCE_OPS[op], 1 if exclusive else 0, hp,
+                                         src.ptr(), dst.ptr(), n, self.m_work.ptr(), self.m_work.getSize()), what)
+
+    def scanTyped(self, device, dst, src, n, op="sum", exclusive=False, init=None):
+        """dst[i] = op ("sum", "min", "max") over src[0 .. i] (inclusive) or src[0 .. i - 1] (exclusive) for the first n elements;
+        uint32 / int32 / float32 / uint64 / int64 / float64, dst of src's type.  dst may be src.  Integer sums wrap; float sums are
+        IEEE adds in an unspecified but reproducible association; min / max follow the order of the typed sorts (floats: totalOrder,
+        NaNs are ordered, not propagated).  Exclusive: dst[0] = init, dst[i] = op(init, inclusive[i - 1]); without an init dst[0] is
+        the operator's identity pattern (0, the type's last / first pattern in that order) and dst[i] = inclusive[i - 1] bit for bit.
+        An inclusive scan takes no init.  `src` is left intact unless it is dst.  Enqueues and returns."""
+        self._scan("scanTyped", device, None, dst, src, n, op, exclusive, init)
+
+    def scanByKey(self, device, keys, dst, src, n, op="sum", exclusive=False, init=None):
+        """scanTyped within every run of adjacent keys with identical bits, the runs of runLengthEncode() (keys of any element type
+        of 4 or 8 bytes, already grouped): the scan starts again at every run's first element, which gets init (exclusive) or its
+        own bits (inclusive).  dst may be src, not keys."""
+        self._scan("scanByKey", device, keys, dst, src, n, op, exclusive, init)
 
     def copy(self, device, dst, src, n):
         """Pprims::copy (Pprims.cpp:31-67, commented out in the reference): first n elements of src -> dst."""

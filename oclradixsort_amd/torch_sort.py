@@ -10,6 +10,8 @@ back-end on torch's own stream.
     u, counts = s.unique_consecutive(t, return_counts=True)                      # torch.unique_consecutive(t), 1-D
     u, sums = s.reduce_by_key(keys, values, op="sum")                            # per distinct key: sum / min / max of its values
     u, sums = s.reduce_consecutive(keys, values, op="sum")                       # the same per run of adjacent equal keys
+    c = s.cumsum(t); m = s.cummax(t); m = s.cummin(t)                            # prefix sum / max / min, in t's dtype
+    r = s.scan_by_key(keys, values, op="sum", exclusive=False, init=None)        # the same within every run of adjacent equal keys
     s.close()
 
 Always out of place and always stable.  The ONE difference from `torch.sort(t, stable=True)`: floats are ordered by
@@ -268,6 +270,53 @@ class TorchSorter:
         """reduce_by_key for keys that are already grouped: one (key, reduced[, count]) per run of adjacent keys with identical bits,
         in input order -- the runs of unique_consecutive.  The same types, operators (min / max in totalOrder) and host read."""
         return self._reduce("reduce_consecutive", False, keys, values, op, False, return_counts)
+
+    def _scan(self, what, keys, values, op, exclusive, init):
+        if op not in ("sum", "min", "max"):
+            raise ValueError("TorchSorter.%s: op must be 'sum', 'min' or 'max', got %r" % (what, op))
+        if init is not None and not exclusive:
+            raise ValueError("TorchSorter.%s: an inclusive scan takes no init" % what)
+        k = self._flat_input(keys, what, True) if keys is not None else None
+        v = self._flat_input(values, what, True)
+        n = v.numel()
+        if k is not None and k.numel() != n:
+            raise ValueError("TorchSorter.%s: %d keys but %d values" % (what, k.numel(), n))
+        out = torch.empty(n, dtype=values.dtype, device=values.device)
+        if n == 0:
+            return out
+        vdt = _NP_DTYPE[values.dtype]
+        if k is None:
+            self.pprims.scanTyped(self.device, self._wrap(out, vdt), self._wrap(v, vdt), n, op=op, exclusive=bool(exclusive), init=init)
+        else:
+            self.pprims.scanByKey(self.device, self._wrap(k, _NP_DTYPE[keys.dtype]), self._wrap(out, vdt), self._wrap(v, vdt), n, op=op,
+                                  exclusive=bool(exclusive), init=init)
+        self.device.checkFault()
+        return out
+
+    def cumsum(self, t):
+        """torch.cumsum(t, 0, dtype=t.dtype) for a 1-D tensor of int32 / int64 / float32 / float64.  The result has the INPUT's dtype:
+        int32 sums wrap in 32 bits, unlike torch.cumsum(t, 0), which promotes int32 to int64.  Float sums are IEEE adds in an
+        unspecified association, the same bits on every call (torch.cumsum makes no such promise).  No host read."""
+        return self._scan("cumsum", None, t, "sum", False, None)
+
+    def cummax(self, t):
+        """The VALUES of torch.cummax(t, 0) for a 1-D tensor; no indices.  The maximum is taken in IEEE totalOrder, -NaN < -inf < ...
+        < -0 < +0 < ... < +inf < +NaN: a NaN is the largest or the smallest element by its sign and is NOT propagated as torch's
+        cummax does, and -0 is below +0; without NaN the values are torch's."""
+        return self._scan("cummax", None, t, "max", False, None)
+
+    def cummin(self, t):
+        """The VALUES of torch.cummin(t, 0) for a 1-D tensor; no indices.  totalOrder, not torch's NaN propagation, as cummax."""
+        return self._scan("cummin", None, t, "min", False, None)
+
+    def scan_by_key(self, keys, values, op="sum", exclusive=False, init=None):
+        """The scan of `values` within every run of adjacent keys with identical bits (the runs of unique_consecutive): thrust's
+        inclusive_scan_by_key / exclusive_scan_by_key, which torch does not have.  keys and values: 1-D tensors of the same length,
+        int32 / int64 / float32 / float64 each, in any combination; the result has the values' dtype (int32 sums wrap).  op "sum",
+        "min" or "max" (totalOrder, as cummax).  exclusive: a run's first element gets init -- without one the operator's identity
+        pattern: 0, the type's largest pattern in that order for "min", its smallest for "max" --, every other one op(init, the
+        inclusive result in front of it).  An inclusive scan takes no init.  No host read."""
+        return self._scan("scan_by_key", keys, values, op, exclusive, init)
 
     def sort(self, t, descending=False):
         """(values, indices) like torch.sort(t, descending=descending, stable=True); indices are int64."""

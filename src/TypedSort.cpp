@@ -4,7 +4,8 @@
 // host branches do for u32 keys (Pprims.cpp:202-212, :306-316).  Pprims::topK: adlhip_topk_typed, or a partial sort on (ordinal,
 // position) on the host.  Pprims::topKRows: adlhip_topk_rows_typed, or the same partial sort per row.  Pprims::unique:
 // adlhip_unique_typed (it waits for the count), or the runs of the host argsort.  Pprims::reduceByKey: adlhip_reduce_by_key_typed (it
-// waits for the count), or a loop over the runs of the host argsort.
+// waits for the count), or a loop over the runs of the host argsort.  Pprims::scanTyped / scanByKey: adlhip_scan_typed /
+// adlhip_scan_by_key, or a plain loop, left to right.
 #include <Tahoe/ParallelPrimitives/Pprims.h>
 
 #include <algorithm>
@@ -364,6 +365,129 @@ TAHOE_REDUCE_KEY(u32)
 TAHOE_REDUCE_KEY(u64)
 #undef TAHOE_REDUCE_KEY
 #undef TAHOE_REDUCE
+
+namespace {
+
+// what an exclusive scan without an init writes at a head: zero bits for sums, the last / first pattern of V in ascending order for
+// MIN / MAX (the inverse of ordinal() at all ones / at 0)
+template <typename V>
+inline V hostScanIdentity(int op)
+{
+    typedef typename KeyTraits<V>::Bits B;
+    const B sign = (B)1 << (8 * sizeof(B) - 1);
+    B b = 0;
+    if (op != ADLHIP_REDUCE_SUM) {
+        b = op == ADLHIP_REDUCE_MIN ? (B)~(B)0 : (B)0;   // the ordinal
+        if (KeyTraits<V>::FLOAT) b = (b & sign) ? (B)(b ^ sign) : (B)~b;
+        if (KeyTraits<V>::SIGNED) b ^= sign;
+    }
+    V v;
+    memcpy(&v, &b, sizeof(B));
+    return v;
+}
+
+// keys == 0: one segment
+template <typename K, typename V>
+void hostScan(const K* keys, const V* src, V* dst, int n, int op, bool exclusive)
+{
+    V acc = V();
+    for (int i = 0; i < n; ++i) {
+        const bool head = i == 0 || (keys && memcmp(&keys[i], &keys[i - 1], sizeof(K)) != 0);
+        V x;
+        memcpy(&x, &src[i], sizeof(V));   // (dst may be src)
+        V out = head ? hostScanIdentity<V>(op) : acc;
+        if (head) memcpy(&acc, &x, sizeof(V));   // a segment's first element keeps its bits
+        else hostReduceStep(acc, x, op);
+        if (!exclusive) out = acc;
+        memcpy(&dst[i], &out, sizeof(V));
+    }
+}
+
+}  // namespace
+
+template <typename K, typename V>
+void Pprims::scanByKey(const adl::Device* device, const adl::Buffer<K>& keys, const adl::Buffer<V>& src, adl::Buffer<V>& dst, int n, int op,
+                       bool exclusive)
+{
+    ADLASSERT(n >= 0);
+    ADLASSERT(op == ADLHIP_REDUCE_SUM || op == ADLHIP_REDUCE_MIN || op == ADLHIP_REDUCE_MAX);
+    if (n <= 0) return;
+    ADLASSERT(device != 0);
+    ADLASSERT((adl::u64)n <= keys.getSize() && (adl::u64)n <= src.getSize() && (adl::u64)n <= dst.getSize());
+    if (!onDevice(device)) {
+        ADLASSERT(device->getType() == adl::TYPE_HOST);   // a HIP device never falls back to the CPU
+        if (device->getType() != adl::TYPE_HOST) return;
+        K* host = keys.getHostPtr(n);
+        V* in = src.getHostPtr(n);
+        V* out = dst.m_ptr == src.m_ptr ? in : dst.getHostPtr(n);
+        adl::DeviceUtils::waitForCompletion(device);
+        hostScan<K, V>(host, in, out, n, op, exclusive);
+        keys.returnHostPtr(host);
+        if (out != in) dst.returnHostPtr(out);
+        src.returnHostPtr(in);
+        adl::DeviceUtils::waitForCompletion(device);
+        return;
+    }
+    size_t wb = 0;
+    const int rcq = adlhip_scan_by_key_scratch_bytes(device->hip(), (int)sizeof(K), KeyTraits<V>::TYPE, (size_t)n, &wb);
+    ADLASSERT(rcq == ADLHIP_SUCCESS);
+    reserve(device, 0, wb);
+    const int rc = adlhip_scan_by_key(device->hip(), (int)sizeof(K), keys.m_ptr, KeyTraits<V>::TYPE, op, exclusive ? 1 : 0, 0, src.m_ptr,
+                                      dst.m_ptr, (size_t)n, m_work->m_ptr, (size_t)m_work->getSize());
+    if (rc != ADLHIP_SUCCESS) TH_LOG_ERROR("Pprims::scanByKey: %s\n", adlhip_last_error());
+    ADLASSERT(rc == ADLHIP_SUCCESS);
+}
+
+template <typename V>
+void Pprims::scanTyped(const adl::Device* device, const adl::Buffer<V>& src, adl::Buffer<V>& dst, int n, int op, bool exclusive)
+{
+    ADLASSERT(n >= 0);
+    ADLASSERT(op == ADLHIP_REDUCE_SUM || op == ADLHIP_REDUCE_MIN || op == ADLHIP_REDUCE_MAX);
+    if (n <= 0) return;
+    ADLASSERT(device != 0);
+    ADLASSERT((adl::u64)n <= src.getSize() && (adl::u64)n <= dst.getSize());
+    if (!onDevice(device)) {
+        ADLASSERT(device->getType() == adl::TYPE_HOST);   // a HIP device never falls back to the CPU
+        if (device->getType() != adl::TYPE_HOST) return;
+        V* in = src.getHostPtr(n);
+        V* out = dst.m_ptr == src.m_ptr ? in : dst.getHostPtr(n);
+        adl::DeviceUtils::waitForCompletion(device);
+        hostScan<u32, V>(0, in, out, n, op, exclusive);
+        if (out != in) dst.returnHostPtr(out);
+        src.returnHostPtr(in);
+        adl::DeviceUtils::waitForCompletion(device);
+        return;
+    }
+    size_t wb = 0;
+    const int rcq = adlhip_scan_typed_scratch_bytes(device->hip(), KeyTraits<V>::TYPE, (size_t)n, &wb);
+    ADLASSERT(rcq == ADLHIP_SUCCESS);
+    reserve(device, 0, wb);
+    const int rc = adlhip_scan_typed(device->hip(), KeyTraits<V>::TYPE, op, exclusive ? 1 : 0, 0, src.m_ptr, dst.m_ptr, (size_t)n, m_work->m_ptr,
+                                     (size_t)m_work->getSize());
+    if (rc != ADLHIP_SUCCESS) TH_LOG_ERROR("Pprims::scanTyped: %s\n", adlhip_last_error());
+    ADLASSERT(rc == ADLHIP_SUCCESS);
+}
+
+#define TAHOE_SCAN(K, V)                                                                                                            \
+    template void Pprims::scanByKey<K, V>(const adl::Device*, const adl::Buffer<K>&, const adl::Buffer<V>&, adl::Buffer<V>&, int, int, bool);
+#define TAHOE_SCAN_KEY(K)                                                                                                           \
+    TAHOE_SCAN(K, int) TAHOE_SCAN(K, float) TAHOE_SCAN(K, long long) TAHOE_SCAN(K, double) TAHOE_SCAN(K, u32) TAHOE_SCAN(K, u64)
+TAHOE_SCAN_KEY(int)
+TAHOE_SCAN_KEY(float)
+TAHOE_SCAN_KEY(long long)
+TAHOE_SCAN_KEY(double)
+TAHOE_SCAN_KEY(u32)
+TAHOE_SCAN_KEY(u64)
+#undef TAHOE_SCAN_KEY
+#undef TAHOE_SCAN
+#define TAHOE_SCAN_PLAIN(V) template void Pprims::scanTyped<V>(const adl::Device*, const adl::Buffer<V>&, adl::Buffer<V>&, int, int, bool);
+TAHOE_SCAN_PLAIN(int)
+TAHOE_SCAN_PLAIN(float)
+TAHOE_SCAN_PLAIN(long long)
+TAHOE_SCAN_PLAIN(double)
+TAHOE_SCAN_PLAIN(u32)
+TAHOE_SCAN_PLAIN(u64)
+#undef TAHOE_SCAN_PLAIN
 
 #define TAHOE_TYPED(T)                                                                                                              \
     void Pprims::sortKeys(const adl::Device* device, const adl::Buffer<T>& inout, int n, bool descending)                         \

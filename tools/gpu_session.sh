@@ -19,7 +19,7 @@ for k in kv u64; do for n in 4194304 8388608 16777216 33554432 67108864 13421772
 echo "== large sort, keys of one eighth of the range (a rank of an 8-GPU sort)"; MSD2CURVE_SHIFT=3 MSD2CURVE_MODES=1,0 timeout -k 10 300 python tools/msd2curve.py 16777216 67108864 134217728 2>&1 | tee $OUT/msd2_rank_range.txt
 echo "== multi-rank rehearsal on one GPU (code path only, host-staged collectives)"
 ADLHIP_BENCH_REHEARSE=1 ADLHIP_BENCH_N=8388608 timeout -k 10 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 4 --master-addr 127.0.0.1 --master-port 29611 bench.py --full --gpus 4 --steps 3 --warmup 1 2>&1 | tail -1 | tee $OUT/bench_multirank_rehearsal.txt
-echo "== scan"; timeout -k 10 300 python tools/scan_bench.py 2>&1 | tee $OUT/scan.txt
+echo "== scan"; timeout -k 10 300 python tools/scan_u32_bench.py 2>&1 | tee $OUT/scan.txt
 fi
 if [ "$PART" = a ]; then exit 0; fi
 echo "== bench"; timeout -k 10 900 python bench.py --full 2>&1 | tail -1 | tee $OUT/bench_n1.json
