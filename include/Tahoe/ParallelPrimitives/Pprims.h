@@ -158,6 +158,27 @@ public:
     void scanByKey(const adl::Device* device, const adl::Buffer<K>& keys, const adl::Buffer<V>& src, adl::Buffer<V>& dst, int n,
                    int op = ADLHIP_REDUCE_SUM, bool exclusive = false);
 
+    // stream compaction: the elements i < n whose flag byte is non-zero, in input order, to itemsOut[0 .. S) and -- where indexOut is
+    // given -- their positions to indexOut[0 .. S).  partition: a stable partition, the rejected elements follow in input order at
+    // [S, n); without it nothing at S and beyond is written.  T: int, float, long long, double, u32, u64; items are copied bit for bit.
+    // The outputs hold n elements.  items and flags are left intact.  Like unique this one WAITS and returns S.  A TYPE_HOST device
+    // runs a plain loop
+    template <typename T>
+    int compactFlagged(const adl::Device* device, const adl::Buffer<T>& items, const adl::Buffer<unsigned char>& flags, adl::Buffer<T>& itemsOut,
+                       adl::Buffer<u32>* indexOut, int n, bool partition = false);
+    // the same for the elements with keys[i] cmp threshold (ADLHIP_CMP_LT .. ADLHIP_CMP_NE) in the ascending order of sortKeys: integers
+    // by value, floats by totalOrder (NaNs are ordered, -0 is below +0); EQ / NE compare bits.  values / valuesOut (both or neither; V
+    // independently of K) travel with their keys
+    template <typename K, typename V>
+    int compactIf(const adl::Device* device, const adl::Buffer<K>& keys, const adl::Buffer<V>* values, int cmp, K threshold,
+                  adl::Buffer<K>& keysOut, adl::Buffer<V>* valuesOut, adl::Buffer<u32>* indexOut, int n, bool partition = false);
+    template <typename K>
+    int compactIf(const adl::Device* device, const adl::Buffer<K>& keys, int cmp, K threshold, adl::Buffer<K>& keysOut,
+                  adl::Buffer<u32>* indexOut, int n, bool partition = false)
+    {
+        return compactIf<K, u32>(device, keys, (const adl::Buffer<u32>*)0, cmp, threshold, keysOut, (adl::Buffer<u32>*)0, indexOut, n, partition);
+    }
+
 private:
     template <typename T> int uniqueTyped(const adl::Device* device, const adl::Buffer<T>& keys, adl::Buffer<T>& uniqueOut, adl::Buffer<u32>& countsOut,
                                           int n, bool descending);

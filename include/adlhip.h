@@ -480,6 +480,61 @@ int adlhip_scan_by_key_scratch_bytes(adlhip_device* dev, int key_bytes, int valu
 int adlhip_scan_by_key(adlhip_device* dev, int key_bytes, const void* d_keys_in, int value_type, int op, int exclusive,
                        const void* h_init_or_null, const void* d_vals_in, void* d_out, size_t n, void* d_work, size_t work_bytes);
 
+/* ---- stream compaction: select and partition by flags or by a comparison (no reference counterpart) ---- */
+
+/* The filter behind a sort or a scan: thrust's copy_if / remove_if / stable_partition, cub's DeviceSelect::Flagged / If and
+ * DevicePartition, torch's masked_select, nonzero and t[t < x].
+ *
+ * Predicate.
+ *   Flagged: element i is selected when d_flags_in[i] != 0.  Flags are one byte per element, the layout of a torch bool tensor; any
+ *     non-zero byte selects.
+ *   If: element i is selected when d_keys_in[i] cmp threshold, in the ASCENDING order of the typed sorts -- integers by value, floats by
+ *     IEEE totalOrder: -NaN < -inf < ... < -0 < +0 < ... < +inf < +NaN.  EQ / NE are equality of bits, as everywhere else in this
+ *     header (so -0 != +0, and a NaN equals the NaN with the same bits).  All six are unsigned comparisons of the code of the key with
+ *     the code of the threshold, the code being what adlhip_key_encode(key_type, ADLHIP_ORDER_ASCENDING) gives.  h_threshold points to
+ *     one key of key_type in HOST memory, read at call time, as h_init_or_null of the scans is.
+ *
+ * Result, with S the number of selected elements: *d_num_selected_out = S.  The selected elements appear in input order at [0, S) of
+ * every output that is given; d_index_out receives their input positions (torch's nonzero, and the gather index for further columns).
+ *   partition == 0: elements at S and beyond are NEVER written.
+ *   partition == 1: a stable partition.  The rejected elements follow in input order at [S, n), and every output element is written.
+ * item_bytes is 4 or 8; it may be 0, with d_items_in_or_null and d_items_out_or_null NULL, for positions only.  value_bytes is 0 (both
+ * value pointers NULL), 4 or 8; the key width and the value width are independent.  With a non-zero width the input array is required,
+ * the output array optional (an input without its output is not read).  At least one output array must be given.  Items, keys and
+ * values are copied bit for bit.
+ *
+ * Contract, as in the unique and reduce blocks: n < 2^32.  The inputs are never written.  Every output array holds n elements.  Every
+ * array and d_work are 16-byte aligned, the count word 4-byte aligned; no output (the count word included) may overlap an input.
+ * n == 0 enqueues one 4-byte clear of the count word and nothing else.  A NULL required pointer (h_threshold included), a misaligned
+ * pointer, an overlap, an unknown item_bytes, value_bytes, key_type, cmp or partition, no output at all, and a work buffer one byte
+ * short (the message names the needed size) fail before anything is enqueued.  The calls enqueue and return: nothing data-dependent
+ * reaches the host (S stays on the device; launch grids depend on n alone), nothing is remembered between calls, all state lives in
+ * d_work -- whose contents on entry are arbitrary -- and the handle owns no device word of it.  No kernel waits on another workgroup
+ * or uses an atomic to global memory.
+ *
+ * Work bytes, with CUs = adlhip_info.compute_units:
+ *   adlhip_compact_scratch_bytes = 16 CUs rounded up to 256 (one count per workgroup of the largest grid, 4 workgroups per CU)
+ * Nothing is proportional to n: the value suffices for every n.
+ *
+ * Three launches over tiles of 2048 elements: the workgroups count the selected elements of their chunks, one workgroup scans the
+ * counts and writes S, the workgroups walk their chunks again, rank every element with a workgroup scan per tile, put the tile in rank
+ * order in LDS and store it where the ranks say (a rejected element of a partition: S + its position - the selected elements in
+ * front of it).  The predicate's input is read twice, everything else once. */
+#define ADLHIP_CMP_LT 0
+#define ADLHIP_CMP_LE 1
+#define ADLHIP_CMP_GT 2
+#define ADLHIP_CMP_GE 3
+#define ADLHIP_CMP_EQ 4
+#define ADLHIP_CMP_NE 5
+int adlhip_compact_scratch_bytes(adlhip_device* dev, size_t n, size_t* work_bytes);
+int adlhip_compact_flagged(adlhip_device* dev, int item_bytes, const void* d_items_in_or_null, const uint8_t* d_flags_in, size_t n,
+                           int partition, void* d_items_out_or_null, uint32_t* d_index_out_or_null,
+                           uint32_t* d_num_selected_out, void* d_work, size_t work_bytes);
+int adlhip_compact_if_typed(adlhip_device* dev, int key_type, int cmp, const void* h_threshold, const void* d_keys_in,
+                            int value_bytes, const void* d_vals_in_or_null, size_t n, int partition,
+                            void* d_keys_out_or_null, void* d_vals_out_or_null, uint32_t* d_index_out_or_null,
+                            uint32_t* d_num_selected_out, void* d_work, size_t work_bytes);
+
 /* ---- segments finished in LDS (no reference counterpart) ------------------------------------- */
 
 /* Sorts, stably and in place, every segment [d_seg_start[s], d_seg_start[s + 1]) of an array of u32 keys
@@ -649,6 +704,8 @@ int adlhip_generate_keys(adlhip_device* dev, int elem_kind, void* dptr, size_t n
  *   "debug.scan_grid"  workgroups the scan stage of adlhip_scan_typed / adlhip_scan_by_key is launched with at most (0 [default]: 4 per
  *                      CU; larger values change nothing); tests set it to make few workgroups take many tiles.  Float sums may differ
  *                      in the last bits between two values of it (another association), never between two calls
+ *   "debug.compact_grid" workgroups adlhip_compact_flagged / adlhip_compact_if_typed are launched with at most (0 [default]: 4 per
+ *                      CU; larger values change nothing); tests set it to make few workgroups take many tiles
  *   "sort.net_lookback" 1 [default] / 0: the LSD passes of the large sort's safety net on whole keys are look-back passes -- the
  *                      one-sweep path's histogram, tables and tile body, taken in turns by the net's resident workgroups, four
  *                      passes at a time (u64 keys: two rounds) -- instead of count -> scan -> scatter passes with per-workgroup

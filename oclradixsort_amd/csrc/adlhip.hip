@@ -2628,6 +2628,9 @@ int adlhip_set_param(adlhip_device* d, const char* name, int value)
     } else if (!strcmp(name, "debug.scan_grid")) {
         if (value < 0) return fail("debug.scan_grid must be >= 0");
         d->scan_grid = value;
+    } else if (!strcmp(name, "debug.compact_grid")) {
+        if (value < 0) return fail("debug.compact_grid must be >= 0");
+        d->compact_grid = value;
     } else if (!strcmp(name, "debug.finish16_alg")) {
         if (value != -1 && value != 1 && value != 2) return fail("debug.finish16_alg must be -1 (the adopted variant), 1 (the round-4 kernel) or 2");
         d->finish16_alg = value;
@@ -2678,6 +2681,7 @@ int adlhip_get_param(adlhip_device* d, const char* name, int* value)
     else if (!strcmp(name, "debug.unique_grid")) *value = d->unique_grid;
     else if (!strcmp(name, "debug.reduce_grid")) *value = d->reduce_grid;
     else if (!strcmp(name, "debug.scan_grid")) *value = d->scan_grid;
+    else if (!strcmp(name, "debug.compact_grid")) *value = d->compact_grid;
     else if (!strcmp(name, "partition.lookback")) *value = d->partition_lookback;
     else if (!strcmp(name, "sort.net_lookback")) *value = d->net_lookback;
     else if (!strcmp(name, "debug.finish16_alg")) *value = d->finish16_alg;

@@ -1,5 +1,5 @@
 // primitives.hip -- the host side of what is built on top of the sorts: typed keys and argsort, top-k, row-wise top-k, unique /
-// run-length encode, reduce by key, typed scans.  No reference counterpart.  It reaches the sorts through adlhip_internal.hpp alone (sort_elements,
+// run-length encode, reduce by key, typed scans, stream compaction.  No reference counterpart.  It reaches the sorts through adlhip_internal.hpp alone (sort_elements,
 // sort_work_bytes, soa_wide_layout) and never sees their kernels.
 #include "adlhip_internal.hpp"
 
@@ -19,9 +19,10 @@
 #include "unique_kernels.hpp"
 #include "reduce_kernels.hpp"
 #include "scan_kernels.hpp"
+#include "compact_kernels.hpp"
 
-// instantiated in kernels_select.hip / kernels_toprows.hip / kernels_unique.hip / kernels_reduce.hip / kernels_scan.hip; here they are
-// only declared
+// instantiated in kernels_select.hip / kernels_toprows.hip / kernels_unique.hip / kernels_reduce.hip / kernels_scan.hip /
+// kernels_compact.hip; here they are only declared
 #ifndef ADLHIP_SINGLE_TU
 #define X(...) extern template __global__ __VA_ARGS__;
 #include "select_kernels.inc"
@@ -29,6 +30,7 @@
 #include "unique_kernels.inc"
 #include "reduce_kernels.inc"
 #include "scan_kernels.inc"
+#include "compact_kernels.inc"
 #undef X
 #endif
 
@@ -715,6 +717,59 @@ int scan_check(adlhip_device* d, const char* what, const char* sizer, int key_by
     return ADLHIP_SUCCESS;
 }
 
+
+// ---- stream compaction (compact_kernels.hpp) ------------------------------------------------------------------
+// Work of the compaction: [selected counts: one u32 per workgroup of the largest grid], rounded up to 256 bytes.  Nothing proportional
+// to n.
+constexpr int kCompactWgsPerCu = 4;   // grid of the compaction per CU at most ("debug.compact_grid" lowers it)
+size_t compact_work_bytes(const adlhip_device* d)
+{
+    return align_up((size_t)d->prop.multiProcessorCount * kCompactWgsPerCu * 4, 256);
+}
+
+// the compaction of n > 0 elements.  P: uint8_t (pred = the flags) or the keys' unsigned type (pred = the keys, pred_out = where they
+// go); V: the unsigned type of the array that travels along (the flagged form's items, the if form's values), vals_out null = none
+template <typename P, typename V>
+int compact_stage(adlhip_device* d, const P* pred, adlhip::CompactPred pr, const V* vals, size_t n, int partition, P* pred_out, V* vals_out,
+                  uint32_t* index_out, uint32_t* num_out, void* work)
+{
+    uint32_t* chunk = static_cast<uint32_t*>(work);
+    const ChunkSplit cs = chunk_split(d, n, (size_t)adlhip::kRedTile, kCompactWgsPerCu, d->compact_grid);
+    const uint32_t wgs = cs.wgs, nn = (uint32_t)n, nt = cs.tiles, tpw = cs.tiles_per_wg;
+    static const char* const kSource[3] = {"flags", "k32", "k64"};
+    const char* source = kSource[sizeof(P) == 1 ? 0 : sizeof(P) == 4 ? 1 : 2];
+    int rc = launch(d, intern(std::string("compact_count_") + source), [&] {
+        hipLaunchKernelGGL((adlhip::compact_count_kernel<P>), dim3(wgs), dim3(adlhip::kSelNT), 0, d->stream, pred, nn, nt, tpw, pr, chunk);
+    });
+    if (rc) return rc;
+    rc = launch_scan_single(d, "compact_scan", chunk, chunk, wgs, num_out);   // in place; the total is the number selected
+    if (rc) return rc;
+    const int vbits = vals_out ? 8 * (int)sizeof(V) : 0;
+    return launch(d, intern(std::string("compact_emit_") + source + "_v" + std::to_string(vbits)), [&] {
+        if (vals_out)
+            hipLaunchKernelGGL((adlhip::compact_emit_kernel<P, V>), dim3(wgs), dim3(adlhip::kSelNT), 0, d->stream, pred, vals, nn, nt, tpw, pr,
+                               (const uint32_t*)chunk, (const uint32_t*)num_out, (uint32_t)partition, pred_out, vals_out, index_out);
+        else
+            hipLaunchKernelGGL((adlhip::compact_emit_kernel<P, adlhip::CompactNone>), dim3(wgs), dim3(adlhip::kSelNT), 0, d->stream, pred,
+                               (const adlhip::CompactNone*)nullptr, nn, nt, tpw, pr, (const uint32_t*)chunk, (const uint32_t*)num_out,
+                               (uint32_t)partition, pred_out, (adlhip::CompactNone*)nullptr, index_out);
+    });
+}
+
+// the width of the array that travels along: 0 (then neither pointer may be given), 4 or 8
+int compact_check_width(const char* what, const char* name, int bytes, bool allow_zero, const void* in, const void* out)
+{
+    if (bytes != 4 && bytes != 8 && !(allow_zero && bytes == 0))
+        return fail("%s: %s must be %s4 or 8, got %d", what, name, allow_zero ? "0, " : "", bytes);
+    if (bytes == 0 && (in || out)) return fail("%s: %s is 0, so its input and output arrays must be NULL", what, name);
+    return ADLHIP_SUCCESS;
+}
+int compact_check_partition(const char* what, int partition)
+{
+    if (partition != 0 && partition != 1) return fail("%s: partition must be 0 (select) or 1 (stable partition), got %d", what, partition);
+    return ADLHIP_SUCCESS;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1026,6 +1081,69 @@ int adlhip_scan_by_key(adlhip_device* d, int key_bytes, const void* keys_in, int
         return rc;
     return ADLHIP_BY_WIDTH(key_bytes, K, ADLHIP_BY_WIDTH(v.bytes, W, scan_stage<K, W>(d, (const K*)keys_in, (const W*)vals_in, (W*)out, n, v.kind,
                            op, exclusive, h_init, work)));
+}
+
+// ---- stream compaction ------------------------------------------------------------------------------
+int adlhip_compact_scratch_bytes(adlhip_device* d, size_t n, size_t* work_bytes)
+{
+    if (!d) return fail("null device handle");
+    if (typed_check_n(n)) return ADLHIP_FAILURE;
+    if (work_bytes) *work_bytes = compact_work_bytes(d);
+    return ADLHIP_SUCCESS;
+}
+
+int adlhip_compact_flagged(adlhip_device* d, int item_bytes, const void* items_in, const uint8_t* flags_in, size_t n, int partition,
+                           void* items_out, uint32_t* index_out, uint32_t* num_selected_out, void* work, size_t work_bytes)
+{
+    const char* what = "compact flagged";
+    if (bind(d) || compact_check_width(what, "item_bytes", item_bytes, true, items_in, items_out) || compact_check_partition(what, partition) ||
+        typed_check_n(n))
+        return ADLHIP_FAILURE;
+    if (!items_out && !index_out) return fail("%s: at least one of d_items_out and d_index_out must be given", what);
+    if (const int rc = count_word(d, what, "d_num_selected_out", num_selected_out, n); rc || n == 0) return rc;
+    const size_t ib = n * (size_t)item_bytes;
+    if (check_buffers(what, {{flags_in, n, "d_flags_in"}, {items_in, ib, "d_items_in", item_bytes != 0}},
+                      {{items_out, ib, "d_items_out", false}, {index_out, n * 4, "d_index_out", false}}, num_selected_out, work))
+        return ADLHIP_FAILURE;
+    const size_t need = compact_work_bytes(d);
+    if (work_bytes < need) return fail("work buffer too small: %zu < %zu (adlhip_compact_scratch_bytes)", work_bytes, need);
+    const adlhip::CompactPred pr = {0u, 0u, 0u};
+    return ADLHIP_BY_WIDTH(item_bytes ? item_bytes : 4, V, compact_stage<uint8_t, V>(d, flags_in, pr, (const V*)items_in, n, partition, nullptr,
+                                                                                      (V*)items_out, index_out, num_selected_out, work));
+}
+
+int adlhip_compact_if_typed(adlhip_device* d, int key_type, int cmp, const void* h_threshold, const void* keys_in, int value_bytes,
+                            const void* vals_in, size_t n, int partition, void* keys_out, void* vals_out, uint32_t* index_out,
+                            uint32_t* num_selected_out, void* work, size_t work_bytes)
+{
+    const char* what = "compact if";
+    TypeInfo t;
+    if (bind(d) || type_info("key_type", key_type, &t)) return ADLHIP_FAILURE;
+    if (cmp < ADLHIP_CMP_LT || cmp > ADLHIP_CMP_NE) return fail("%s: cmp must be one of ADLHIP_CMP_LT .. ADLHIP_CMP_NE (0..5), got %d", what, cmp);
+    if (compact_check_width(what, "value_bytes", value_bytes, true, vals_in, vals_out) || compact_check_partition(what, partition) ||
+        typed_check_n(n))
+        return ADLHIP_FAILURE;
+    if (!h_threshold) return fail("%s: h_threshold is required", what);
+    if (!keys_out && !vals_out && !index_out) return fail("%s: at least one of d_keys_out, d_vals_out and d_index_out must be given", what);
+    if (const int rc = count_word(d, what, "d_num_selected_out", num_selected_out, n); rc || n == 0) return rc;
+    const size_t kb = n * (size_t)t.bytes, vb = n * (size_t)value_bytes;
+    if (check_buffers(what, {{keys_in, kb, "d_keys_in"}, {vals_in, vb, "d_vals_in", value_bytes != 0}},
+                      {{keys_out, kb, "d_keys_out", false}, {vals_out, vb, "d_vals_out", false}, {index_out, n * 4, "d_index_out", false}},
+                      num_selected_out, work))
+        return ADLHIP_FAILURE;
+    const size_t need = compact_work_bytes(d);
+    if (work_bytes < need) return fail("work buffer too small: %zu < %zu (adlhip_compact_scratch_bytes)", work_bytes, need);
+    // the threshold's code, as the kernels encode the keys
+    uint64_t bits = 0;
+    __builtin_memcpy(&bits, h_threshold, (size_t)t.bytes);   // (little endian: a 4-byte key lands in the low dword)
+    uint64_t code = 0;
+#define ADLHIP_THRESHOLD(KIND_, DESC_) \
+    code = t.bytes == 4 ? (uint64_t)adlhip::key_enc<uint32_t, KIND_, 0>((uint32_t)bits) : adlhip::key_enc<uint64_t, KIND_, 0>(bits)
+    ADLHIP_TYPED_DISPATCH(t.kind, 0, ADLHIP_THRESHOLD);
+#undef ADLHIP_THRESHOLD
+    const adlhip::CompactPred pr = {(uint32_t)t.kind, (uint32_t)cmp, code};
+    return ADLHIP_BY_WIDTH(t.bytes, K, ADLHIP_BY_WIDTH(value_bytes ? value_bytes : 4, V, compact_stage<K, V>(d, (const K*)keys_in, pr,
+                           (const V*)vals_in, n, partition, (K*)keys_out, (V*)vals_out, index_out, num_selected_out, work)));
 }
 
 }  // extern "C"

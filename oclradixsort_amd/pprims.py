@@ -16,6 +16,8 @@
     p.reduceRuns(device, keys, values, n, op="sum")        # -> ReduceResult: the same per run of keys that are already grouped
     p.scanTyped(device, dst, src, n, op="sum")             # inclusive / exclusive prefix sum, min or max of typed values
     p.scanByKey(device, keys, dst, src, n, op="sum")       # the same within every run of keys that are already grouped
+    p.compactFlagged(device, flags, n, items=buf)          # -> CompactResult: the items whose flag byte is non-zero, in input order
+    p.compactIf(device, keys, n, "lt", x, values=buf)      # -> CompactResult: the keys (and their values) that compare so with x
 
 Like the reference object it owns lazily grown device scratch (m_u32WorkBuffer[0] = ping-pong data
 buffer, m_u32WorkBuffer[1] = histogram table; Pprims.h:44-45, Pprims.cpp:226-232, :332-337) and must be
@@ -50,6 +52,14 @@ REDUCE_OPS = {"sum": 0, "min": 1, "max": 2}
 # What reduceByKey / reduceRuns return: device Buffers (None where not asked).  `count` is a one-element uint32 Buffer that holds R;
 # unique, reduced and counts have n elements of which the first R are written, offsets n + 1 (R + 1 written).
 ReduceResult = collections.namedtuple("ReduceResult", "unique reduced counts offsets count")
+
+# ADLHIP_CMP_* by name (include/adlhip.h, "stream compaction")
+CMP_OPS = {"lt": 0, "le": 1, "gt": 2, "ge": 3, "eq": 4, "ne": 5, "<": 0, "<=": 1, ">": 2, ">=": 3, "==": 4, "!=": 5}
+
+# What compactFlagged / compactIf return: device Buffers (None where not asked).  `count` is a one-element uint32 Buffer that holds S,
+# the number of selected elements; items (compactIf: the keys), values and index have n elements of which the first S are written --
+# all n with partition=True, the rejected elements behind the selected ones.
+CompactResult = collections.namedtuple("CompactResult", "items values index count")
 
 
 class Pprims:
@@ -510,6 +520,102 @@ class Pprims:
         of 4 or 8 bytes, already grouped): the scan starts again at every run's first element, which gets init (exclusive) or its
         own bits (inclusive).  dst may be src, not keys."""
         self._scan("scanByKey", device, keys, dst, src, n, op, exclusive, init)
+
+    # -- stream compaction (no reference counterpart; include/adlhip.h adlhip_compact_flagged / adlhip_compact_if_typed)
+    def _compact(self, what, device, n, pred, arrays, indexOut, countOut, call):
+        """arrays: [(name, input Buffer or None, output: None / False / True / Buffer)] -- an input's output defaults to a new Buffer of
+        its type.  call(lib, pointers of the inputs, pointers of the outputs, index pointer, count pointer) runs the entry point."""
+        if device is None:
+            raise AdlHipError("%s needs a device" % what)
+        n = int(n)
+        room = min([pred.getSize()] + [b.getSize() for _, b, _ in arrays if b is not None])
+        if n < 0 or room < n:
+            raise AdlHipError("%s: n = %d outside [0, %d]" % (what, n, room))
+        outs = []
+        for name, b, o in arrays:
+            if b is None:
+                if o is not None and o is not False:
+                    raise AdlHipError("%s: %sOut needs %s" % (what, name, name))
+                outs.append(None)
+                continue
+            if np.dtype(b.dtype).itemsize not in (4, 8):
+                raise AdlHipError("%s: unsupported %s type %s (4 or 8 bytes)" % (what, name, b.dtype))
+            if o is None:
+                o = True
+            if o is not True and o is not False and (not hasattr(o, "getSize") or np.dtype(o.dtype) != np.dtype(b.dtype) or o.getSize() < n):
+                raise AdlHipError("%s: %sOut must hold n elements of %s" % (what, name, b.dtype))
+            outs.append(o)
+        if countOut is not None and (np.dtype(countOut.dtype) != np.uint32 or countOut.getSize() < 1):
+            raise AdlHipError("%s: countOut must hold one uint32 element" % what)
+        if not any(o is not None and o is not False for o in outs) and (indexOut is None or indexOut is False):
+            raise AdlHipError("%s: nothing asked (an array to compact, or indexOut)" % what)
+        (idx,), own = self._runs_outputs(what, device, n, [("indexOut", indexOut, n)])
+        try:
+            lib = _lib.load()
+            wb = ctypes.c_size_t()
+            check(lib.adlhip_compact_scratch_bytes(device._h, n, ctypes.byref(wb)), "adlhip_compact_scratch_bytes")
+            self._scratch(device, 0, wb.value)
+            for k, (name, b, _) in enumerate(arrays):
+                if outs[k] is True:
+                    outs[k] = Buffer(device, n, b.dtype)
+                    own.append(outs[k])
+                elif outs[k] is False:
+                    outs[k] = None
+            if countOut is None:
+                countOut = Buffer(device, 1, np.uint32)
+                own.append(countOut)
+
+            def p(b):
+                return b.ptr() if b is not None else None
+            check(call(lib, [p(b) for _, b, _ in arrays], [p(o) for o in outs], p(idx), countOut.ptr()), what)
+        except AdlHipError:
+            for b in own:
+                b.release()
+            raise
+        return outs, idx, countOut
+
+    def compactFlagged(self, device, flags, n, items=None, partition=False, itemsOut=None, indexOut=None, countOut=None):
+        """The elements i < n whose flag byte flags[i] (a uint8 or bool Buffer) is non-zero, in input order -> CompactResult.  With S of
+        them (result.count, on the device): items[0 .. S) the selected elements of `items` (any element type of 4 or 8 bytes; None:
+        positions only), index[0 .. S) their positions.  partition=True: a stable partition -- the rejected elements follow in input
+        order at [S, n); otherwise nothing at S and beyond is written.  itemsOut: a Buffer of the items' type to fill (n elements),
+        False for none, default a new one; indexOut: True for a new uint32 Buffer, or one to fill; countOut (uint32, 1 element).
+        The inputs are left intact.  Enqueues and returns; read result.count (toHost) to learn S."""
+        what = "compactFlagged"
+        if flags is not None and np.dtype(flags.dtype).itemsize != 1:
+            raise AdlHipError("%s: flags must be one byte per element (uint8 or bool), got %s" % (what, flags.dtype))
+        ib = np.dtype(items.dtype).itemsize if items is not None else 0
+
+        def call(lib, ins, outs, idx, cnt):
+            return lib.adlhip_compact_flagged(device._h, ib, ins[0], flags.ptr(), int(n), 1 if partition else 0, outs[0], idx, cnt,
+                                              self.m_work.ptr(), self.m_work.getSize())
+        if device is None:
+            raise AdlHipError("%s needs a device" % what)
+        outs, idx, cnt = self._compact(what, device, n, flags, [("items", items, itemsOut)], indexOut, countOut, call)
+        return CompactResult(outs[0], None, idx, cnt)
+
+    def compactIf(self, device, keys, n, cmp, threshold, values=None, partition=False, keysOut=None, valuesOut=None, indexOut=None,
+                  countOut=None):
+        """The keys i < n with keys[i] cmp threshold ("lt", "le", "gt", "ge", "eq", "ne") in the ascending order of sortKeys, in input
+        order -> CompactResult (items = the keys).  Integers compare by value, floats by totalOrder (-NaN < -inf < ... < -0 < +0 < ...
+        < +NaN: NaNs are ordered, -0 is below +0); eq / ne compare bits.  `values` (any element type of 4 or 8 bytes, whatever the
+        keys' width) travel with their keys.  partition, keysOut / valuesOut (False: not written), indexOut and countOut as in
+        compactFlagged.  The inputs are left intact.  Enqueues and returns; read result.count (toHost) to learn S."""
+        what = "compactIf"
+        if device is None:
+            raise AdlHipError("%s needs a device" % what)
+        kt = self._key_type(keys, what)
+        if cmp not in CMP_OPS:
+            raise AdlHipError("%s: cmp must be 'lt', 'le', 'gt', 'ge', 'eq' or 'ne', got %r" % (what, cmp))
+        pat = np.array(threshold, dtype=keys.dtype).reshape(1)
+        vb = np.dtype(values.dtype).itemsize if values is not None else 0
+
+        def call(lib, ins, outs, idx, cnt):
+            return lib.adlhip_compact_if_typed(device._h, kt, CMP_OPS[cmp], pat.ctypes.data_as(ctypes.c_void_p), ins[0], vb, ins[1], int(n),
+                                               1 if partition else 0, outs[0], outs[1], idx, cnt, self.m_work.ptr(), self.m_work.getSize())
+        outs, idx, cnt = self._compact(what, device, n, keys, [("keys", keys, keysOut), ("values", values, valuesOut)], indexOut, countOut,
+                                       call)
+        return CompactResult(outs[0], outs[1], idx, cnt)
 
     def copy(self, device, dst, src, n):
         """Pprims::copy (Pprims.cpp:31-67, commented out in the reference): first n elements of src -> dst."""

@@ -12,6 +12,9 @@ back-end on torch's own stream.
     u, sums = s.reduce_consecutive(keys, values, op="sum")                       # the same per run of adjacent equal keys
     c = s.cumsum(t); m = s.cummax(t); m = s.cummin(t)                            # prefix sum / max / min, in t's dtype
     r = s.scan_by_key(keys, values, op="sum", exclusive=False, init=None)        # the same within every run of adjacent equal keys
+    sel = s.masked_select(t, mask); pos = s.nonzero(mask)                        # torch.masked_select / torch.nonzero (bool or uint8 mask)
+    sel = s.select_if(t, "lt", x)                                                # t[t < x], in totalOrder; also "le", "gt", "ge", "eq", "ne"
+    out, count = s.partition(t, mask)                                            # the selected elements, then the others; both in input order
     s.close()
 
 Always out of place and always stable.  The ONE difference from `torch.sort(t, stable=True)`: floats are ordered by
@@ -317,6 +320,120 @@ class TorchSorter:
         pattern: 0, the type's largest pattern in that order for "min", its smallest for "max" --, every other one op(init, the
         inclusive result in front of it).  An inclusive scan takes no init.  No host read."""
         return self._scan("scan_by_key", keys, values, op, exclusive, init)
+
+    def _flat_mask(self, mask, what):
+        """the checks of _flat_input for a bool / uint8 mask; returns it flattened, contiguous and 16-byte aligned"""
+        if not isinstance(mask, torch.Tensor):
+            raise TypeError("TorchSorter: expected a torch.Tensor, got %s" % type(mask).__name__)
+        if mask.dtype not in (torch.bool, torch.uint8):
+            raise TypeError("TorchSorter.%s: the mask must be bool or uint8, got %s" % (what, mask.dtype))
+        if mask.device != self.torch_device:
+            raise ValueError("TorchSorter: tensor is on %s, the sorter on %s" % (mask.device, self.torch_device))
+        if mask.numel() >= 1 << 32:
+            raise ValueError("TorchSorter: fewer than 2^32 elements")
+        if torch.cuda.current_stream(self.torch_device).cuda_stream != self.raw_stream:
+            raise RuntimeError("TorchSorter: bound to the stream that was current at construction; another stream is current now")
+        flat = mask.contiguous().reshape(-1)
+        if flat.data_ptr() % 16:
+            flat = flat.clone()
+        return flat
+
+    def _compact_flagged(self, what, t, mask, partition, want_index):
+        """(items or None, int64 positions or None, S) of the flagged compaction of t (None: positions only) by mask"""
+        m = self._flat_mask(mask, what)
+        flat = None
+        if t is not None:
+            flat = self._flat_input(t, what, False)
+            if tuple(t.shape) != tuple(mask.shape):
+                raise ValueError("TorchSorter.%s: the mask's shape %s is not the tensor's %s (no broadcasting)"
+                                 % (what, tuple(mask.shape), tuple(t.shape)))
+        n = m.numel()
+        dev = mask.device
+        if n == 0:
+            return (torch.empty(0, dtype=t.dtype, device=dev) if t is not None else None,
+                    torch.empty(0, dtype=torch.int64, device=dev) if want_index else None, 0)
+        out = torch.empty(n, dtype=t.dtype, device=dev) if t is not None else None
+        idx32 = torch.empty(n, dtype=torch.int32, device=dev) if want_index else None   # uint32 positions in an int32 tensor
+        count = torch.empty(1, dtype=torch.int32, device=dev)
+        self.pprims.compactFlagged(self.device, self._wrap(m, np.uint8), n,
+                                   items=self._wrap(flat, _NP_DTYPE[t.dtype]) if t is not None else None, partition=partition,
+                                   itemsOut=self._wrap(out, _NP_DTYPE[t.dtype]) if t is not None else None,
+                                   indexOut=self._wrap(idx32, np.uint32) if want_index else None, countOut=self._wrap(count, np.uint32))
+        self.device.checkFault()
+        s = int(count.item()) & 0xffffffff   # the one host read
+        keep = n if partition else s
+        if out is not None and not partition:
+            out = out[:s].clone()
+        return out, (idx32[:keep].to(torch.int64) & 0xffffffff) if want_index else None, s
+
+    def masked_select(self, t, mask):
+        """torch.masked_select(t, mask) for a mask of t's shape (NO broadcasting), bool or uint8 (any non-zero byte selects): the
+        selected elements of t in row-major order, 1-D, bit for bit.  t: int32 / int64 / float32 / float64, any number of dimensions.
+        Like torch.masked_select this makes ONE host read, of the number of selected elements: the call waits for the stream."""
+        return self._compact_flagged("masked_select", t, mask, False, False)[0]
+
+    def nonzero(self, mask):
+        """torch.nonzero(mask) for a bool or uint8 mask of any number of dimensions: int64 of shape [S, mask.dim()], the positions of
+        the non-zero elements in row-major order (the flat positions come from the device, they are unravelled with torch ops).
+        ONE host read, as torch.nonzero makes."""
+        idx = self._compact_flagged("nonzero", None, mask, False, True)[1]
+        if idx.numel() == 0:
+            return torch.empty((0, mask.dim()), dtype=torch.int64, device=mask.device)
+        cols = []
+        for size in reversed(mask.shape):
+            cols.append(idx % size)
+            idx = idx // size
+        return torch.stack(cols[::-1], dim=1)
+
+    def partition(self, t, mask):
+        """(out, S): out has t's elements flattened -- first the S elements whose mask byte is non-zero, then the others, both in
+        input (row-major) order: thrust's stable_partition with a stencil.  mask as in masked_select.  ONE host read, of S."""
+        out, _, s = self._compact_flagged("partition", t, mask, True, False)
+        return out, s
+
+    def select_if(self, t, cmp, threshold, values=None, return_indices=False):
+        """t[t cmp threshold] for a 1-D tensor; cmp is "lt", "le", "gt", "ge", "eq" or "ne" (or "<", "<=", ">", ">=", "==", "!=").
+        Returns the selected elements in input order, then -- where given / asked -- values[t cmp threshold] (a 1-D tensor of t's
+        length, int32 / int64 / float32 / float64 whatever t's dtype) and their int64 positions; one tensor or a tuple.
+        The comparison is the order of sort(): integers by value, floats by IEEE totalOrder.  It differs from torch's t[t < x] on
+        NaN and -0 ONLY: NaNs are ordered by sign and payload (-NaN below -inf, +NaN above +inf) where torch's comparisons with a
+        NaN are all false (and != true), -0 is below +0 where torch holds them equal, and "eq" / "ne" compare bits (so a NaN equals
+        itself).  Inputs and thresholds without NaN and -0 give torch's result bit for bit.  ONE host read, of the number selected."""
+        if cmp not in ("lt", "le", "gt", "ge", "eq", "ne", "<", "<=", ">", ">=", "==", "!="):
+            raise ValueError("TorchSorter.select_if: cmp must be 'lt', 'le', 'gt', 'ge', 'eq' or 'ne', got %r" % (cmp,))
+        k = self._flat_input(t, "select_if", True)
+        v = self._flat_input(values, "select_if", True) if values is not None else None
+        n = k.numel()
+        if v is not None and v.numel() != n:
+            raise ValueError("TorchSorter.select_if: %d elements but %d values" % (n, v.numel()))
+        dev = t.device
+        if n == 0:
+            out = (torch.empty(0, dtype=t.dtype, device=dev),)
+            if v is not None:
+                out += (torch.empty(0, dtype=values.dtype, device=dev),)
+            if return_indices:
+                out += (torch.empty(0, dtype=torch.int64, device=dev),)
+            return out if len(out) > 1 else out[0]
+        kdt = _NP_DTYPE[t.dtype]
+        kout = torch.empty(n, dtype=t.dtype, device=dev)
+        vout = torch.empty(n, dtype=values.dtype, device=dev) if v is not None else None
+        idx32 = torch.empty(n, dtype=torch.int32, device=dev) if return_indices else None   # uint32 positions in an int32 tensor
+        count = torch.empty(1, dtype=torch.int32, device=dev)
+        if isinstance(threshold, torch.Tensor):
+            threshold = threshold.item()
+        self.pprims.compactIf(self.device, self._wrap(k, kdt), n, cmp, threshold,
+                              values=self._wrap(v, _NP_DTYPE[values.dtype]) if v is not None else None,
+                              keysOut=self._wrap(kout, kdt),
+                              valuesOut=self._wrap(vout, _NP_DTYPE[values.dtype]) if v is not None else None,
+                              indexOut=self._wrap(idx32, np.uint32) if return_indices else None, countOut=self._wrap(count, np.uint32))
+        self.device.checkFault()
+        s = int(count.item()) & 0xffffffff   # the one host read
+        out = (kout[:s].clone(),)
+        if v is not None:
+            out += (vout[:s].clone(),)
+        if return_indices:
+            out += (idx32[:s].to(torch.int64) & 0xffffffff,)
+        return out if len(out) > 1 else out[0]
 
     def sort(self, t, descending=False):
         """(values, indices) like torch.sort(t, descending=descending, stable=True); indices are int64."""

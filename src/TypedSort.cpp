@@ -5,7 +5,8 @@
 // position) on the host.  Pprims::topKRows: adlhip_topk_rows_typed, or the same partial sort per row.  Pprims::unique:
 // adlhip_unique_typed (it waits for the count), or the runs of the host argsort.  Pprims::reduceByKey: adlhip_reduce_by_key_typed (it
 // waits for the count), or a loop over the runs of the host argsort.  Pprims::scanTyped / scanByKey: adlhip_scan_typed /
-// adlhip_scan_by_key, or a plain loop, left to right.
+// adlhip_scan_by_key, or a plain loop, left to right.  Pprims::compactFlagged / compactIf: adlhip_compact_flagged /
+// adlhip_compact_if_typed (they wait for the count), or a plain loop.
 #include <Tahoe/ParallelPrimitives/Pprims.h>
 
 #include <algorithm>
@@ -488,6 +489,164 @@ TAHOE_SCAN_PLAIN(double)
 TAHOE_SCAN_PLAIN(u32)
 TAHOE_SCAN_PLAIN(u64)
 #undef TAHOE_SCAN_PLAIN
+
+namespace {
+
+// keep[i] -> the stable order: the kept positions, then (partition) the others; returns the number kept
+inline int hostCompactOrder(const std::vector<unsigned char>& keep, bool partition, std::vector<u32>& order)
+{
+    const int n = (int)keep.size();
+    order.clear();
+    for (int i = 0; i < n; ++i)
+        if (keep[i]) order.push_back((u32)i);
+    const int kept = (int)order.size();
+    if (partition)
+        for (int i = 0; i < n; ++i)
+            if (!keep[i]) order.push_back((u32)i);
+    return kept;
+}
+
+template <typename T>
+inline void hostGather(const adl::Buffer<T>& src, adl::Buffer<T>& dst, const std::vector<u32>& order, int n)
+{
+    T* in = src.getHostPtr(n);
+    T* out = dst.getHostPtr(n);
+    adl::DeviceUtils::waitForCompletion(src.m_device);
+    for (size_t j = 0; j < order.size(); ++j) memcpy(&out[j], &in[order[j]], sizeof(T));
+    src.returnHostPtr(in);
+    dst.returnHostPtr(out);
+}
+
+inline void hostWriteIndex(adl::Buffer<u32>* indexOut, const std::vector<u32>& order, int n)
+{
+    if (!indexOut) return;
+    u32* out = indexOut->getHostPtr(n);
+    adl::DeviceUtils::waitForCompletion(indexOut->m_device);
+    for (size_t j = 0; j < order.size(); ++j) out[j] = order[j];
+    indexOut->returnHostPtr(out);
+}
+
+inline bool hostCompare(int cmp, bool lt, bool eq)
+{
+    switch (cmp) {
+    case ADLHIP_CMP_LT: return lt;
+    case ADLHIP_CMP_LE: return lt || eq;
+    case ADLHIP_CMP_GT: return !lt && !eq;
+    case ADLHIP_CMP_GE: return !lt;
+    case ADLHIP_CMP_EQ: return eq;
+    default: return !eq;
+    }
+}
+
+}  // namespace
+
+template <typename T>
+int Pprims::compactFlagged(const adl::Device* device, const adl::Buffer<T>& items, const adl::Buffer<unsigned char>& flags, adl::Buffer<T>& itemsOut,
+                           adl::Buffer<u32>* indexOut, int n, bool partition)
+{
+    ADLASSERT(n >= 0);
+    if (n <= 0) return 0;
+    ADLASSERT(device != 0);
+    ADLASSERT((adl::u64)n <= items.getSize() && (adl::u64)n <= flags.getSize() && (adl::u64)n <= itemsOut.getSize() &&
+              (!indexOut || (adl::u64)n <= indexOut->getSize()));
+    if (!onDevice(device)) {
+        ADLASSERT(device->getType() == adl::TYPE_HOST);   // a HIP device never falls back to the CPU
+        if (device->getType() != adl::TYPE_HOST) return 0;
+        unsigned char* f = flags.getHostPtr(n);
+        adl::DeviceUtils::waitForCompletion(device);
+        std::vector<unsigned char> keep(f, f + n);
+        flags.returnHostPtr(f);
+        std::vector<u32> order;
+        const int kept = hostCompactOrder(keep, partition, order);
+        hostGather(items, itemsOut, order, n);
+        hostWriteIndex(indexOut, order, n);
+        adl::DeviceUtils::waitForCompletion(device);
+        return kept;
+    }
+    size_t wb = 0;
+    const int rcq = adlhip_compact_scratch_bytes(device->hip(), (size_t)n, &wb);
+    ADLASSERT(rcq == ADLHIP_SUCCESS);
+    reserve(device, 16, wb);   // m_tmp holds the count word
+    const int rc = adlhip_compact_flagged(device->hip(), (int)sizeof(T), items.m_ptr, (const uint8_t*)flags.m_ptr, (size_t)n, partition ? 1 : 0,
+                                          itemsOut.m_ptr, indexOut ? (uint32_t*)indexOut->m_ptr : 0, (uint32_t*)m_tmp->m_ptr, m_work->m_ptr,
+                                          (size_t)m_work->getSize());
+    if (rc != ADLHIP_SUCCESS) TH_LOG_ERROR("Pprims::compactFlagged: %s\n", adlhip_last_error());
+    ADLASSERT(rc == ADLHIP_SUCCESS);
+    if (rc != ADLHIP_SUCCESS) return 0;
+    unsigned char word[4] = {0, 0, 0, 0};
+    m_tmp->read(word, 4);
+    adl::DeviceUtils::waitForCompletion(device);
+    u32 kept = 0;
+    memcpy(&kept, word, 4);
+    return (int)kept;
+}
+
+template <typename K, typename V>
+int Pprims::compactIf(const adl::Device* device, const adl::Buffer<K>& keys, const adl::Buffer<V>* values, int cmp, K threshold,
+                      adl::Buffer<K>& keysOut, adl::Buffer<V>* valuesOut, adl::Buffer<u32>* indexOut, int n, bool partition)
+{
+    ADLASSERT(n >= 0);
+    ADLASSERT(cmp >= ADLHIP_CMP_LT && cmp <= ADLHIP_CMP_NE);
+    ADLASSERT((values != 0) == (valuesOut != 0));
+    if (n <= 0) return 0;
+    ADLASSERT(device != 0);
+    ADLASSERT((adl::u64)n <= keys.getSize() && (adl::u64)n <= keysOut.getSize() && (!values || (adl::u64)n <= values->getSize()) &&
+              (!valuesOut || (adl::u64)n <= valuesOut->getSize()) && (!indexOut || (adl::u64)n <= indexOut->getSize()));
+    if (!onDevice(device)) {
+        ADLASSERT(device->getType() == adl::TYPE_HOST);   // a HIP device never falls back to the CPU
+        if (device->getType() != adl::TYPE_HOST) return 0;
+        K* host = keys.getHostPtr(n);
+        adl::DeviceUtils::waitForCompletion(device);
+        const typename KeyTraits<K>::Bits t = ordinal(threshold, false);
+        std::vector<unsigned char> keep((size_t)n);
+        for (int i = 0; i < n; ++i) {
+            const typename KeyTraits<K>::Bits o = ordinal(host[i], false);
+            keep[i] = hostCompare(cmp, o < t, o == t) ? 1 : 0;
+        }
+        keys.returnHostPtr(host);
+        std::vector<u32> order;
+        const int kept = hostCompactOrder(keep, partition, order);
+        hostGather(keys, keysOut, order, n);
+        if (values) hostGather(*values, *valuesOut, order, n);
+        hostWriteIndex(indexOut, order, n);
+        adl::DeviceUtils::waitForCompletion(device);
+        return kept;
+    }
+    size_t wb = 0;
+    const int rcq = adlhip_compact_scratch_bytes(device->hip(), (size_t)n, &wb);
+    ADLASSERT(rcq == ADLHIP_SUCCESS);
+    reserve(device, 16, wb);   // m_tmp holds the count word
+    const int rc = adlhip_compact_if_typed(device->hip(), KeyTraits<K>::TYPE, cmp, &threshold, keys.m_ptr, values ? (int)sizeof(V) : 0,
+                                           values ? values->m_ptr : 0, (size_t)n, partition ? 1 : 0, keysOut.m_ptr,
+                                           valuesOut ? valuesOut->m_ptr : 0, indexOut ? (uint32_t*)indexOut->m_ptr : 0, (uint32_t*)m_tmp->m_ptr,
+                                           m_work->m_ptr, (size_t)m_work->getSize());
+    if (rc != ADLHIP_SUCCESS) TH_LOG_ERROR("Pprims::compactIf: %s\n", adlhip_last_error());
+    ADLASSERT(rc == ADLHIP_SUCCESS);
+    if (rc != ADLHIP_SUCCESS) return 0;
+    unsigned char word[4] = {0, 0, 0, 0};
+    m_tmp->read(word, 4);
+    adl::DeviceUtils::waitForCompletion(device);
+    u32 kept = 0;
+    memcpy(&kept, word, 4);
+    return (int)kept;
+}
+
+#define TAHOE_COMPACT(K, V)                                                                                                         \
+    template int Pprims::compactIf<K, V>(const adl::Device*, const adl::Buffer<K>&, const adl::Buffer<V>*, int, K, adl::Buffer<K>&, \
+                                         adl::Buffer<V>*, adl::Buffer<u32>*, int, bool);
+#define TAHOE_COMPACT_KEY(K)                                                                                                        \
+    TAHOE_COMPACT(K, int) TAHOE_COMPACT(K, float) TAHOE_COMPACT(K, long long) TAHOE_COMPACT(K, double) TAHOE_COMPACT(K, u32)        \
+    TAHOE_COMPACT(K, u64)                                                                                                           \
+    template int Pprims::compactFlagged<K>(const adl::Device*, const adl::Buffer<K>&, const adl::Buffer<unsigned char>&, adl::Buffer<K>&, \
+                                           adl::Buffer<u32>*, int, bool);
+TAHOE_COMPACT_KEY(int)
+TAHOE_COMPACT_KEY(float)
+TAHOE_COMPACT_KEY(long long)
+TAHOE_COMPACT_KEY(double)
+TAHOE_COMPACT_KEY(u32)
+TAHOE_COMPACT_KEY(u64)
+#undef TAHOE_COMPACT_KEY
+#undef TAHOE_COMPACT
 
 #define TAHOE_TYPED(T)                                                                                                              \
     void Pprims::sortKeys(const adl::Device* device, const adl::Buffer<T>& inout, int n, bool descending)                         \

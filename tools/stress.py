@@ -6,6 +6,7 @@ is followed -- while later sorts are already queued -- by the LDS-order self-tes
 behaviour "sort.rank" = 1 rests on, adlhip_selftest_lds_order), and one size class reaches past 64 Mi keys (the
 pointer-store write-out).  Half of the sorts take the automatic choice (mid-size sort, large sort with its look-back /
 cursor passes and the safety net inside its offsets kernel), with "sort.msd2" forced on for some and keys shifted down by a random number of bits.
+One kind in six is a stream compaction between the sorts (a stable partition of the keys by a comparison, values and positions along).
    python tools/stress.py [--seconds 60]"""
 import argparse, os, sys, time
 import numpy as np
@@ -32,7 +33,7 @@ def checks(a):
     return int(a64.sum(dtype=np.uint64)), int(np.bitwise_xor.reduce(a64)) if a.size else 0
 while time.time() < t_end and it < args.stop_after:
     it += 1
-    kind = rng.choice(["u32", "kv", "u64", "soa", "soaw"])
+    kind = rng.choice(["u32", "kv", "u64", "soa", "soaw", "compact"])
     n = int(2 ** rng.uniform(10, 25.5)) + int(rng.randint(0, 1000))
     if it % 7 == 0: n = int(2 ** rng.uniform(21, 26.3))   # more of the large sort's range
     if kind == "u32" and it % 23 == 0: n = (1 << 26) + int(rng.randint(1, 1 << 22))     # past 256 MiB: pointer stores
@@ -51,7 +52,7 @@ while time.time() < t_end and it < args.stop_after:
             else: rng.randint(1, 4)
         continue
     if verbose: print("it %d %s n=%d algo=%d bits=%d tile=%d msd2=%d dist=%s shift=%d" % (it, kind, n, algo, bits, tile, msd2_mode, dist, shift), flush=True)
-    if kind in ("u32", "soa", "kv", "soaw"):
+    if kind in ("u32", "soa", "kv", "soaw", "compact"):
         k = oracle.keys_u32(n, seed=it)
         if dist == "heavy": k = np.where(np.arange(n) % 10 != 0, (k >> np.uint32(8)) | np.uint32(0x37000000), k).astype(np.uint32)
         elif dist == "vals4096": k = (k >> np.uint32(20)) * np.uint32(0x00100801)
@@ -90,6 +91,18 @@ while time.time() < t_end and it < args.stop_after:
         p.radixSortSoA(d, kb, vb, n); ok, ov = kb.toHost(), vb.toHost(); kb.release(); vb.release()
         assert np.all(ok[1:] >= ok[:-1]); same = ok[1:] == ok[:-1]
         assert np.all(ov[1:][same] > ov[:-1][same]) and np.array_equal(k[ov], ok), (it, kind, n, algo, bits, tile, dist)
+    elif kind == "compact":   # a stable partition of the keys (as int32) below / not below one of them, 8-byte values and positions along
+        n = min(n, 1 << 24)
+        k = k[:n]
+        th = k[n // 3]
+        v = np.arange(n, dtype=np.uint64) * np.uint64(0x9E3779B97F4A7C15)
+        kb = Buffer(d, n, np.int32); vb = Buffer(d, n, np.uint64); kb.write(k.view(np.int32)); vb.write(v)
+        r = p.compactIf(d, kb, n, "lt", th.view(np.int32), values=vb, partition=True, indexOut=True)
+        s, ok, ov, oi = int(r.count.toHost()[0]), r.items.toHost().view(np.uint32), r.values.toHost(), r.index.toHost()
+        for b in (kb, vb, r.items, r.values, r.index, r.count): b.release()
+        below = k.view(np.int32) < th.view(np.int32)
+        order = np.concatenate([np.flatnonzero(below), np.flatnonzero(~below)])
+        assert s == int(below.sum()) and np.array_equal(oi, order) and np.array_equal(ok, k[order]) and np.array_equal(ov, v[order]), (it, kind, n, dist)
     elif kind == "soaw":   # wide values / 64-bit keys on separate arrays (adlhip_radix_sort_soa): index sort + gather
         n = min(n, 1 << 23)
         k = k[:n]
