@@ -726,9 +726,6 @@ int adlhip_generate_keys(adlhip_device* dev, int elem_kind, void* dptr, size_t n
  *                      sort's, 3 the dictionary block, 4 the fault words); 0 when clean
  *   "debug.idle_poke"  (set-only; tests) region << 24 | word: flips bit 0 of that word in stream order -- the positive control of
  *                      "debug.idle_dirty"; a second poke undoes the first
- *   "debug.finish16_alg" variant of the 16-bit LDS finish of the large u32 sort (finish16_kernels.hpp): -1 [default] the adopted
- *                      one (2: bin starts gathered by plain LDS reads), 1 the round-4 kernel (gathers through a volatile
- *                      pointer: FLAT loads); for A/B runs and tests
  *   "debug.resident_wgs" workgroups the device certainly keeps resident at once (asked of the runtime at creation); the
  *                      paths whose safety nets hold a grid-wide barrier over 256 workgroups are taken only when it is
  *                      >= 256.  Setting it stands in for a small partition (tests); 0 = ask the device again

@@ -348,7 +348,7 @@ int dispatch_scatter(adlhip_device* d, const Buf& src, const Buf& dst, const uin
 
 // three-kernel pass with at most this many workgroups: the count kernel leaves its raw counts workgroup-major and the
 // scatter kernel sums its column itself (16 or 64 independent coalesced loads per thread), so the table-scan launch is
-// dropped -- 12 -> 8 dependent launches per 32-bit sort.  Same-session A/B (ADLHIP_FUSED_SCAN_MAX = 0 / 16 / 64):
+// dropped -- 12 -> 8 dependent launches per 32-bit sort.  Same-session A/B (a limit of 0 / 16 / 64 workgroups):
 // 32 Ki keys 35.8 -> 26.5 us; 64 Ki + 1 .. 128 Ki keys 38.3 -> 36.0 / 37.2 -> 34.5 us; 200000 .. 256 Ki keys level.
 constexpr uint32_t kScanInScatterMaxWgs = 64;
 
@@ -362,8 +362,7 @@ int three_kernel_pass(adlhip_device* d, const Buf& src, const Buf& dst, void* wo
     uint32_t* table = reinterpret_cast<uint32_t*>(work);
     uint32_t* totals = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(work) + table_bytes(d, n, kMinTile));
     const uint32_t elems_per_wg = g.tiles_per_wg * g.tile;
-    static const uint32_t fused_max = getenv("ADLHIP_FUSED_SCAN_MAX") ? (uint32_t)atoi(getenv("ADLHIP_FUSED_SCAN_MAX")) : kScanInScatterMaxWgs;
-    const bool fused = !need_totals && g.n_wgs <= std::min<uint32_t>(fused_max, 64u);
+    const bool fused = !need_totals && g.n_wgs <= kScanInScatterMaxWgs;
     int rc = launch(d, kernel_name<Buf, NBITS>("count"), [&] {
         hipLaunchKernelGGL((adlhip::radix_count_kernel<key_t, NBITS, kCountNT>), dim3(g.n_wgs), dim3(kCountNT), 0, d->stream,
                            src.keys(), table, (uint32_t)n, (int)g.n_wgs, start_bit, elems_per_wg, fused ? 1 : 0);
@@ -683,8 +682,7 @@ int segment_sort(adlhip_device* d, const E* in, E* out, const uint32_t* seg_star
                  int low_bits, const uint32_t* dyn)
 {
     // small segments, at most 16 bits: one wave per segment
-    static const bool no_wave = getenv("ADLHIP_SEGSORT_NO_WAVE") != nullptr;
-    if (!no_wave && low_bits <= 16 && dyn == nullptr && max_segment <= 1280)
+    if (low_bits <= 16 && dyn == nullptr && max_segment <= 1280)
         return launch_wave_segment_sort<E, 20>(d, in, out, seg_start, num_segments, low_bits);
     // tile by the caller's bound on the segment size; the digit width of the local passes by what fits beside the tile
     if (sizeof(E) == 4) {
@@ -700,6 +698,9 @@ int segment_sort(adlhip_device* d, const E* in, E* out, const uint32_t* seg_star
 }
 
 // ---- mid-size sort: byte histograms + tables -> one MSD pass -> buckets finished in LDS (hybrid_kernels.hpp) ----------
+// u32 keys take the two-launch mid-size sort from here -- below the one-workgroup sort's limit kSmallMax: 10000 keys 16.5 -> 15.6 us,
+// 12288 17.9 -> 15.5, 16384 19.3 -> 15.4; from 4096 it loses (6000 keys 13.6 -> 15.1).  profiles/r3_small_mid_ab.txt
+constexpr size_t kMidMinU32 = 8192;
 constexpr size_t kMidMaxU32 = size_t(2) << 20;
 constexpr size_t kMidMaxE64 = size_t(1) << 20;
 constexpr uint32_t kMidTile = 4096;   // pass 2 runs on 256 x 16 tiles
@@ -729,19 +730,11 @@ MidLayout mid_layout(size_t n)
     return L;
 }
 
-// u32 keys take the two-launch mid-size sort from here -- below the one-workgroup sort's limit kSmallMax: 10000 keys 16.5 -> 15.6 us,
-// 12288 17.9 -> 15.5, 16384 19.3 -> 15.4; from 4096 it loses (6000 keys 13.6 -> 15.1).  profiles/r3_small_mid_ab.txt; A/B: ADLHIP_MID_MIN
-size_t mid_min_u32()
-{
-    static const size_t v = getenv("ADLHIP_MID_MIN") ? (size_t)atoll(getenv("ADLHIP_MID_MIN")) : 8192;
-    return v;
-}
-
 bool mid_eligible(const adlhip_device* d, size_t elem_bytes, size_t n, int sort_bits, int max_bits)
 {
     if (d->resident_wgs < 256) return false;   // the finish's one workgroup per bucket doubles as a 256-workgroup cooperative sort
     return d->sort_algo < 0 && d->mid_path && max_bits == 32 && sort_bits == 32 && d->rank_mode == 1 && d->digit_bits == 8 &&
-           d->tile_variant < 0 && n > (elem_bytes == 4 ? mid_min_u32() : kSmallMax) && n <= (elem_bytes == 4 ? kMidMaxU32 : kMidMaxE64);
+           d->tile_variant < 0 && n > (elem_bytes == 4 ? kMidMinU32 : kSmallMax) && n <= (elem_bytes == 4 ? kMidMaxU32 : kMidMaxE64);
 }
 
 // Which form an eligible sort takes: 2 = two launches (u32 keys only), 3 = three launches, 0 = the per-digit passes.
@@ -929,8 +922,7 @@ uint32_t msd2_stride_b(size_t n, uint32_t slots = 65536, bool fine = false, bool
 // the LSD finish pays for every extra bit with LDS passes, so there the narrow digit stops at 16 Mi elements.
 uint32_t msd2_seg_shift(size_t n, bool bin_finish)
 {
-    static const long long env = getenv("ADLHIP_SEGSHIFT_MAXN") ? atoll(getenv("ADLHIP_SEGSHIFT_MAXN")) : -1;   // A/B: 0 = never
-    const size_t max_n = env >= 0 ? (size_t)env : (bin_finish ? size_t(1) << 40 : size_t(16) << 20);
+    const size_t max_n = bin_finish ? size_t(1) << 40 : size_t(16) << 20;
     if (n >= max_n) return 8u;
     uint32_t w = 2u;
     while (w < 8u && (n >> (8u + w)) > 1024u) ++w;
@@ -1118,8 +1110,6 @@ Msd2Layout msd2_layout(size_t n, size_t elem_bytes, int headroom_pct = kFullHead
     const uint32_t tile = elem_bytes == 4 ? 16384u : 8192u;   // TileCfg<E, 8, 512, 32 | 16>
     // mean bucket + 50 % + 4096: the head-room of the segment slabs below (1536 for a mean of 1024), so that keys whose density
     // varies by up to ~45 % over the key range stay on this path (with + 3 % any mild skew went to the safety net)
-    static const int env_pct = getenv("ADLHIP_SLAB_A_HEADROOM_PCT") ? atoi(getenv("ADLHIP_SLAB_A_HEADROOM_PCT")) : -1;   // A/B only
-    if (headroom_pct == kFullHeadroomPct && env_pct >= 0) headroom_pct = env_pct;
     L.stride_a = (uint32_t)align_up(n / 256 + (n / 256) * (size_t)headroom_pct / 100 + 4096, 64);
     L.seg_shift = msd2_seg_shift(n, elem_bytes == 8);   // the cursor form sorts whole keys: 8-byte elements = u64 keys
     L.slots = 256u << L.seg_shift;
@@ -1387,8 +1377,7 @@ int launch_large_finish(adlhip_device* d, const E* slab_b, E* out, uint32_t* out
             const uint16_t* sb = reinterpret_cast<const uint16_t*>(slab_b);
 #define ADLHIP_F16(R2_, WAVES_)                                                                                                      \
     {                                                                                                                                \
-        auto kf = d->finish16_alg == 1 ? adlhip::wave_finish16_kernel<R2_, WAVES_, true, true, 1>                                    \
-                                       : adlhip::wave_finish16_kernel<R2_, WAVES_, true, true, 2>;                                   \
+        auto kf = adlhip::wave_finish16_kernel<R2_, WAVES_>;                                                                         \
         const size_t lds = (size_t)WAVES_ * adlhip::Finish16Cfg<R2_>::PER_WAVE;                                                      \
         if (ensure_lds(kf, lds)) return ADLHIP_FAILURE;                                                                              \
         return launch(d, "segment_sort_wave_u32", [&] {                                                                              \
@@ -1402,23 +1391,17 @@ int launch_large_finish(adlhip_device* d, const E* slab_b, E* out, uint32_t* out
 #undef ADLHIP_F16
         }
     }
-    // A/B knobs: ADLHIP_WG_MIN_TIER = smallest tile that takes the workgroup finish, ADLHIP_WG_NT = 0 (default choice) / 128 / 256 / 512
-    static const uint32_t wg_min = getenv("ADLHIP_WG_MIN_TIER") ? (uint32_t)atoi(getenv("ADLHIP_WG_MIN_TIER")) : 3072u;
-    static const int wg_nt = getenv("ADLHIP_WG_NT") ? atoi(getenv("ADLHIP_WG_NT")) : 0;
-    if (tier_b > 5120 || (wg_kind && tier_b >= wg_min && seg_shift == 8)) {
+    if (tier_b > 5120 || (wg_kind && tier_b >= 3072 && seg_shift == 8)) {
         if constexpr (wg_kind) {
             const S* sb = reinterpret_cast<const S*>(slab_b);
             if (seg_shift != 8) return fail("internal: the workgroup-per-segment finish takes 65536 segments");
 #define ADLHIP_WG(NT_, K_) return launch_wg_segment_sort<E, S, NT_, K_>(d, sb, out, seg_off, seg_cnt, stride_b, mode, slots)
             switch (tier_b) {
-            case 1280: if (wg_nt == 256) ADLHIP_WG(256, 5); ADLHIP_WG(128, 10);
-            case 1536: if (wg_nt == 256) ADLHIP_WG(256, 6); ADLHIP_WG(128, 12);
-            case 2560: if (wg_nt == 128) ADLHIP_WG(128, 20); ADLHIP_WG(256, 10);
             case 3072: ADLHIP_WG(256, 12);
             case 4096: ADLHIP_WG(256, 16);
-            case 5120: if (wg_nt == 512) ADLHIP_WG(512, 10); ADLHIP_WG(256, 20);
-            case 8192: if (wg_nt == 512) ADLHIP_WG(512, 16); ADLHIP_WG(256, 32);
-            case 12288: if (wg_nt == 256) ADLHIP_WG(256, 48); ADLHIP_WG(512, 24);
+            case 5120: ADLHIP_WG(256, 20);
+            case 8192: ADLHIP_WG(256, 32);
+            case 12288: ADLHIP_WG(512, 24);
             case 16384: ADLHIP_WG(512, 32);
             default: ADLHIP_WG(512, 40);
             }
@@ -1712,7 +1695,7 @@ int sort_entry(adlhip_device* d, int elem_kind, E* data, E* tmp, void* work, siz
     // one workgroup, one launch -- except u32 keys just below its limit, which the two-launch mid-size sort does faster (while
     // the mid-size sort's own reports do not keep them off it, choose_mid_form)
     const bool small = d->sort_algo < 0 && n <= kSmallMax;
-    const bool small_mid = small && sizeof(E) == 4 && sort_bits == max_bits && n > mid_min_u32() && (d->mid_path == 2 || d->mid2_skip == 0);
+    const bool small_mid = small && sizeof(E) == 4 && sort_bits == max_bits && n > kMidMinU32 && (d->mid_path == 2 || d->mid2_skip == 0);
     if (small && !small_mid) return small_sort<E>(d, data, n, plan);
     if (mid_eligible(d, sizeof(E), n, sort_bits, max_bits) && mid_layout(n).total <= work_bytes) {
         const int form = choose_mid_form(d, sizeof(E) == 4);
@@ -2631,9 +2614,6 @@ int adlhip_set_param(adlhip_device* d, const char* name, int value)
     } else if (!strcmp(name, "debug.compact_grid")) {
         if (value < 0) return fail("debug.compact_grid must be >= 0");
         d->compact_grid = value;
-    } else if (!strcmp(name, "debug.finish16_alg")) {
-        if (value != -1 && value != 1 && value != 2) return fail("debug.finish16_alg must be -1 (the adopted variant), 1 (the round-4 kernel) or 2");
-        d->finish16_alg = value;
     } else if (!strcmp(name, "debug.resident_wgs")) {
         // what the paths with a grid-wide barrier (the safety nets) and the one-workgroup-per-bucket finish may count on;
         // 0 = ask the device again.  Tests use it to stand in for a small partition.
@@ -2684,7 +2664,6 @@ int adlhip_get_param(adlhip_device* d, const char* name, int* value)
     else if (!strcmp(name, "debug.compact_grid")) *value = d->compact_grid;
     else if (!strcmp(name, "partition.lookback")) *value = d->partition_lookback;
     else if (!strcmp(name, "sort.net_lookback")) *value = d->net_lookback;
-    else if (!strcmp(name, "debug.finish16_alg")) *value = d->finish16_alg;
     else if (!strcmp(name, "debug.resident_wgs")) *value = d->resident_wgs;
     else if (!strcmp(name, "stat.net_runs") || !strcmp(name, "stat.net_counting")) {
         // how often the large sort's safety net has run on this handle, and how often it sorted by counting (waits for the stream)

@@ -60,8 +60,6 @@ struct adlhip_device {
     int bin_finish = 1;       // "sort.binfinish": the large keys-only sort finishes its segments with one counting pass + compares
                               // (1: u64 keys, 2: u32 keys too, 0: the wave-per-segment LSD finish)
     int persist = 1;          // "sort.persist": the cursor passes of the large sort as persistent, prefetching kernels + the 16-bit finish
-    int finish16_alg = -1;    // "debug.finish16_alg": the variant of the 16-bit finish (finish16_kernels.hpp ALG); -1 = the adopted one (2:
-                              // plain LDS gathers), 1 = the round-4 kernel (gathers through a volatile pointer); A/B runs and tests
     int msd2_path = 1;        // "sort.msd2": the large sort (msd2_sort for keys, msd2s_sort for pairs); 2 = forced (tests)
     int net_lookback = 1;                   // "sort.net_lookback": the large sort's safety net runs look-back passes (0: count-scan-scatter passes)
     int partition_lookback = 1;             // "partition.lookback": the MSB partition as one look-back pass where it pays (0: always three kernels)

@@ -12,14 +12,16 @@
 // bank conflicts; conflicts of 64 random bins over 32 banks cannot be laid out away, so what this kernel buys is fewer LDS
 // instructions per key and more waves in flight to keep the LDS pipe full while others wait for memory.
 //
-// Variants (ALG; "debug.finish16_alg" chooses between 1 and 2, launch_large_finish): 0 and 1 are round 4's.  1 reads the bin starts
-// through a volatile pointer, which the compiler cannot place in LDS: a FLAT load and a full wait per key.  2 gathers them with plain
-// LDS reads (the compiler keeps eight ahead of their 16-bit stores, counted lgkmcnt waits) and is what runs: 64 Mi keys 0.102 ->
-// 0.096-0.097 ms.  There the LDS array is the limit -- SQ_LDS_IDX_ACTIVE is 186 K cycles per CU, 62 % of them bank conflicts of the
-// returning atomics, the gathers and the 16-bit scatter, in either variant -- and what was tried on top changed nothing: 8 waves per
-// SIMD instead of 5 (bounded batches of ranks and gathers, digits recomputed: 63 VGPRs), a prologue of one round trip, a tile index
-// of four instructions instead of eight (CHANGELOG.md, profiles/finish16_ab.txt, finish16_pmc.txt).  Registers: <10,4> 73, <12,4> 86,
-// <20,4> 125 VGPRs, no scratch.
+// Per pass ONE returning atomic per key counts its bin and ranks the key (its arrival number inside its bin, in position order); a
+// scan turns the counts into bin starts, and slot = bin start + rank.  The bin starts are gathered with plain LDS reads (a gather is
+// cheaper than a second atomic, tools/r4_lds_bench; the compiler keeps eight ahead of their 16-bit stores, counted lgkmcnt waits):
+// read through a volatile pointer, which the compiler cannot place in LDS, they were a FLAT load and a full wait per key -- 64 Mi keys
+// 0.102 -> 0.096-0.097 ms per launch (CHANGELOG.md, "the 16-bit finish gathers its bin starts from LDS", records the variants that
+// were compared).  The slab is loaded and the result stored non-temporally: neither is read again.  The LDS array is the limit --
+// SQ_LDS_IDX_ACTIVE is 186 K cycles per CU, 62 % of them bank conflicts of the returning atomics, the gathers and the 16-bit scatter
+// -- and what was tried on top changed nothing: 8 waves per SIMD instead of 5 (bounded batches of ranks and gathers, digits
+// recomputed: 63 VGPRs), a prologue of one round trip, a tile index of four instructions instead of eight (profiles/finish16_ab.txt,
+// finish16_pmc.txt).  Registers: <10,4> 73, <12,4> 86, <20,4> 125 VGPRs, no scratch.
 // What the wave's LDS accesses may assume of each other is written down once, at finish16_lds_order().
 //
 // Reference behaviour: Tahoe/ClKernels/RadixSort32Kernels.cl:401-489 (sort4Bits1: the stable local sort of a block).
@@ -47,10 +49,7 @@ __device__ __forceinline__ uint32_t finish16_index(uint32_t p) { return (p & ~12
 __device__ __forceinline__ void finish16_lds_order() { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); }
 
 // RR row pairs; the first RR - 1 are full (m > 128 (RR - 1)), only the last is tested per lane
-// NTL / NTS: non-temporal loads of the slab / stores of the result.  ALG: 0 = count, scan, then a returning atomic per key hands out
-// its slot; 1 = ONE returning atomic per key counts and ranks (its arrival number inside its bin, in position order), then scan and
-// slot = bin start (a gather: cheaper than an atomic, tools/r4_lds_bench) + rank; 2 = the same, the gather a plain LDS read.
-template <int RR, bool NTL, bool NTS, int ALG>
+template <int RR>
 __device__ __forceinline__ void finish16_rows(const uint32_t* __restrict__ src32, uint32_t* __restrict__ out, uint32_t m, int lane,
                                               uint16_t* __restrict__ buf16, uint32_t* __restrict__ cnt, uint32_t low_bits, uint32_t hi)
 {
@@ -61,7 +60,7 @@ __device__ __forceinline__ void finish16_rows(const uint32_t* __restrict__ src32
     uint32_t kp[RR];
 #pragma unroll
     for (int j = 0; j < RR; ++j)
-        if (j < L || a_lo) kp[j] = NTL ? __builtin_nontemporal_load(src32 + j * 64 + lane) : src32[j * 64 + lane];
+        if (j < L || a_lo) kp[j] = __builtin_nontemporal_load(src32 + j * 64 + lane);
     bool placed = false;   // wave-uniform: the keys sit in position order (a pass has run)
     const int npass = ((int)low_bits + 7) / 8;
     int sb = 0;
@@ -87,18 +86,13 @@ __device__ __forceinline__ void finish16_rows(const uint32_t* __restrict__ src32
         }
         const u32x4 z = {0u, 0u, 0u, 0u};
         *reinterpret_cast<u32x4*>(cnt + 4 * lane) = z;
-        uint32_t rk[RR];   // ALG 1: the two ranks of a register's keys
+        uint32_t rk[RR];   // the two ranks of a register's keys
 #pragma unroll
-        for (int j = 0; j < RR; ++j) {
-            if constexpr (ALG == 0) {
-                if (j < L || v_lo) __hip_atomic_fetch_add(&cnt[dlo(kp[j])], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-                if (j < L || v_hi) __hip_atomic_fetch_add(&cnt[dhi(kp[j])], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-            } else {   // position order: row 2j before row 2j + 1, colliding lanes in lane order (stable)
-                uint32_t r0 = 0u, r1 = 0u;
-                if (j < L || v_lo) r0 = __hip_atomic_fetch_add(&cnt[dlo(kp[j])], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-                if (j < L || v_hi) r1 = __hip_atomic_fetch_add(&cnt[dhi(kp[j])], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-                rk[j] = r0 | (r1 << 16);
-            }
+        for (int j = 0; j < RR; ++j) {   // position order: row 2j before row 2j + 1, colliding lanes in lane order (stable)
+            uint32_t r0 = 0u, r1 = 0u;
+            if (j < L || v_lo) r0 = __hip_atomic_fetch_add(&cnt[dlo(kp[j])], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+            if (j < L || v_hi) r1 = __hip_atomic_fetch_add(&cnt[dhi(kp[j])], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+            rk[j] = r0 | (r1 << 16);
         }
         {   // counts -> bin starts
             const u32x4 c = *reinterpret_cast<const u32x4*>(cnt + 4 * lane);
@@ -112,36 +106,13 @@ __device__ __forceinline__ void finish16_rows(const uint32_t* __restrict__ src32
             *reinterpret_cast<u32x4*>(cnt + 4 * lane) = o;
         }
         finish16_lds_order();   // the bin starts are written before any lane gathers one
-        if constexpr (ALG == 0) {
-            // slots: one returning atomic per key in position order (row 2j before row 2j + 1; colliding lanes are served in lane
-            // order: stable, radix_kernels.hpp rank_in_wave), then its 16-bit store
 #pragma unroll
-            for (int j = 0; j < RR; ++j) {
-                uint32_t p0 = 0u, p1 = 0u;
-                if (j < L || v_lo) p0 = __hip_atomic_fetch_add(&cnt[dlo(kp[j])], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-                if (j < L || v_hi) p1 = __hip_atomic_fetch_add(&cnt[dhi(kp[j])], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-                if (j < L || v_lo) buf16[finish16_index(p0)] = (uint16_t)kp[j];
-                if (j < L || v_hi) buf16[finish16_index(p1)] = (uint16_t)(kp[j] >> 16);
-            }
-        } else if constexpr (ALG == 1) {
-            const volatile uint32_t* start = cnt;
-#pragma unroll
-            for (int j = 0; j < RR; ++j) {
-                uint32_t p0 = 0u, p1 = 0u;
-                if (j < L || v_lo) p0 = start[dlo(kp[j])] + (rk[j] & 0xffffu);
-                if (j < L || v_hi) p1 = start[dhi(kp[j])] + (rk[j] >> 16);
-                if (j < L || v_lo) buf16[finish16_index(p0)] = (uint16_t)kp[j];
-                if (j < L || v_hi) buf16[finish16_index(p1)] = (uint16_t)(kp[j] >> 16);
-            }
-        } else {   // ALG 2: plain LDS reads
-#pragma unroll
-            for (int j = 0; j < RR; ++j) {
-                uint32_t p0 = 0u, p1 = 0u;
-                if (j < L || v_lo) p0 = cnt[dlo(kp[j])] + (rk[j] & 0xffffu);
-                if (j < L || v_hi) p1 = cnt[dhi(kp[j])] + (rk[j] >> 16);
-                if (j < L || v_lo) buf16[finish16_index(p0)] = (uint16_t)kp[j];
-                if (j < L || v_hi) buf16[finish16_index(p1)] = (uint16_t)(kp[j] >> 16);
-            }
+        for (int j = 0; j < RR; ++j) {   // slot = bin start (a plain LDS read) + rank
+            uint32_t p0 = 0u, p1 = 0u;
+            if (j < L || v_lo) p0 = cnt[dlo(kp[j])] + (rk[j] & 0xffffu);
+            if (j < L || v_hi) p1 = cnt[dhi(kp[j])] + (rk[j] >> 16);
+            if (j < L || v_lo) buf16[finish16_index(p0)] = (uint16_t)kp[j];
+            if (j < L || v_hi) buf16[finish16_index(p1)] = (uint16_t)(kp[j] >> 16);
         }
         finish16_lds_order();   // the 16-bit stores of the tile are issued before its 32-bit read-back
 #pragma unroll
@@ -153,14 +124,8 @@ __device__ __forceinline__ void finish16_rows(const uint32_t* __restrict__ src32
     if (placed) {
 #pragma unroll
         for (int j = 0; j < RR; ++j) {
-            if (j < L || b_lo) {
-                if constexpr (NTS) __builtin_nontemporal_store(hi | (kp[j] & 0xffffu), out + 128 * j + lane);
-                else out[128 * j + lane] = hi | (kp[j] & 0xffffu);
-            }
-            if (j < L || b_hi) {
-                if constexpr (NTS) __builtin_nontemporal_store(hi | (kp[j] >> 16), out + 128 * j + 64 + lane);
-                else out[128 * j + 64 + lane] = hi | (kp[j] >> 16);
-            }
+            if (j < L || b_lo) __builtin_nontemporal_store(hi | (kp[j] & 0xffffu), out + 128 * j + lane);
+            if (j < L || b_hi) __builtin_nontemporal_store(hi | (kp[j] >> 16), out + 128 * j + 64 + lane);
         }
     } else {   // no pass had anything to do: every key of the segment is the same, any order will do
 #pragma unroll
@@ -171,22 +136,22 @@ __device__ __forceinline__ void finish16_rows(const uint32_t* __restrict__ src32
     }
 }
 
-template <int RR, int R2, bool NTL, bool NTS, int ALG>
+template <int RR, int R2>
 __device__ __forceinline__ void finish16_dispatch(int rows2, const uint32_t* __restrict__ src32, uint32_t* __restrict__ out, uint32_t m,
                                                   int lane, uint16_t* __restrict__ buf16, uint32_t* __restrict__ cnt, uint32_t low_bits,
                                                   uint32_t hi)
 {
     if constexpr (RR >= R2) {
-        finish16_rows<R2, NTL, NTS, ALG>(src32, out, m, lane, buf16, cnt, low_bits, hi);
+        finish16_rows<R2>(src32, out, m, lane, buf16, cnt, low_bits, hi);
     } else {
-        if (rows2 <= RR) finish16_rows<RR, NTL, NTS, ALG>(src32, out, m, lane, buf16, cnt, low_bits, hi);
-        else finish16_dispatch<RR + 1, R2, NTL, NTS, ALG>(rows2, src32, out, m, lane, buf16, cnt, low_bits, hi);
+        if (rows2 <= RR) finish16_rows<RR>(src32, out, m, lane, buf16, cnt, low_bits, hi);
+        else finish16_dispatch<RR + 1, R2>(rows2, src32, out, m, lane, buf16, cnt, low_bits, hi);
     }
 }
 
 // slab: 65536 segment slabs of `stride` uint16_t (stride even); segment s holds seg_cnt[s] keys and goes to out[seg_off[s] ...).
 // dyn[0] = bits the finish sorts (<= 16), dyn[1] = the keys' common prefix above the two digits (msd2_offsets_kernel).
-template <int R2, int WAVES, bool NTL = false, bool NTS = false, int ALG = 0>
+template <int R2, int WAVES>
 __global__ __launch_bounds__(64 * WAVES) void wave_finish16_kernel(const uint16_t* __restrict__ slab, uint32_t* __restrict__ out,
                                                                     const uint32_t* __restrict__ seg_off,
                                                                     const uint32_t* __restrict__ seg_cnt, uint32_t stride,
@@ -213,7 +178,7 @@ __global__ __launch_bounds__(64 * WAVES) void wave_finish16_kernel(const uint16_
     }
     const uint32_t hi = ((dyn[1] << 16) | seg) << low_bits;
     const uint32_t* src32 = reinterpret_cast<const uint32_t*>(slab + (size_t)seg * stride);
-    finish16_dispatch<1, R2, NTL, NTS, ALG>((int)((m + 127u) >> 7), src32, out + begin, m, lane, buf16, cnt, low_bits, hi);
+    finish16_dispatch<1, R2>((int)((m + 127u) >> 7), src32, out + begin, m, lane, buf16, cnt, low_bits, hi);
 }
 
 }   // namespace adlhip

@@ -1,9 +1,9 @@
-"""The 16-bit LDS finish of the large u32 sort (finish16_kernels.hpp), every variant (run with `-m gpu` on the MI355X box).
+"""The 16-bit LDS finish of the large u32 sort (finish16_kernels.hpp) (run with `-m gpu` on the MI355X box).
 
 The finish sorts one segment per wave with a code path per number of row pairs (128 keys each), a validity test on the last row
 pair only, and local passes that are skipped when a digit is constant.  Random keys at one size visit two or three of those
 paths.  Here the keys are built segment by segment -- (segment << 16) | low -- so that chosen segments hold chosen counts and
-chosen low halves, and every case runs with "debug.finish16_alg" = 1 (the round-4 kernel) and -1 (the adopted variant).
+chosen low halves.  The kernel has one form; the knob that once chose between two is gone, and setting it is an error.
 
 Every case: bit-exact against the oracle's sort of the same keys; exactly the five launches of the cursor form with the wave
 finish; the safety net has not run (a case that falls into it would test nothing); a clean fault word and an idle handle.
@@ -15,12 +15,11 @@ import pytest
 
 import oracle
 from oclradixsort_amd import Buffer, DeviceUtils, _lib
-from oclradixsort_amd._lib import check
+from oclradixsort_amd._lib import AdlHipError, check
 
 MI = 1 << 20
 SLOTS = 65536
 LAUNCHES = {"msd2_sample", "msd2_pass1_u32", "msd2_pass2_u32", "msd2_offsets", "segment_sort_wave_u32"}
-VARIANTS = (1, -1)
 DYN_LOW_BITS = 4   # hybrid_kernels.hpp kDynLowBits: word of the work buffer's first block that holds the bits the finish sorts
 
 
@@ -82,12 +81,11 @@ def fits(keys, n):
 def dev():
     d = DeviceUtils.allocate()
     yield d
-    d.setParam("debug.finish16_alg", -1)
     DeviceUtils.deallocate(d)
 
 
-def sort_once(d, host, alg):
-    """One sort through the C ABI with `alg`; returns (result, launch names, safety nets run, the low bits the finish sorted)."""
+def sort_once(d, host):
+    """One sort through the C ABI; returns (result, launch names, safety nets run, the low bits the finish sorted)."""
     lib = _lib.load()
     n = host.size
     tb, wb = ctypes.c_size_t(), ctypes.c_size_t()
@@ -95,8 +93,6 @@ def sort_once(d, host, alg):
     bufs = [Buffer(d, n, np.uint32), Buffer(d, max(n, tb.value // 4), np.uint32), Buffer(d, wb.value, np.uint8)]
     try:
         bufs[0].write(host)
-        d.setParam("debug.finish16_alg", alg)
-        assert d.getParam("debug.finish16_alg") == alg
         runs0 = d.getParam("stat.net_runs")
         d.toggleProfiling(True)
         d.profile(reset=True)
@@ -106,7 +102,6 @@ def sort_once(d, host, alg):
         finally:
             prof = d.profile(reset=True)
             d.toggleProfiling(False)
-            d.setParam("debug.finish16_alg", -1)
         low_bits = int(bufs[2].toHost(4 * (DYN_LOW_BITS + 1)).view(np.uint32)[DYN_LOW_BITS])
         return out, set(prof), d.getParam("stat.net_runs") - runs0, low_bits
     finally:
@@ -119,16 +114,15 @@ def run_case(d, name, keys, want=None, low_bits=16, tier=None, times=1):
     if tier is not None:
         assert layout(n)[2] == tier, (name, layout(n))
     want = oracle.sort_u32(keys) if want is None else want
-    for alg in VARIANTS:
-        for t in range(times):
-            got, names, nets, lb = sort_once(d, keys, alg)
-            tag = (name, "finish16_alg", alg, "run", t)
-            assert names == LAUNCHES, (tag, sorted(names))
-            assert nets == 0, (tag, "the safety net ran: the case did not reach the finish")
-            assert lb == low_bits, (tag, "low bits", lb)
-            assert np.array_equal(got, want), tag
-            d.checkFault()
-            assert d.getParam("debug.idle_dirty") == 0, tag
+    for t in range(times):
+        got, names, nets, lb = sort_once(d, keys)
+        tag = (name, "run", t)
+        assert names == LAUNCHES, (tag, sorted(names))
+        assert nets == 0, (tag, "the safety net ran: the case did not reach the finish")
+        assert lb == low_bits, (tag, "low bits", lb)
+        assert np.array_equal(got, want), tag
+        d.checkFault()
+        assert d.getParam("debug.idle_dirty") == 0, tag
 
 
 def test_the_builder_keeps_its_counts():
@@ -255,6 +249,8 @@ def test_the_2560_tile_at_72Mi(dev):
 @pytest.mark.gpu
 @pytest.mark.parametrize("n_mi", [16, 64])
 def test_uniform_keys_twice_on_one_handle(dev, n_mi):
+    with pytest.raises(AdlHipError, match="unknown parameter"):   # the retired A/B knob; the handle sorts on as before
+        dev.setParam("debug.finish16_alg", 1)
     n = n_mi * MI
     keys = oracle.keys_u32(n, seed=n_mi)
     run_case(dev, "uniform %d Mi" % n_mi, keys, tier=1280 if n_mi == 16 else 1536, times=2)

@@ -307,31 +307,14 @@ int main(int argc, char** argv)
         snprintf(title, sizeof title, "persist %dx%d wg/cu=%d aux %d%d/%d%d %s", NT_, K_, WGS_, L1, S1, L2, S2, #FIN);           \
         chain(title, p1, p2, FIN);                                                                                               \
     }
-#define FIN16(NAME, WAVES_, NTL_, NTS_, ALG_)                                                                                    \
-    auto kf_##NAME = wave_finish16_kernel<12, WAVES_, NTL_, NTS_, ALG_>;                                                         \
-    const size_t lds_##NAME = (size_t)WAVES_ * Finish16Cfg<12>::PER_WAVE;                                                        \
-    ensure_lds(kf_##NAME, lds_##NAME);                                                                                           \
-    auto NAME = [&] {                                                                                                            \
-        hipLaunchKernelGGL(kf_##NAME, dim3(65536 / WAVES_), dim3(64 * WAVES_), lds_##NAME, 0, (const uint16_t*)slab_b, keys, seg_off,  \
-                           seg_cnt, stride_b, mode, mode + kDynLowBits, 65536u, fault);                                          \
+    auto kf16 = wave_finish16_kernel<12, 4>;
+    const size_t lds_f16 = (size_t)4 * Finish16Cfg<12>::PER_WAVE;
+    ensure_lds(kf16, lds_f16);
+    auto f16 = [&] {
+        hipLaunchKernelGGL(kf16, dim3(65536 / 4), dim3(64 * 4), lds_f16, 0, (const uint16_t*)slab_b, keys, seg_off, seg_cnt, stride_b, mode,
+                           mode + kDynLowBits, 65536u, fault);
     };
-    FIN16(f16_00_a0, 4, false, false, 0)
-    FIN16(f16_10_a0, 4, true, false, 0)
-    FIN16(f16_01_a0, 4, false, true, 0)
-    FIN16(f16_11_a0, 4, true, true, 0)
-    FIN16(f16_00_a1, 4, false, false, 1)
-    FIN16(f16_10_a1, 4, true, false, 1)
-    FIN16(f16_11_a1, 4, true, true, 1)
-    FIN16(f16_10_a1_w8, 8, true, false, 1)
     PERSIST(512, 32, 2, 2, 0, 2, 0, f_old)
-    PERSIST(512, 32, 2, 2, 0, 2, 0, f16_00_a0)
-    PERSIST(512, 32, 2, 2, 0, 2, 0, f16_10_a0)
-    PERSIST(512, 32, 2, 2, 0, 2, 0, f16_01_a0)
-    PERSIST(512, 32, 2, 2, 0, 2, 0, f16_11_a0)
-    PERSIST(512, 32, 2, 2, 0, 2, 0, f16_00_a1)
-    PERSIST(512, 32, 2, 2, 0, 2, 0, f16_10_a1)
-    PERSIST(512, 32, 2, 2, 0, 2, 0, f16_11_a1)
-    PERSIST(512, 32, 2, 2, 0, 2, 0, f16_10_a1_w8)
-    PERSIST(512, 32, 2, 0, 0, 0, 0, f16_00_a0)
+    PERSIST(512, 32, 2, 2, 0, 2, 0, f16)
     return 0;
 }
