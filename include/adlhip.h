@@ -706,6 +706,10 @@ int adlhip_generate_keys(adlhip_device* dev, int elem_kind, void* dptr, size_t n
  *                      in the last bits between two values of it (another association), never between two calls
  *   "debug.compact_grid" workgroups adlhip_compact_flagged / adlhip_compact_if_typed are launched with at most (0 [default]: 4 per
  *                      CU; larger values change nothing); tests set it to make few workgroups take many tiles
+ *   "debug.persist_grid" workgroups both persistent passes of the large keys-only sort (cursor form) are launched with, rounded up to
+ *                      a multiple of 8 (0 [default]: two per CU; at most 4096); tests set it to give every workgroup many rounds of
+ *                      tile tickets with small inputs: while it is set the passes draw their tickets at every size (at 0 only
+ *                      sorts of six rounds of tiles and more do).  The result does not depend on it
  *   "sort.net_lookback" 1 [default] / 0: the LSD passes of the large sort's safety net on whole keys are look-back passes -- the
  *                      one-sweep path's histogram, tables and tile body, taken in turns by the net's resident workgroups, four
  *                      passes at a time (u64 keys: two rounds) -- instead of count -> scan -> scatter passes with per-workgroup

@@ -842,6 +842,7 @@ int mid_sort_keys(adlhip_device* d, uint32_t* data, uint32_t* tmp, void* work, s
     pa.dst_total = 256u * L.stride; pa.start_bit = 24; pa.zero_me = state + 8194;
     pa.sample = nullptr; pa.which_digit = 0; pa.dst16 = 0;
     pa.place = nullptr; pa.status_a = nullptr; pa.pieces = 0; pa.rows_per_chain_a = 0; pa.slice = 0; pa.seg_shift = 8;
+    pa.tickets = nullptr;
     int rc = launch(d, "mid_bucket_scatter_u32", [&] {
         hipLaunchKernelGGL(ka, dim3(tiles), dim3(256), CA::LDS_BYTES, d->stream, pa);
     });
@@ -945,6 +946,10 @@ uint32_t net_wgs(const adlhip_device* d) { return d->resident_wgs >= (int)kNetWg
 // d_msd2: 256 first-pass cursors (one line each) + 65536 second-pass cursors + 64 words (flag, done, barrier, sample words, the
 // first kernel's repeat count and arrival word, net counters)
 constexpr size_t kMsd2Words = 8192 + 65536 + 64;
+// Behind them, in the same allocation: the persistent passes' nine tile-ticket counters, one 128-byte line each (flag[64 + 32 i];
+// hybrid_kernels.hpp kTileTicketWord0).  Reset on entry by msd2_sample_kernel, read by nothing else, and NOT part of the idle
+// table's region: tests/test_gpu_call_sequences.py pins that region's size (no word flag[64] to poke).
+constexpr size_t kMsd2TicketWords = (size_t)adlhip::kTileTicketCounters * adlhip::kTileTicketStride;
 uint32_t* net_stats(const adlhip_device* d) { return d->d_msd2 + 8192 + 65536 + 16; }
 
 // ---- what the handle-owned device words hold between sorts ("debug.idle_dirty"; DESIGN.md "Idle state of a handle") ----
@@ -963,6 +968,7 @@ constexpr uint32_t kDictSmallWords = (uint32_t)(sizeof(adlhip::DictBlock) / 4);
 constexpr uint32_t kDictWords = (uint32_t)((sizeof(adlhip::DictBlock) + sizeof(adlhip::BigDictBlock)) / 4);
 constexpr uint32_t kFaultWords = 16;
 static_assert(adlhip::kSampleRepeatsWord == 12 && adlhip::kSampleArriveWord == 13 && adlhip::kSampleThresholdWord == 14, "the idle table below");
+static_assert(adlhip::kTileTicketWord0 == 64 && adlhip::kTileTicketStride == 32, "the ticket counters start behind the flag's 64 words, one 128-byte line each");
 struct IdleRange {
     int region;
     uint32_t first, count;
@@ -1173,6 +1179,7 @@ int msd2_sort(adlhip_device* d, E* data, E* tmp, void* work, size_t n, int headr
     pa.src_stride = 0; pa.tiles_per_bucket = 1; pa.dst_stride = L.stride_a; pa.dst_total = 256u * L.stride_a; pa.start_bit = KEY_BITS - 8;
     pa.zero_me = nullptr; pa.sample = sample; pa.which_digit = 1; pa.dst16 = 0;
     pa.place = nullptr; pa.status_a = nullptr; pa.pieces = 0; pa.rows_per_chain_a = 0; pa.slice = 0; pa.seg_shift = 8;
+    pa.tickets = flag + adlhip::kTileTicketWord0;   // zeroed by the sample kernel above
     const uint32_t tiles_a = (uint32_t)((n + CT::TILE - 1) / CT::TILE);
     // round 4: the same pass as a persistent kernel -- 2 workgroups per CU take the tiles in turns, the next tile's keys are in
     // flight (non-temporal 16-byte buffer loads) while the current one is ranked, and no wait ever covers a tile's stores
@@ -1181,11 +1188,21 @@ int msd2_sort(adlhip_device* d, E* data, E* tmp, void* work, size_t n, int headr
     const bool persist = d->persist && (size_t)256 * L.stride_a * sizeof(E) < (size_t(1) << 32) - (1u << 20) &&
                          (size_t)L.slots * L.stride_b * (slab16 ? 2 : sizeof(E)) < (size_t(1) << 32) - (1u << 20);
     using PC = adlhip::PersistCfg<E, 512, K>;
-    const uint32_t pgrid = (uint32_t)(2 * d->prop.multiProcessorCount + 7) / 8 * 8;   // a multiple of 8: workgroup % 8 = XCD
+    // a multiple of 8: workgroup % 8 = XCD ("debug.persist_grid": tests reach many rounds per workgroup with small inputs)
+    const uint32_t pgrid = (uint32_t)((d->persist_grid ? d->persist_grid : 2 * d->prop.multiProcessorCount) + 7) / 8 * 8;
+    // Tile tickets are drawn (the kernels' DYN = true) from six rounds of tiles up: all workgroups draw first at the same moment, 512
+    // deep on pass 1's counter, about 3.5 us that fewer rounds do not win back (pass 1 + pass 2, drawing from the third round on at
+    // every size, against static tickets: 24 Mi keys + 4 us, 32 Mi + 1, 40 Mi 0, 48 Mi - 6, 64 Mi - 8; profiles/tile_tickets_ab.txt).
+    // Below, the static kernels of before.  One decision for both passes: pass 2 has the tiles of pass 1 plus at most one per bucket.
+    // With "debug.persist_grid" set the tickets are drawn at every size: that is what tests set it for.
+    constexpr uint32_t kDynamicRounds = 6;
+    const bool draw = d->persist_grid != 0 || tiles_a >= kDynamicRounds * pgrid;
     if (persist) {
-        auto pk = adlhip::msd_scatter_persist_kernel<E, 512, K, 1, 4, false, 2, 0>;
-        if (ensure_lds(pk, PC::LDS_BYTES)) return ADLHIP_FAILURE;
-        rc = launch(d, k32 ? "msd2_pass1_u32" : "msd2_pass1_u64", [&] { hipLaunchKernelGGL(pk, dim3(pgrid), dim3(512), PC::LDS_BYTES, d->stream, pa); });
+        auto pk = adlhip::msd_scatter_persist_kernel<E, 512, K, 1, 4, false, 2, 0, false>;
+        auto pkd = adlhip::msd_scatter_persist_kernel<E, 512, K, 1, 4, false, 2, 0, true>;
+        if (ensure_lds(pk, PC::LDS_BYTES) || ensure_lds(pkd, PC::LDS_BYTES)) return ADLHIP_FAILURE;
+        rc = launch(d, k32 ? "msd2_pass1_u32" : "msd2_pass1_u64",
+                    [&] { hipLaunchKernelGGL(draw ? pkd : pk, dim3(pgrid), dim3(512), PC::LDS_BYTES, d->stream, pa); });
     } else {
         rc = launch(d, k32 ? "msd2_pass1_u32" : "msd2_pass1_u64", [&] { hipLaunchKernelGGL(kern, dim3(tiles_a), dim3(512), CT::LDS_BYTES, d->stream, pa); });
     }
@@ -1198,12 +1215,16 @@ int msd2_sort(adlhip_device* d, E* data, E* tmp, void* work, size_t n, int headr
     pb.sample = sample; pb.which_digit = 2; pb.seg_shift = L.seg_shift;
     pb.dst16 = slab16 ? 1 : 0;   // u32 keys: the second slab holds the low 16 bits only
     if (persist) {
-        auto pk16 = adlhip::msd_scatter_persist_kernel<E, 512, K, 2, 4, true, 2, 0>;
-        auto pkE = adlhip::msd_scatter_persist_kernel<E, 512, K, 2, 4, false, 2, 0>;
-        if (ensure_lds(pk16, PC::LDS_BYTES) || ensure_lds(pkE, PC::LDS_BYTES)) return ADLHIP_FAILURE;
+        auto pk16 = adlhip::msd_scatter_persist_kernel<E, 512, K, 2, 4, true, 2, 0, false>;
+        auto pkE = adlhip::msd_scatter_persist_kernel<E, 512, K, 2, 4, false, 2, 0, false>;
+        auto pk16d = adlhip::msd_scatter_persist_kernel<E, 512, K, 2, 4, true, 2, 0, true>;
+        auto pkEd = adlhip::msd_scatter_persist_kernel<E, 512, K, 2, 4, false, 2, 0, true>;
+        if (ensure_lds(pk16, PC::LDS_BYTES) || ensure_lds(pkE, PC::LDS_BYTES) || ensure_lds(pk16d, PC::LDS_BYTES) ||
+            ensure_lds(pkEd, PC::LDS_BYTES))
+            return ADLHIP_FAILURE;
         rc = launch(d, k32 ? "msd2_pass2_u32" : "msd2_pass2_u64", [&] {
-            if (slab16) hipLaunchKernelGGL(pk16, dim3(pgrid), dim3(512), PC::LDS_BYTES, d->stream, pb);
-            else hipLaunchKernelGGL(pkE, dim3(pgrid), dim3(512), PC::LDS_BYTES, d->stream, pb);
+            if (slab16) hipLaunchKernelGGL(draw ? pk16d : pk16, dim3(pgrid), dim3(512), PC::LDS_BYTES, d->stream, pb);
+            else hipLaunchKernelGGL(draw ? pkEd : pkE, dim3(pgrid), dim3(512), PC::LDS_BYTES, d->stream, pb);
         });
     } else {
         rc = launch(d, k32 ? "msd2_pass2_u32" : "msd2_pass2_u64", [&] {
@@ -1525,7 +1546,7 @@ int msd2s_sort(adlhip_device* d, E* data, E* tmp, void* work, size_t n, int sort
             pc.dst_stride = L.stride_b; pc.dst_total = L.slots * L.stride_b; pc.start_bit = 0; pc.zero_me = nullptr; pc.sample = nullptr;
             pc.which_digit = 2; pc.dst16 = slab16 ? 1 : 0;
             pc.place = place; pc.status_a = status_a; pc.pieces = L.pieces; pc.rows_per_chain_a = L.rows_a; pc.slice = L.slice;
-            pc.seg_shift = L.seg_shift;
+            pc.seg_shift = L.seg_shift; pc.tickets = nullptr;
             rc = launch(d, k32 ? "msd2h_pass2_u32" : "msd2h_pass2_u64", [&] {
                 hipLaunchKernelGGL(kern2, dim3(256 * L.rows_b), dim3(512), CT::LDS_BYTES, d->stream, pc);
             });
@@ -2017,8 +2038,8 @@ static int create_common(int device_idx, void* stream, bool own, adlhip_device**
     }
     // the large sort's handle-owned words (cursors, flags: 270 KB), zero between sorts -- allocated here rather than by a handle's
     // first large sort
-    if (hipMalloc(&d->d_msd2, kMsd2Words * 4) != hipSuccess ||
-        hipMemsetAsync(d->d_msd2, 0, kMsd2Words * 4, d->stream) != hipSuccess ||
+    if (hipMalloc(&d->d_msd2, (kMsd2Words + kMsd2TicketWords) * 4) != hipSuccess ||
+        hipMemsetAsync(d->d_msd2, 0, (kMsd2Words + kMsd2TicketWords) * 4, d->stream) != hipSuccess ||
         hipMemsetAsync(d->d_msd2 + 8192 + 65536 + 10, 0xff, 8, d->stream) != hipSuccess) {   // the sample's AND words: all ones when idle
         if (d->d_msd2) hipFree(d->d_msd2);
         hipFree(d->d_mid_hist);
@@ -2614,6 +2635,9 @@ int adlhip_set_param(adlhip_device* d, const char* name, int value)
     } else if (!strcmp(name, "debug.compact_grid")) {
         if (value < 0) return fail("debug.compact_grid must be >= 0");
         d->compact_grid = value;
+    } else if (!strcmp(name, "debug.persist_grid")) {
+        if (value < 0 || value > 4096) return fail("debug.persist_grid must be in [0, 4096]");
+        d->persist_grid = value;
     } else if (!strcmp(name, "debug.resident_wgs")) {
         // what the paths with a grid-wide barrier (the safety nets) and the one-workgroup-per-bucket finish may count on;
         // 0 = ask the device again.  Tests use it to stand in for a small partition.
@@ -2662,6 +2686,7 @@ int adlhip_get_param(adlhip_device* d, const char* name, int* value)
     else if (!strcmp(name, "debug.reduce_grid")) *value = d->reduce_grid;
     else if (!strcmp(name, "debug.scan_grid")) *value = d->scan_grid;
     else if (!strcmp(name, "debug.compact_grid")) *value = d->compact_grid;
+    else if (!strcmp(name, "debug.persist_grid")) *value = d->persist_grid;
     else if (!strcmp(name, "partition.lookback")) *value = d->partition_lookback;
     else if (!strcmp(name, "sort.net_lookback")) *value = d->net_lookback;
     else if (!strcmp(name, "debug.resident_wgs")) *value = d->resident_wgs;

@@ -75,6 +75,8 @@ struct adlhip_device {
     int reduce_grid = 0;                    // "debug.reduce_grid": workgroups of the reduce stage at most (0: kReduceWgsPerCu per CU)
     int scan_grid = 0;                      // "debug.scan_grid": workgroups of the scan stage at most (0: kScanWgsPerCu per CU)
     int compact_grid = 0;                   // "debug.compact_grid": workgroups of the compaction at most (0: kCompactWgsPerCu per CU)
+    int persist_grid = 0;                   // "debug.persist_grid": workgroups of the large sort's persistent passes, rounded up to a
+                                            // multiple of 8 (0: two per CU)
     adlhip::DictBlock* d_dict = nullptr;    // its dictionary and counters (handle-owned; rebuilt by every net that uses them)
     uint32_t* d_msd2 = nullptr;   // the large sort's handle-owned words, allocated with the handle: cursors of pass 1 (256, one
                                   // 128-byte line each) and pass 2 (65536), overflow flag, done counter, the safety net's barrier

@@ -70,6 +70,12 @@ __device__ __forceinline__ bool grid_barrier(uint32_t* counter, uint32_t& target
 // first instruction: set = the passes have nothing to do, the offsets kernel runs the net.
 constexpr int kSampleRepeatsWord = 12;
 constexpr int kSampleThresholdWord = 14;
+// The tile tickets of the cursor form's persistent passes (persist_kernels.hpp): nine counters behind the flag's 64 words, each on a
+// 128-byte line of its own (every workgroup loads flag[0] once per tile: not on that line) -- word kTileTicketWord0 + 32 x for the
+// pass-2 queue of XCD x, x = 8 for pass 1.  msd2_sample_kernel zeroes them; whatever a sort leaves in them is never read.
+constexpr int kTileTicketWord0 = 64;
+constexpr int kTileTicketStride = 32;   // words: one 128-byte line per counter
+constexpr int kTileTicketCounters = 9;
 __device__ __forceinline__ uint32_t large_sort_gave_up(const uint32_t* flag)
 {
     const uint32_t over = __hip_atomic_load(flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -1361,6 +1367,8 @@ struct BucketPass {
     const uint32_t* status_a;
     uint32_t pieces, rows_per_chain_a, slice;
     uint32_t seg_shift;           // second pass: width w of the second digit (see slot_to_segment); 8 otherwise
+    uint32_t* tickets;            // the persistent passes' tile-ticket counters (kTileTicketWord0; persist_kernels.hpp), zero on entry;
+                                  // no other kernel reads it
 };
 
 // Digit placement of the large keys-only sort, chosen on the device from a sample of the keys: keys that do not use their top
@@ -1502,6 +1510,8 @@ __global__ __launch_bounds__(64) void msd2_sample_kernel(const E* __restrict__ s
         fault[0] = 0u;   // the live fault word: the first kernel of every sort clears it (include/adlhip.h)
         __hip_atomic_store(flag + kSampleThresholdWord, dup_thr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
+    if (tid < kTileTicketCounters)   // the passes' tile tickets: whatever the sort before drew, and wherever it left
+        __hip_atomic_store(flag + kTileTicketWord0 + kTileTicketStride * tid, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     // (this form sorts whole keys; its offsets kernel puts the sample words back to their idle values)
     const E x0 = src[sample_position(2 * tid, n)], x1 = src[sample_position(2 * tid + 1, n)];
     sample_accumulate((unsigned long long)x0, (unsigned long long)x1, sample, flag);

@@ -7,7 +7,7 @@
 // read latency 2812 cycles with 4 waves per SIMD) and so did the pass-shaped copy without ranking (107-117 us against the
 // pass's 145-150 us at 64 Mi keys, profiles/r1_scatter_granularity_probe.txt, r2_writeout_shape_probe.txt).
 //
-// Here a workgroup stays and takes tiles g, g + G, g + 2G, ...: the keys of tile i + 1 are requested (16 bytes per lane)
+// Here a workgroup stays and takes tile after tile (by ticket, below): the keys of tile i + 1 are requested (16 bytes per lane)
 // BEFORE tile i is ranked, into a second set of registers, and are in flight through tile i's whole body; the stores of
 // tile i drain while tile i + 1 is ranked.  Barriers are LDS-only (s_waitcnt lgkmcnt(0); s_barrier) so that they do not
 // wait for the prefetch.  Two barriers per tile: the third one of the one-shot kernel (LDS free for the next tile) is
@@ -20,6 +20,19 @@
 // Pass 2 (source = the 256 bucket slabs of pass 1): tickets are (bucket, tile) pairs, and workgroup g serves only buckets with
 // bucket % 8 == g % 8 -- workgroups g and g + 8 share an XCD (speed only, never correctness), so all runs of one segment slab
 // are written through ONE L2 and abutting partial lines are completed there before they are written back.
+//
+// Tile tickets.  A queue is a range of tickets and a counter in the handle (BucketPass::tickets: one for pass 1, one per XCD for
+// pass 2, each on a 128-byte line of its own, zeroed by msd2_sample_kernel).  A workgroup's first two tickets are static (g and
+// g + G; in pass 2 g / 8 and g / 8 + G / 8 of its XCD's queue), every later one is drawn: the ticket of tile i + 2 is requested
+// during tile i by lane 0 of wave 1, through the instruction with which wave 0 requests its first cursor, consumed where the
+// cursors are, handed to all waves through LDS behind the tile's second barrier, and turned into a tile there -- so the prefetch
+// at the top of the next iteration has its address.  A workgroup that is slow, or starts late, simply draws less; with static
+// tickets (g + k G) 16 wave slots per CU were filled 13.0 (pass 1) and 12.0 (pass 2) on average (64 Mi keys).  Pass 2's tickets
+// are ordered: every bucket's FULL tiles first, then the remainder tiles, largest first (32 lanes rank the XCD's 32 remainders in
+// the prologue) -- at 64 Mi uniform keys half of the buckets hold 16 full tiles and a 17th of a few hundred keys, which as the
+// ninth round's full tiles kept a quarter of the workgroups for a whole round.  All of this is the instantiation DYN = true; sorts
+// of fewer than six rounds of tiles are launched with DYN = false, the static tickets g + k G and the code of before (adlhip.hip
+// msd2_sort: all workgroups draw first at the same moment, which costs more than few rounds win back).
 //
 // Reference behaviour: Tahoe/ClKernels/RadixSort32Kernels.cl:493-631 (SortAndScatterKernel: local sort + scatter with a
 // running per-workgroup carry); the mechanism is different throughout.
@@ -115,7 +128,9 @@ __device__ __forceinline__ void rank_batch(const E* e, uint32_t* rnk, uint32_t* 
 // WPE = waves per SIMD the launch wants resident (workgroups per CU x NT / 256): bounds the registers.
 // D16: the destination slabs hold uint16_t (a.dst16; compile-time here: a run-time test would put a branch around every store)
 // LAUX / SAUX: cache policy of the key loads / the run stores (buffer aux bits: 0 = default, 2 = nt)
-template <typename E, int NT, int K, int PASS, int WPE, bool D16, int LAUX = 0, int SAUX = 0>
+// DYN: tile tickets are drawn (header comment); false = static tickets g + k G, pass 2 bucket-major -- the code of before the
+// tickets, unchanged, which the host launches where drawing cannot win (msd2_sort: fewer than six rounds of tiles)
+template <typename E, int NT, int K, int PASS, int WPE, bool D16, int LAUX = 0, int SAUX = 0, bool DYN = false>
 __global__ __launch_bounds__(NT, WPE) void msd_scatter_persist_kernel(BucketPass<E> a)
 {
     using C = PersistCfg<E, NT, K>;
@@ -140,7 +155,7 @@ __global__ __launch_bounds__(NT, WPE) void msd_scatter_persist_kernel(BucketPass
     // Either way the decision is the same for every wave of the workgroup -- the flag can rise between two waves' loads, and a
     // workgroup of which some waves have left would go on with stale counters and tickets: one thread's (one tile ago: every wave's)
     // view goes through LDS and a barrier.
-    uint32_t* __restrict__ s_give = reinterpret_cast<uint32_t*>(smem + C::OFF_WSUM);   // [8 + 1] (the block scan's scratch: prologue only)
+    uint32_t* __restrict__ s_give = reinterpret_cast<uint32_t*>(smem + C::OFF_WSUM);   // [8 + 1 + 1]: a word per wave, the prologue's verdict, the drawn ticket (the block scan's scratch in the prologue)
     {   // (pass 1 too: the sample kernel raises the flag for keys that repeat a few thousand values)
         if (tid == 0) s_give[8] = large_sort_gave_up(a.flag);
         __syncthreads();
@@ -156,14 +171,23 @@ __global__ __launch_bounds__(NT, WPE) void msd_scatter_persist_kernel(BucketPass
     if constexpr (PASS >= 2) start_bit += 8 - (int)a.seg_shift;   // narrow second digit: the field sits 8 - w bits higher
 
     // ---- tickets ---------------------------------------------------------------------------------------------------------------
+    // A queue's tickets are 0 ... t_end - 1 (pass 2, static: the XCD's range of s_pref).  DYN: the first 2 * t_step of them are the
+    // workgroups' first TWO tiles each (no round trip in front of the first loads: a draw of every workgroup at once, in a
+    // prologue, queued 512 deep on pass 1's counter and cost 4 us at any n); every later one is drawn from the queue's counter
+    // (a.tickets, zero on entry): 2 * t_step + the old value.
+    static_assert((TILE & (TILE - 1)) == 0, "remainders by mask");
     const uint32_t G = gridDim.x, g = blockIdx.x;
     uint32_t ticket, t_end, t_step, t_origin = 0u;
+    [[maybe_unused]] uint32_t n_full = 0u;
+    [[maybe_unused]] uint32_t* t_counter = nullptr;
+    [[maybe_unused]] const uint32_t* s_rem = nullptr;
     if constexpr (PASS == 1) {
         ticket = g;
         t_end = (a.n + (uint32_t)TILE - 1u) / (uint32_t)TILE;
         t_step = G;
+        if constexpr (DYN) t_counter = a.tickets + 8 * kTileTicketStride;
     } else {
-        // permuted bucket p = (b % 8) * 32 + b / 8: the buckets of one XCD are consecutive
+        // permuted bucket p = (b % 8) * 32 + b / 8: the buckets of one XCD are consecutive.  DYN: s_pref counts FULL tiles only.
         uint32_t* s_wsum = reinterpret_cast<uint32_t*>(smem + C::OFF_WSUM);
         uint32_t tiles = 0u;
         if (tid < 256) {
@@ -171,7 +195,8 @@ __global__ __launch_bounds__(NT, WPE) void msd_scatter_persist_kernel(BucketPass
             uint32_t cnt = a.src_counts[b << a.src_count_shift];
             if (cnt > a.src_stride) cnt = a.src_stride;   // the bucket overflowed: the flag is set, only stay in bounds
             s_bcnt[tid] = cnt;
-            tiles = (cnt + (uint32_t)TILE - 1u) / (uint32_t)TILE;
+            if constexpr (DYN) tiles = cnt / (uint32_t)TILE;
+            else tiles = (cnt + (uint32_t)TILE - 1u) / (uint32_t)TILE;
         }
         uint32_t total;
         const uint32_t ex = block_excl_scan_u32<NT>(tiles, s_wsum, &total);
@@ -180,9 +205,34 @@ __global__ __launch_bounds__(NT, WPE) void msd_scatter_persist_kernel(BucketPass
         __syncthreads();
         const uint32_t x = g & 7u;
         t_origin = 32u * x;
-        ticket = s_pref[t_origin] + (g >> 3);
-        t_end = s_pref[t_origin + 32u];
-        t_step = G >> 3;
+        if constexpr (DYN) {
+            // the XCD's remainder tiles, largest first (equal ones by bucket): 32 lanes rank their bucket's remainder among the 32.
+            // The list of (permuted) buckets takes the place of the NEXT XCD's 32 counts, which this workgroup never reads; its
+            // length goes into a spare word behind the prefix.
+            uint32_t* rem_list = s_bcnt + 32u * ((x + 1u) & 7u);
+            s_rem = rem_list;
+            if (tid < 32) {
+                const uint32_t r = s_bcnt[t_origin + (uint32_t)tid] & (uint32_t)(TILE - 1);
+                uint32_t rank = 0u;
+                for (uint32_t q = 0u; q < 32u; ++q) {
+                    const uint32_t rq = s_bcnt[t_origin + q] & (uint32_t)(TILE - 1);
+                    rank += (rq > r || (rq == r && q < (uint32_t)tid)) ? 1u : 0u;
+                }
+                if (r) rem_list[rank] = t_origin + (uint32_t)tid;   // (empty remainders rank behind all others)
+                const uint32_t n_rem = (uint32_t)__popcll(__ballot(r != 0u));
+                if (tid == 0) s_pref[257] = n_rem;
+            }
+            __syncthreads();
+            ticket = g >> 3;
+            n_full = s_pref[t_origin + 32u] - s_pref[t_origin];
+            t_end = n_full + s_pref[257];
+            t_step = G >> 3;
+            t_counter = a.tickets + x * kTileTicketStride;
+        } else {
+            ticket = s_pref[t_origin] + (g >> 3);
+            t_end = s_pref[t_origin + 32u];
+            t_step = G >> 3;
+        }
     }
     if (ticket >= t_end) return;
 
@@ -193,6 +243,31 @@ __global__ __launch_bounds__(NT, WPE) void msd_scatter_persist_kernel(BucketPass
             const uint32_t left = a.n - r.base;
             r.valid = left < (uint32_t)TILE ? left : (uint32_t)TILE;
             r.cursor_base = 0u;
+        } else if constexpr (DYN) {
+            uint32_t p, off;
+            if (t < n_full) {
+                // the bucket (of this XCD's 32) whose full tiles include number T: s_pref[p] <= T < s_pref[p + 1]
+                const uint32_t T = s_pref[t_origin] + t;
+                p = t_origin;
+#pragma unroll
+                for (uint32_t s = 16u; s >= 1u; s >>= 1)
+                    if (s_pref[p + s] <= T) p += s;
+                off = (T - s_pref[p]) * (uint32_t)TILE;
+                r.valid = (uint32_t)TILE;
+            } else {
+                p = s_rem[t - n_full];
+                const uint32_t cnt = s_bcnt[p];
+                off = cnt & ~(uint32_t)(TILE - 1);
+                r.valid = cnt - off;
+            }
+            // (what comes out of LDS sits in vector registers: a tile base the compiler cannot prove uniform turns every buffer load
+            // of the tile into a loop over the distinct resources)
+            p = (uint32_t)__builtin_amdgcn_readfirstlane((int)p);
+            off = (uint32_t)__builtin_amdgcn_readfirstlane((int)off);
+            r.valid = (uint32_t)__builtin_amdgcn_readfirstlane((int)r.valid);
+            const uint32_t b = ((p & 31u) << 3) | (p >> 5);
+            r.base = b * a.src_stride + off;
+            r.cursor_base = b * 256u;
         } else {
             // the bucket (of this XCD's 32) whose tiles include ticket t: s_pref[p] <= t < s_pref[p + 1]
             uint32_t p = t_origin;
@@ -216,6 +291,11 @@ __global__ __launch_bounds__(NT, WPE) void msd_scatter_persist_kernel(BucketPass
     // meant to avoid.  So: tiles load with 16-byte BUFFER loads whose resource ends at the tile's last element (what lies beyond
     // reads as zero, no branch); the write-out is K unrolled buffer stores, and a position beyond the tile's elements gets an
     // offset outside the destination resource (the hardware drops the store).
+    // What the compiler made of it when this was last built (every u32 and u64 instantiation, static and drawing): ONE wait for
+    // vector memory inside the loop, s_waitcnt vmcnt(0) where the cursors are consumed -- in front of the tile's stores, with the
+    // prefetch long complete --, and none at the loop's bottom.  No scratch, except pass 1 of u32 keys: wave 0's four 64-bit
+    // cursor addresses are spilled (28 bytes per lane static, 32 drawing) and reloaded in front of the cursor atomics, each
+    // reload with a vmcnt(0) of its own, which there waits for the prefetch and nothing else.
     auto load_tile = [&](const PersistTile& t, E(&e)[K]) {
         // (the thread's tile position is hidden from loop-invariant code motion: the compiler otherwise keeps K addresses per phase
         // in registers across the whole tile loop, and the kernel spills)
@@ -250,18 +330,31 @@ __global__ __launch_bounds__(NT, WPE) void msd_scatter_persist_kernel(BucketPass
     E cur[K], nxt[K];
     PersistTile tc = tile_of(ticket), tn{0u, 0u, 0u};
     load_tile(tc, cur);
+    static_assert(NW >= 2, "wave 1 draws the tickets");
 #pragma unroll
     for (int j = 0; j < K; ++j) asm volatile("" : "+v"(cur[j]));
     uint32_t flag_prev = 0u;   // the overflow flag as this wave loaded it during the previous tile
+    // A ticket becomes a tile (LDS look-ups in pass 2) where no vector-memory result is outstanding -- here, and behind a tile's
+    // second barrier: at the loop's top the look-up's registers once were the prefetch's, and the compiler waited for them there
+    // with a count that let the previous tile's stores drain first.  (The second ticket is static.)
+    if constexpr (DYN) {
+        if (ticket + t_step < t_end) tn = tile_of(ticket + t_step);
+    }
     for (;;) {
-        const uint32_t ticket_n = ticket + t_step;
-        const bool has_next = ticket_n < t_end;
+        [[maybe_unused]] uint32_t ticket_n = 0u;
+        bool has_next;
+        if constexpr (DYN) {
+            has_next = tn.valid != 0u;
+        } else {
+            ticket_n = ticket + t_step;
+            has_next = ticket_n < t_end;
+        }
         // the overflow flag, requested with the next tile's keys (one more countable vector-memory operation in front of this
-        // tile's stores: the wait at the bottom stays s_waitcnt vmcnt(K)) and looked at ONE TILE LATER, behind that tile's first
-        // barrier: by then it has long arrived, and every wave sees every wave's view
+        // tile's stores) and looked at ONE TILE LATER, behind that tile's first barrier: by then it has long arrived, and every
+        // wave sees every wave's view
         const uint32_t flag_now = __hip_atomic_load(a.flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if (has_next) {
-            tn = tile_of(ticket_n);
+            if constexpr (!DYN) tn = tile_of(ticket_n);
             load_tile(tn, nxt);   // in flight through the whole body below
         }
         const uint32_t valid = tc.valid;
@@ -341,14 +434,26 @@ __global__ __launch_bounds__(NT, WPE) void msd_scatter_persist_kernel(BucketPass
             *reinterpret_cast<u32x2*>(my_wpos + 4 * lane) = packed;
         }
         // ---- wave 0: reserve room for the tile's runs (requested now, consumed after the scatter) -----------------------------------
+        // ---- wave 1, lane 0: the ticket of the tile after the next one, the same way -- and through the SAME instruction as wave 0's
+        // first cursor: a second atomic into at4.x on a path of its own makes the compiler wait where the two paths join, an atomic
+        // on an address it can prove uniform is turned into a wave reduction that waits at once.  Drawn while this workgroup has a
+        // next tile (by the lane's operand: no branch); what is drawn from an empty queue is no ticket (>= t_end), and a queue
+        // that is empty stays empty.
         u32x4 at4 = {0u, 0u, 0u, 0u};
-        if (w == 0) {
+        if (DYN ? w <= 1 : w == 0) {
             uint32_t* cp = a.cursors + ((size_t)(tc.cursor_base + 4u * (uint32_t)lane) << a.cursor_shift);
             const size_t step = (size_t)1 << a.cursor_shift;
-            if (cnt4.x) at4.x = __hip_atomic_fetch_add(cp + 0 * step, cnt4.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (cnt4.y) at4.y = __hip_atomic_fetch_add(cp + 1 * step, cnt4.y, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (cnt4.z) at4.z = __hip_atomic_fetch_add(cp + 2 * step, cnt4.z, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (cnt4.w) at4.w = __hip_atomic_fetch_add(cp + 3 * step, cnt4.w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            u32x4 add4 = cnt4;
+            if constexpr (DYN) {
+                if (w == 1) {
+                    cp = t_counter;
+                    add4 = u32x4{lane == 0 && has_next ? 1u : 0u, 0u, 0u, 0u};
+                }
+            }
+            if (add4.x) at4.x = __hip_atomic_fetch_add(cp + 0 * step, add4.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (add4.y) at4.y = __hip_atomic_fetch_add(cp + 1 * step, add4.y, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (add4.z) at4.z = __hip_atomic_fetch_add(cp + 2 * step, add4.z, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (add4.w) at4.w = __hip_atomic_fetch_add(cp + 3 * step, add4.w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
         // ---- scatter into tile-sorted order ------------------------------------------------------------------------------------------
         {
@@ -386,7 +491,16 @@ __global__ __launch_bounds__(NT, WPE) void msd_scatter_persist_kernel(BucketPass
             go.w = (d0 + 3u) * a.dst_stride + at4.w - toff4.w;
             *reinterpret_cast<u32x4*>(s_goff + 4 * lane) = go * SC;
         }
+        if constexpr (DYN) {
+            if (w == 1 && lane == 0) s_give[9] = 2u * t_step + at4.x;
+        }
         lds_barrier();
+        [[maybe_unused]] PersistTile tnn{0u, 0u, 0u};
+        if constexpr (DYN) {
+            // (wave 1 writes the word again behind the NEXT tile's first barrier, which every wave reaches after this read)
+            const uint32_t ticket_nn = (uint32_t)__builtin_amdgcn_readfirstlane((int)s_give[9]);
+            if (has_next && ticket_nn < t_end) tnn = tile_of(ticket_nn);
+        }
         // ---- write-out: consecutive lanes -> consecutive tile positions -> contiguous runs per digit ----------------------------------
         {
             const uint32_t tsc = tid_v * SC;
@@ -421,14 +535,16 @@ __global__ __launch_bounds__(NT, WPE) void msd_scatter_persist_kernel(BucketPass
         flag_prev = flag_now;
         // (no barrier here: the next tile touches s_elems / s_goff / the positions only behind ITS first barrier, which every wave
         // reaches after its write-out; the wave's own counters are read by the other waves before this tile's second barrier)
-        // the prefetched keys become the current ones: s_waitcnt vmcnt(K) -- the K stores above stay in flight
+        // the prefetched keys become the current ones; the K stores above stay in flight (the keys were waited for where the cursors
+        // were: the compiler this was last built with puts no wait here at all, a counted one, vmcnt(K), is the most it may need)
 #pragma unroll
         for (int j = 0; j < K; ++j) {
             cur[j] = nxt[j];
             asm volatile("" : "+v"(cur[j]));
         }
         tc = tn;
-        ticket = ticket_n;
+        if constexpr (DYN) tn = tnn;
+        else ticket = ticket_n;
     }
 }
 
