@@ -77,6 +77,15 @@ class TorchSorter:
         if t.numel() >= 1 << 32:
             raise ValueError("TorchSorter: fewer than 2^32 elements")
 
+    @staticmethod
+    def _aligned(t):
+        """t contiguous and on a 16-byte boundary, as the ABI wants its inputs: a copy only for a strided input or for a view that
+        starts at an odd offset (t[1:]); the input is never written"""
+        src = t.contiguous()
+        if src.data_ptr() % 16:
+            src = src.clone()
+        return src
+
     def _wrap(self, t, dtype):
         b = Buffer(dtype=dtype)
         b.setRawPtr(self.device, t.data_ptr(), t.numel())
@@ -87,7 +96,7 @@ class TorchSorter:
         if torch.cuda.current_stream(self.torch_device).cuda_stream != self.raw_stream:
             raise RuntimeError("TorchSorter: bound to the stream that was current at construction; another stream is current now")
         n = t.numel()
-        src = t.contiguous()           # (a copy only for a strided input; the sort never writes its input)
+        src = self._aligned(t)
         values = torch.empty(n, dtype=t.dtype, device=t.device) if want_values else None
         if n == 0:
             return values, torch.empty(0, dtype=torch.int64, device=t.device)
@@ -114,7 +123,7 @@ class TorchSorter:
         values = torch.empty(k, dtype=t.dtype, device=t.device)
         if k == 0:
             return values, torch.empty(0, dtype=torch.int64, device=t.device)
-        src = t.contiguous()
+        src = self._aligned(t)
         npdt = _NP_DTYPE[t.dtype]
         idx32 = torch.empty(k, dtype=torch.int32, device=t.device)   # uint32 positions in an int32 tensor
         self.pprims.topk(self.device, self._wrap(src, npdt), n, k, descending=bool(largest), keysOut=self._wrap(values, npdt),
@@ -147,7 +156,7 @@ class TorchSorter:
         values = torch.empty(shape, dtype=t.dtype, device=t.device)
         if k == 0 or rows == 0:
             return values, torch.empty(shape, dtype=torch.int64, device=t.device)
-        src = t.contiguous()
+        src = self._aligned(t)         # (the base pointer only: rows may start anywhere)
         npdt = _NP_DTYPE[t.dtype]
         idx32 = torch.empty(shape, dtype=torch.int32, device=t.device)   # uint32 columns in an int32 tensor
         self.pprims.topkRows(self.device, self._wrap(src, npdt), rows, cols, k, descending=bool(largest),
@@ -170,10 +179,7 @@ class TorchSorter:
             raise ValueError("TorchSorter: fewer than 2^32 elements")
         if torch.cuda.current_stream(self.torch_device).cuda_stream != self.raw_stream:
             raise RuntimeError("TorchSorter: bound to the stream that was current at construction; another stream is current now")
-        flat = t.contiguous().reshape(-1)
-        if flat.data_ptr() % 16:
-            flat = flat.clone()
-        return flat
+        return self._aligned(t).reshape(-1)
 
     def unique(self, t, return_inverse=False, return_counts=False):
         """What torch.unique(t, sorted=True, return_inverse=..., return_counts=...) returns (dim=None): t of any number of dimensions is
@@ -333,10 +339,7 @@ class TorchSorter:
             raise ValueError("TorchSorter: fewer than 2^32 elements")
         if torch.cuda.current_stream(self.torch_device).cuda_stream != self.raw_stream:
             raise RuntimeError("TorchSorter: bound to the stream that was current at construction; another stream is current now")
-        flat = mask.contiguous().reshape(-1)
-        if flat.data_ptr() % 16:
-            flat = flat.clone()
-        return flat
+        return self._aligned(mask).reshape(-1)
 
     def _compact_flagged(self, what, t, mask, partition, want_index):
         """(items or None, int64 positions or None, S) of the flagged compaction of t (None: positions only) by mask"""

@@ -597,6 +597,18 @@ def test_torch_sorter_topk_matches_torch(sorter, dtype_name, largest):
     values, indices = sorter.topk(half, 100, largest=largest)
     assert torch.equal(values, torch.topk(half, 100, largest=largest).values)
     assert torch.equal(indices, torch.sort(half, descending=largest, stable=True).indices[:100])
+    for view in (t[1:], t[3:]):   # contiguous views that start at an odd offset (the ABI wants 16-byte alignment)
+        assert view.is_contiguous() and view.data_ptr() % 16
+        view_order = torch.sort(view, descending=largest, stable=True).indices
+        for k in (1, 100, view.numel()):
+            values, indices = sorter.topk(view, k, largest=largest)
+            assert torch.equal(values, torch.topk(view, k, largest=largest, sorted=True).values)
+            assert torch.equal(indices, view_order[:k])
+    values, indices = sorter.topk(t[1:1], 0, largest=largest)   # empty, at an odd offset
+    assert values.numel() == 0 and indices.numel() == 0 and indices.dtype == torch.int64 and values.dtype == dtype
+    with pytest.raises(ValueError):
+        sorter.topk(t[1:1], 1)
+    assert torch.equal(t, keep), "the input was changed"
     values, indices = sorter.topk(t, 0, largest=largest)
     assert values.numel() == 0 and indices.numel() == 0 and indices.dtype == torch.int64 and values.dtype == dtype
     with pytest.raises(ValueError):

@@ -779,6 +779,20 @@ def test_torch_sorter_topk_rows_matches_torch(sorter, dtype_name, largest):
     assert torch.equal(values, torch.topk(tt, 20, dim=-1, largest=largest).values)
     assert torch.equal(indices, torch.sort(tt, dim=-1, descending=largest, stable=True).indices[..., :20])
     assert torch.equal(base, keep), "the input was changed"
+    # contiguous views that start at an odd offset (the ABI wants the base pointer on 16 bytes), and a view strided by columns
+    m = _torch_input(torch, dtype, (65, 33))
+    keep = m.clone()
+    assert m[1:].is_contiguous() and m[1:].data_ptr() % 16 and not m[:, 1:].is_contiguous()
+    for view in (m[1:], m[3:], m[:, 1:], m[1:, 1:]):
+        order = torch.sort(view, dim=-1, descending=largest, stable=True).indices
+        for k in (1, 7, view.shape[-1]):
+            values, indices = sorter.topk_rows(view, k, largest=largest)
+            assert values.shape == (view.shape[0], k) and indices.shape == (view.shape[0], k)
+            assert torch.equal(values, torch.topk(view, k, dim=-1, largest=largest, sorted=True).values)
+            assert torch.equal(indices, order[..., :k])
+    values, indices = sorter.topk_rows(m[1:1], 5, largest=largest)   # no rows, at an odd offset
+    assert values.shape == (0, 5) and indices.shape == (0, 5) and indices.dtype == torch.int64
+    assert torch.equal(m, keep), "the input was changed"
 
 
 def test_torch_sorter_topk_rows_refusals(sorter, monkeypatch):

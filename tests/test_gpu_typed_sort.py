@@ -1,6 +1,6 @@
 """Typed keys, order and argsort on the GPU (include/adlhip.h "typed keys, order, argsort"; oclradixsort_amd/torch_sort.py).
 
-Expected results come from numpy and are stated independently of the key codec's formula: a key's ordinal is its bit pattern
+Expected results come from numpy (tests/typed_shapes.py) and are stated independently of the key codec's formula: a key's ordinal is its bit pattern
 read as sign-magnitude (s = the bits as a signed integer; ordinal = s if s >= 0 else -(s & MAX) - 1) for floats, the value itself
 for integers, and the expected permutation is the stable argsort of the ordinal (descending: of the negated ordinal, which is
 exact in int64 for 4-byte keys and taken on (high, low) halves for 8-byte keys).  Everything is compared bit for bit.
@@ -15,57 +15,13 @@ import torch  # noqa: F401  (before the HIP back-end is loaded: a torch wheel th
 #                            the back-end then shares it; the other way round the process holds two runtimes and torch sees no GPU)
 
 from oclradixsort_amd import Buffer, DeviceUtils, Pprims, _lib
+from typed_shapes import ASC, DESC, SPECIALS, TYPES, expected_perm, ordinal_halves   # the expected order, from numpy
 
 pytestmark = pytest.mark.gpu
 
-ASC, DESC = 0, 1
-# name, ADLHIP_KEY_*, the element type, its unsigned twin
-TYPES = [("u32", 0, np.uint32, np.uint32), ("i32", 1, np.int32, np.uint32), ("f32", 2, np.float32, np.uint32),
-         ("u64", 3, np.uint64, np.uint64), ("i64", 4, np.int64, np.uint64), ("f64", 5, np.float64, np.uint64)]
 TYPE_IDS = [t[0] for t in TYPES]
 ORDER_IDS = ["asc", "desc"]
 SENTINELS = 64
-
-# bit patterns that matter to some reading of the bits: +-0 (0x80.. is INT_MIN too), +-smallest denormal, +-smallest normal, +-largest
-# finite, +-inf, quiet and signalling NaNs of both signs with distinct payloads, INT_MAX (a NaN), -1 (a NaN), 1, -2
-SPECIALS = {
-    4: np.array([0x00000000, 0x80000000, 0x00000001, 0x80000001, 0x00800000, 0x80800000, 0x7f7fffff, 0xff7fffff, 0x7f800000,
-                 0xff800000, 0x7fc00000, 0xffc00000, 0x7fc00123, 0xffc00123, 0x7f800001, 0xff800001, 0x7fffffff, 0xffffffff,
-                 0xfffffffe, 0x3f800000, 0xbf800000], dtype=np.uint32),
-    8: np.array([0x0000000000000000, 0x8000000000000000, 0x0000000000000001, 0x8000000000000001, 0x0010000000000000,
-                 0x8010000000000000, 0x7fefffffffffffff, 0xffefffffffffffff, 0x7ff0000000000000, 0xfff0000000000000,
-                 0x7ff8000000000000, 0xfff8000000000000, 0x7ff8000000000123, 0xfff8000000000123, 0x7ff0000000000001,
-                 0xfff0000000000001, 0x7fffffffffffffff, 0xffffffffffffffff, 0xfffffffffffffffe, 0x3ff0000000000000,
-                 0xbff0000000000000, 0x00000000ffffffff, 0x0000000100000000, 0xffffffff00000000], dtype=np.uint64),
-}
-
-
-# ---------------------------------------------------------------------------------------------
-# the expected order, from numpy
-# ---------------------------------------------------------------------------------------------
-def ordinal_halves(bits, name):
-    """(high, low) int64 arrays whose lexicographic order is the order of the keys with these bit patterns."""
-    w = bits.dtype.itemsize
-    if name[0] == "u":
-        if w == 4:
-            return bits.astype(np.int64), np.zeros(bits.size, np.int64)
-        return (bits >> np.uint64(32)).astype(np.int64), (bits & np.uint64(0xffffffff)).astype(np.int64)
-    s = bits.view(np.int32 if w == 4 else np.int64).astype(np.int64)
-    if name[0] == "f":   # sign-magnitude
-        mx = np.int64(0x7fffffff if w == 4 else 0x7fffffffffffffff)
-        s = np.where(s >= 0, s, -(s & mx) - 1)
-    if w == 4:
-        return s, np.zeros(bits.size, np.int64)
-    return s >> np.int64(32), s & np.int64(0xffffffff)
-
-
-def expected_perm(bits, name, order):
-    hi, lo = ordinal_halves(bits, name)
-    if order == DESC:
-        hi, lo = -hi, -lo
-    if bits.dtype.itemsize == 4:
-        return np.argsort(hi, kind="stable")
-    return np.lexsort((lo, hi))   # stable; the last key is the primary one
 
 
 def random_bits(udt, n, seed, few=False):
@@ -576,9 +532,55 @@ def test_torch_sorter_matches_torch_sort(sorter, dtype_name, descending):
     want_v, want_i = torch.sort(half, stable=True, descending=descending)
     assert torch.equal(values, want_v) and torch.equal(indices, want_i)
     assert torch.equal(t, keep), "the input was changed"
-    # empty
-    values, indices = sorter.sort(t[:0], descending=descending)
-    assert values.numel() == 0 and indices.numel() == 0 and indices.dtype == torch.int64
+    # contiguous views that start at an odd offset: the ABI wants 16-byte alignment, the front end sees to it
+    for view in (t[1:], t[3:]):
+        assert view.is_contiguous() and view.data_ptr() % 16
+        values, indices = sorter.sort(view, descending=descending)
+        want_v, want_i = torch.sort(view, stable=True, descending=descending)
+        assert torch.equal(values, want_v) and torch.equal(indices, want_i)
+        assert torch.equal(sorter.argsort(view, descending=descending), want_i)
+    assert torch.equal(t, keep), "the input was changed"
+    # empty, aligned and not
+    for view in (t[:0], t[1:1]):
+        values, indices = sorter.sort(view, descending=descending)
+        assert values.numel() == 0 and indices.numel() == 0 and indices.dtype == torch.int64 and values.dtype == dtype
+        assert sorter.argsort(view, descending=descending).numel() == 0
+
+
+@pytest.mark.parametrize("descending", [False, True], ids=ORDER_IDS)
+@pytest.mark.parametrize("kind", ["int64-in-1000", "float64-normal", "float64-nan30"])
+def test_torch_sorter_on_value_shaped_keys_above_one_mi(sorter, kind, descending):
+    """The torch front end against torch itself where each key dword sends its pair sort somewhere else (tests/typed_shapes.py): small
+    int64 values (two high dwords, 2001 low ones) and float64 normals (distinct low dwords, high ones under one top byte) have no NaN
+    and no -0, so values and indices are torch.sort(stable=True)'s bit for bit; with 30 % (+)NaN the finite keys are torch's and the
+    NaNs are last ascending, first descending, in index order -- where totalOrder and torch both put them."""
+    import torch
+    n = (1 << 20) + 77
+    g = torch.Generator(device="cuda").manual_seed(5)
+    if kind == "int64-in-1000":
+        t = torch.randint(-1000, 1001, (n,), dtype=torch.int64, device="cuda", generator=g)
+    else:
+        t = torch.randn(n, dtype=torch.float64, device="cuda", generator=g)
+        t = torch.where(t == 0, torch.ones_like(t), t)   # no -0
+        if kind == "float64-nan30":
+            t[torch.rand(n, device="cuda", generator=g) < 0.30] = float("nan")
+    keep = t.clone()
+    values, indices = sorter.sort(t, descending=descending)
+    want_v, want_i = torch.sort(t, stable=True, descending=descending)
+    torch.cuda.synchronize()
+    if kind != "float64-nan30":
+        assert torch.equal(values, want_v) and torch.equal(indices, want_i)
+    else:
+        nan = torch.isnan(t)
+        k = int(nan.sum())
+        assert 0.29 * n < k < 0.31 * n and not torch.signbit(t[nan]).any()
+        where_nan = torch.nonzero(nan).reshape(-1)
+        fin = slice(k, n) if descending else slice(0, n - k)
+        nans = slice(0, k) if descending else slice(n - k, n)
+        assert torch.equal(values[fin], want_v[fin]) and torch.equal(indices[fin], want_i[fin])
+        assert torch.isnan(values[nans]).all() and torch.equal(indices[nans], where_nan)
+        assert torch.isnan(want_v[nans]).all()
+    assert torch.equal(t.view(torch.int64), keep.view(torch.int64)), "the input was changed"   # (bits: a NaN equals no NaN)
 
 
 def test_torch_sorter_refuses_before_any_native_call(sorter, monkeypatch):
