@@ -179,6 +179,19 @@ public:
         return compactIf<K, u32>(device, keys, (const adl::Buffer<u32>*)0, cmp, threshold, keysOut, (adl::Buffer<u32>*)0, indexOut, n, partition);
     }
 
+    // histogram by edges: counts[b] = the keys i < n with edges[b] <= keys[i] < edges[b + 1] for b < numBins (at most
+    // ADLHIP_HISTOGRAM_MAX_RANGE_BINS), in the ascending order of sortKeys: integers by value, floats by totalOrder (-0 below +0, NaNs
+    // at the two ends).  edges holds numBins + 1 non-decreasing keys.  Keys outside the edges are ignored; includeUpper closes the
+    // last bin as numpy.histogram does.  T: int, float, long long, double, u32, u64.  keys and edges are left intact.  Enqueues
+    // and returns.  A TYPE_HOST device runs a plain loop
+    template <typename T>
+    void histogramRange(const adl::Device* device, const adl::Buffer<T>& keys, const adl::Buffer<T>& edges, adl::Buffer<u32>& counts, int n,
+                        int numBins, bool includeUpper = false);
+    // counts[v] = the keys i < n with value v for 0 <= v < numBins; negative keys and keys >= numBins are ignored.  T: int, long long,
+    // u32, u64
+    template <typename T>
+    void binCount(const adl::Device* device, const adl::Buffer<T>& keys, adl::Buffer<u32>& counts, int n, int numBins);
+
 private:
     template <typename T> int uniqueTyped(const adl::Device* device, const adl::Buffer<T>& keys, adl::Buffer<T>& uniqueOut, adl::Buffer<u32>& countsOut,
                                           int n, bool descending);

@@ -535,6 +535,54 @@ int adlhip_compact_if_typed(adlhip_device* dev, int key_type, int cmp, const voi
                             void* d_keys_out_or_null, void* d_vals_out_or_null, uint32_t* d_index_out_or_null,
                             uint32_t* d_num_selected_out, void* d_work, size_t work_bytes);
 
+/* ---- histograms: bin counts by edges and bincount (no reference counterpart) ---- */
+
+/* How many keys fall in each bin: cub's DeviceHistogram::HistogramRange, numpy.histogram with an array of edges, torch.histc and
+ * torch.bincount.
+ *
+ * Range (adlhip_histogram_range_typed).  d_edges_in holds num_bins + 1 keys of key_type in DEVICE memory, non-decreasing in the
+ *   ASCENDING order of the typed sorts -- integers by value, floats by IEEE totalOrder: -NaN < -inf < ... < -0 < +0 < ... < +inf <
+ *   +NaN.  Bin b counts the keys with edge[b] <= key < edge[b + 1]; both are unsigned comparisons of the codes that
+ *   adlhip_key_encode(key_type, ADLHIP_ORDER_ASCENDING) gives, exactly as adlhip_compact_if_typed compares: -0 is below +0, NaNs sit
+ *   at the two ends and are counted only where the edges reach them, nothing is compared as a float and nothing is divided.  Keys
+ *   outside the edges are ignored.  Repeated edges give empty bins; a key equal to a repeated edge belongs to the last of them.
+ *   include_upper == 1 closes the last bin, as numpy does: a key whose bits equal edge[num_bins] counts in the last bin b with
+ *   edge[b] < edge[num_bins] (in bin num_bins - 1 if all edges are equal).  1 <= num_bins <= ADLHIP_HISTOGRAM_MAX_RANGE_BINS: 8-byte
+ *   edges and the counters together fit LDS several times over.  Edges that are not sorted give unspecified counts and no access
+ *   outside the arrays: the search's result is always clamped to a bin or to "ignored".
+ * Bincount (adlhip_bincount_typed).  Integer key types only (U32, I32, U64, I64).  counts[v] is the number of keys with value v for
+ *   0 <= v < num_bins; negative keys and keys >= num_bins are ignored.  1 <= num_bins < 2^31.
+ *
+ * Contract, as in the neighbouring blocks: n < 2^32.  The inputs are never written.  Every one of the num_bins counters is written,
+ * with zeros where nothing fell, and nothing beyond them.  Every array and d_work are 16-byte aligned; no output may overlap an
+ * input.  n == 0 enqueues one clear of the counters and nothing else; d_keys_in, d_work and work_bytes are then not looked at (an empty
+ * array has no address to check), as in the neighbouring blocks, while everything else is checked as for any n.  A NULL pointer, a misaligned pointer, an overlap, an unknown
+ * key type (bincount: a float type), an out-of-range num_bins, an include_upper other than 0 or 1 and a work buffer one byte short
+ * (the message names the needed size) fail before anything is enqueued.  The calls enqueue and return: nothing data-dependent
+ * reaches the host, launch grids depend on n and num_bins alone, nothing is remembered between calls, all state lives in d_work --
+ * whose contents on entry are arbitrary.  No kernel waits on another workgroup or uses an atomic to global memory.  Counts are
+ * exact and identical from run to run.
+ *
+ * LDS path (range; bincount up to the limit "debug.histogram_lds_bins" reports, 8192 bins): two launches over tiles of
+ * ADLHIP_HISTOGRAM_TILE elements.  The workgroups count the keys of their chunks with LDS atomics into private tables (range mode: a
+ * branch-free binary search over the edges' codes in LDS) and store their tables as rows of d_work; a second launch sums the rows.
+ * The keys are read once.  Sorted path (bincount above the limit): a copy of the keys in d_work is sorted as unsigned numbers by
+ * what adlhip_sort_keys_typed runs, the counters are cleared, and two launches over the sorted keys turn the boundaries of the runs
+ * into counts (run heads store -i, run ends add i + 1: one writer per word per launch).
+ *
+ * Work bytes (adlhip_histogram_scratch_bytes; by_edges: 1 for the range mode, 0 for bincount), with CUs = adlhip_info.compute_units:
+ *   LDS path     G x num_bins x 4 rounded up to 256, G = 4 CUs x 2048 / num_bins kept within [2 CUs, 4 CUs]: one row per workgroup of
+ *                the largest grid, which shrinks as the bins grow (at most 16 MiB at 256 CUs); nothing proportional to n
+ *   sorted path  2 x (n keys rounded up to 256) + the work of the unsigned keys sort of n keys
+ * The value holds for the knobs as they are when it is asked. */
+#define ADLHIP_HISTOGRAM_MAX_RANGE_BINS 4096
+#define ADLHIP_HISTOGRAM_TILE 2048
+int adlhip_histogram_scratch_bytes(adlhip_device* dev, int key_type, size_t n, size_t num_bins, int by_edges, size_t* work_bytes);
+int adlhip_histogram_range_typed(adlhip_device* dev, int key_type, const void* d_keys_in, size_t n, const void* d_edges_in,
+                                 size_t num_bins, int include_upper, uint32_t* d_counts_out, void* d_work, size_t work_bytes);
+int adlhip_bincount_typed(adlhip_device* dev, int key_type, const void* d_keys_in, size_t n, size_t num_bins, uint32_t* d_counts_out,
+                          void* d_work, size_t work_bytes);
+
 /* ---- segments finished in LDS (no reference counterpart) ------------------------------------- */
 
 /* Sorts, stably and in place, every segment [d_seg_start[s], d_seg_start[s + 1]) of an array of u32 keys
@@ -706,6 +754,11 @@ int adlhip_generate_keys(adlhip_device* dev, int elem_kind, void* dptr, size_t n
  *                      in the last bits between two values of it (another association), never between two calls
  *   "debug.compact_grid" workgroups adlhip_compact_flagged / adlhip_compact_if_typed are launched with at most (0 [default]: 4 per
  *                      CU; larger values change nothing); tests set it to make few workgroups take many tiles
+ *   "debug.histogram_grid" workgroups the count kernel of adlhip_histogram_range_typed / adlhip_bincount_typed is launched with at
+ *                      most (0 [default]: the G of the histogram block; larger values change nothing); tests set it to make few
+ *                      workgroups take many tiles
+ *   "debug.histogram_lds_bins" the largest num_bins for which adlhip_bincount_typed takes the LDS path (1 .. 8192, default 8192; 0
+ *                      sets the default); tests lower it to reach the sorted path with few keys.  adlhip_get_param reports the limit
  *   "debug.persist_grid" workgroups both persistent passes of the large keys-only sort (cursor form) are launched with, rounded up to
  *                      a multiple of 8 (0 [default]: two per CU; at most 4096); tests set it to give every workgroup many rounds of
  *                      tile tickets with small inputs: while it is set the passes draw their tickets at every size (at 0 only

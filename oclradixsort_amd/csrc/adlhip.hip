@@ -2635,6 +2635,12 @@ int adlhip_set_param(adlhip_device* d, const char* name, int value)
     } else if (!strcmp(name, "debug.compact_grid")) {
         if (value < 0) return fail("debug.compact_grid must be >= 0");
         d->compact_grid = value;
+    } else if (!strcmp(name, "debug.histogram_grid")) {
+        if (value < 0) return fail("debug.histogram_grid must be >= 0");
+        d->histogram_grid = value;
+    } else if (!strcmp(name, "debug.histogram_lds_bins")) {
+        if (value < 0 || value > kHistogramLdsBinsMax) return fail("debug.histogram_lds_bins must be in [1, %d], or 0 for the default", kHistogramLdsBinsMax);
+        d->histogram_lds_bins = value ? value : kHistogramLdsBinsMax;
     } else if (!strcmp(name, "debug.persist_grid")) {
         if (value < 0 || value > 4096) return fail("debug.persist_grid must be in [0, 4096]");
         d->persist_grid = value;
@@ -2686,6 +2692,8 @@ int adlhip_get_param(adlhip_device* d, const char* name, int* value)
     else if (!strcmp(name, "debug.reduce_grid")) *value = d->reduce_grid;
     else if (!strcmp(name, "debug.scan_grid")) *value = d->scan_grid;
     else if (!strcmp(name, "debug.compact_grid")) *value = d->compact_grid;
+    else if (!strcmp(name, "debug.histogram_grid")) *value = d->histogram_grid;
+    else if (!strcmp(name, "debug.histogram_lds_bins")) *value = d->histogram_lds_bins;
     else if (!strcmp(name, "debug.persist_grid")) *value = d->persist_grid;
     else if (!strcmp(name, "partition.lookback")) *value = d->partition_lookback;
     else if (!strcmp(name, "sort.net_lookback")) *value = d->net_lookback;

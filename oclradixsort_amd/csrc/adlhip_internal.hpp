@@ -13,6 +13,9 @@
 namespace adlhip { struct DictBlock; }   // dict_build.hpp
 
 namespace adlhip_internal {
+// the largest table of the histogram's LDS path: the default and the ceiling of "debug.histogram_lds_bins".  primitives.hip asserts
+// that it is what the count kernel's LDS is sized for (adlhip::kHistLdsBins, histogram_kernels.hpp)
+constexpr int kHistogramLdsBinsMax = 8192;
 struct ProfEntry {
     uint64_t launches = 0;
     double total_ms = 0.0;
@@ -75,6 +78,8 @@ struct adlhip_device {
     int reduce_grid = 0;                    // "debug.reduce_grid": workgroups of the reduce stage at most (0: kReduceWgsPerCu per CU)
     int scan_grid = 0;                      // "debug.scan_grid": workgroups of the scan stage at most (0: kScanWgsPerCu per CU)
     int compact_grid = 0;                   // "debug.compact_grid": workgroups of the compaction at most (0: kCompactWgsPerCu per CU)
+    int histogram_grid = 0;                 // "debug.histogram_grid": workgroups of the histogram's count kernel at most (0: hist_grid_cap)
+    int histogram_lds_bins = adlhip_internal::kHistogramLdsBinsMax;   // "debug.histogram_lds_bins": bincount takes the LDS path up to this many bins
     int persist_grid = 0;                   // "debug.persist_grid": workgroups of the large sort's persistent passes, rounded up to a
                                             // multiple of 8 (0: two per CU)
     adlhip::DictBlock* d_dict = nullptr;    // its dictionary and counters (handle-owned; rebuilt by every net that uses them)

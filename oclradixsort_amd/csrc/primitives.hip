@@ -1,5 +1,5 @@
 // primitives.hip -- the host side of what is built on top of the sorts: typed keys and argsort, top-k, row-wise top-k, unique /
-// run-length encode, reduce by key, typed scans, stream compaction.  No reference counterpart.  It reaches the sorts through adlhip_internal.hpp alone (sort_elements,
+// run-length encode, reduce by key, typed scans, stream compaction, histograms.  No reference counterpart.  It reaches the sorts through adlhip_internal.hpp alone (sort_elements,
 // sort_work_bytes, soa_wide_layout) and never sees their kernels.
 #include "adlhip_internal.hpp"
 
@@ -20,9 +20,10 @@
 #include "reduce_kernels.hpp"
 #include "scan_kernels.hpp"
 #include "compact_kernels.hpp"
+#include "histogram_kernels.hpp"
 
 // instantiated in kernels_select.hip / kernels_toprows.hip / kernels_unique.hip / kernels_reduce.hip / kernels_scan.hip /
-// kernels_compact.hip; here they are only declared
+// kernels_compact.hip / kernels_histogram.hip; here they are only declared
 #ifndef ADLHIP_SINGLE_TU
 #define X(...) extern template __global__ __VA_ARGS__;
 #include "select_kernels.inc"
@@ -31,6 +32,7 @@
 #include "reduce_kernels.inc"
 #include "scan_kernels.inc"
 #include "compact_kernels.inc"
+#include "histogram_kernels.inc"
 #undef X
 #endif
 
@@ -770,6 +772,137 @@ int compact_check_partition(const char* what, int partition)
     return ADLHIP_SUCCESS;
 }
 
+// ---- histograms (histogram_kernels.hpp) ---------------------------------------------------------------------
+static_assert(ADLHIP_HISTOGRAM_TILE == adlhip::kRedTile, "the header states the tile of the count kernel");
+static_assert(ADLHIP_HISTOGRAM_MAX_RANGE_BINS == adlhip::kHistRangeWords, "the range mode's counters are sized for the public limit");
+static_assert(kHistogramLdsBinsMax == (int)adlhip::kHistLdsBins, "\"debug.histogram_lds_bins\" may ask for no more bins than the LDS of the launch holds");
+constexpr int kHistWgsPerCu = 4;   // grid of the count kernel per CU at most, while num_bins <= 2048
+
+// Workgroups of the count kernel at most: 4 per CU up to 2048 bins, then fewer in proportion -- every workgroup stores a row of
+// num_bins words and the reduce kernel reads them all -- and never less than two per CU: with one, a SIMD holds a single wave and
+// every LDS latency of the search and of the adds is exposed (measured: 4096 range bins took 5 x as long as 256).
+size_t hist_grid_cap(const adlhip_device* d, size_t num_bins)
+{
+    const size_t cus = (size_t)d->prop.multiProcessorCount, full = cus * kHistWgsPerCu;
+    return std::max(2 * cus, std::min(full, full * 2048 / num_bins));
+}
+// Work of the LDS path: [rows: one of num_bins u32 per workgroup of the largest grid], rounded up to 256 bytes
+size_t hist_rows_bytes(const adlhip_device* d, size_t num_bins)
+{
+    return align_up(hist_grid_cap(d, num_bins) * num_bins * 4, 256);
+}
+// Work of the sorted path: [S: the sorted keys, n][tmp: the sort's partner array, n keys][work of the unsigned keys sort]
+struct HistSortLayout {
+    size_t off_tmp, off_swork, swork_bytes, total;
+};
+HistSortLayout hist_sort_layout(const adlhip_device* d, size_t key_bytes, size_t n)
+{
+    HistSortLayout L;
+    L.off_tmp = align_up(n * key_bytes, 256);
+    L.off_swork = 2 * L.off_tmp;
+    L.swork_bytes = sort_work_bytes(d, key_bytes == 4 ? ADLHIP_ELEM_U32 : ADLHIP_ELEM_U64, n, 8 * (int)key_bytes, 1);
+    L.total = L.off_swork + align_up(L.swork_bytes, 256);
+    return L;
+}
+bool hist_lds_path(const adlhip_device* d, bool by_edges, size_t num_bins)
+{
+    return by_edges || num_bins <= (size_t)d->histogram_lds_bins;
+}
+size_t hist_work_bytes(const adlhip_device* d, size_t key_bytes, size_t n, size_t num_bins, bool by_edges)
+{
+    return hist_lds_path(d, by_edges, num_bins) ? hist_rows_bytes(d, num_bins) : hist_sort_layout(d, key_bytes, n).total;
+}
+
+// the LDS path on n > 0 keys: count into rows of the work buffer, sum the rows
+template <typename U, int MODE>
+int hist_lds_stage(adlhip_device* d, const U* keys, size_t n, const U* edges, int kind, size_t num_bins, int include_upper, uint32_t* counts,
+                   void* work)
+{
+    uint32_t* rows = static_cast<uint32_t*>(work);
+    size_t cap = hist_grid_cap(d, num_bins);
+    if (d->histogram_grid > 0) cap = std::min(cap, (size_t)d->histogram_grid);
+    const size_t tiles = (n + adlhip::kRedTile - 1) / adlhip::kRedTile, tpw = (tiles + cap - 1) / cap;
+    const uint32_t wgs = (uint32_t)((tiles + tpw - 1) / tpw);   // (<= cap: the rows fit hist_rows_bytes)
+    adlhip::HistArgs a;
+    a.kind = (uint32_t)kind;
+    a.num_bins = (uint32_t)num_bins;
+    a.include_upper = (uint32_t)include_upper;
+    const uint32_t words = MODE == adlhip::kHistRange ? adlhip::kHistRangeWords : adlhip::kHistLdsBins;
+    a.copies = 1;
+    while (a.copies < adlhip::kHistMaxCopies && (size_t)a.copies * 2 * num_bins <= words) a.copies *= 2;
+    a.stride = (uint32_t)num_bins | 1u;
+    a.top_step = 1;
+    while ((size_t)a.top_step * 2 <= num_bins + 1) a.top_step *= 2;
+    const size_t lds = adlhip::hist_edge_bytes<U, MODE>(a.num_bins) + (size_t)a.copies * a.stride * 4;   // (at most 49 172 bytes: 4097 8-byte edges + 4097 counters)
+    static const char* const kName[2][2] = {{"hist_count_range_k32", "hist_count_range_k64"}, {"hist_count_bins_k32", "hist_count_bins_k64"}};
+    int rc = launch(d, kName[MODE][sizeof(U) == 8], [&] {
+        hipLaunchKernelGGL((adlhip::hist_count_kernel<U, MODE>), dim3(wgs), dim3(adlhip::kSelNT), lds, d->stream, keys, (uint32_t)n, (uint32_t)tiles,
+                           (uint32_t)tpw, edges, a, rows);
+    });
+    if (rc) return rc;
+    const uint32_t rwgs = (uint32_t)((num_bins + adlhip::kHistRedBins - 1) / adlhip::kHistRedBins);
+    return launch(d, "hist_reduce", [&] {
+        hipLaunchKernelGGL(adlhip::hist_reduce_kernel, dim3(rwgs), dim3(adlhip::kSelNT), 0, d->stream, (const uint32_t*)rows, wgs, (uint32_t)num_bins,
+                           counts);
+    });
+}
+
+// the sorted path on n > 0 integer keys: negative keys are large unsigned numbers, so the unsigned order groups every value below
+// num_bins in front of everything that is ignored
+template <typename U>
+int hist_sorted_stage(adlhip_device* d, const U* keys, size_t n, size_t num_bins, uint32_t* counts, void* work)
+{
+    const HistSortLayout L = hist_sort_layout(d, sizeof(U), n);
+    char* w = static_cast<char*>(work);
+    U* sorted = reinterpret_cast<U*>(w);
+    HIPCHK(hipMemcpyAsync(sorted, keys, n * sizeof(U), hipMemcpyDeviceToDevice, d->stream));
+    int rc = sort_elements(d, sizeof(U) == 4 ? ADLHIP_ELEM_U32 : ADLHIP_ELEM_U64, sorted, w + L.off_tmp, w + L.off_swork, L.swork_bytes, n,
+                           8 * (int)sizeof(U));
+    if (rc) return rc;
+    HIPCHK(hipMemsetAsync(counts, 0, num_bins * 4, d->stream));
+    const uint32_t wgs = (uint32_t)std::min<size_t>((n + adlhip::kSelNT - 1) / adlhip::kSelNT, (size_t)d->prop.multiProcessorCount * 16);
+    rc = launch(d, sizeof(U) == 4 ? "hist_heads_k32" : "hist_heads_k64", [&] {
+        hipLaunchKernelGGL((adlhip::hist_heads_kernel<U>), dim3(wgs), dim3(adlhip::kSelNT), 0, d->stream, (const U*)sorted, (uint32_t)n,
+                           (uint32_t)num_bins, counts);
+    });
+    if (rc) return rc;
+    return launch(d, sizeof(U) == 4 ? "hist_tails_k32" : "hist_tails_k64", [&] {
+        hipLaunchKernelGGL((adlhip::hist_tails_kernel<U>), dim3(wgs), dim3(adlhip::kSelNT), 0, d->stream, (const U*)sorted, (uint32_t)n,
+                           (uint32_t)num_bins, counts);
+    });
+}
+
+// what both histogram entry points refuse before anything is enqueued; *done: nothing is left to do (n == 0: the counters are cleared)
+int hist_check(adlhip_device* d, const char* what, const TypeInfo& t, const void* keys_in, size_t n, const void* edges_in, size_t num_bins,
+               bool by_edges, uint32_t* counts, const void* work, size_t work_bytes, bool* done)
+{
+    *done = false;
+    if (typed_check_n(n)) return ADLHIP_FAILURE;
+    if (!counts) return fail("null buffer passed to %s", what);
+    if (check_aligned16(what, {counts})) return ADLHIP_FAILURE;
+    if (n == 0) {
+        *done = true;
+        HIPCHK(hipMemsetAsync(counts, 0, num_bins * 4, d->stream));
+        return ADLHIP_SUCCESS;
+    }
+    const size_t kb = n * (size_t)t.bytes, eb = by_edges ? (num_bins + 1) * (size_t)t.bytes : 0;
+    if (check_buffers(what, {{keys_in, kb, "d_keys_in"}, {edges_in, eb, "d_edges_in", by_edges}}, {{counts, num_bins * 4, "d_counts_out"}}, nullptr,
+                      work))
+        return ADLHIP_FAILURE;
+    const size_t need = hist_work_bytes(d, (size_t)t.bytes, n, num_bins, by_edges);
+    if (work_bytes < need) return fail("work buffer too small: %zu < %zu (adlhip_histogram_scratch_bytes)", work_bytes, need);
+    return ADLHIP_SUCCESS;
+}
+// key_type and num_bins of either mode
+int hist_check_mode(const char* what, int key_type, size_t num_bins, bool by_edges, TypeInfo* t)
+{
+    if (type_info("key_type", key_type, t)) return ADLHIP_FAILURE;
+    if (!by_edges && t->kind == adlhip::kKeyFloat) return fail("%s: integer key types only (U32, I32, U64, I64), got %d", what, key_type);
+    const size_t most = by_edges ? (size_t)ADLHIP_HISTOGRAM_MAX_RANGE_BINS : ((size_t)1 << 31) - 1;
+    if (num_bins < 1 || num_bins > most) return fail("%s: num_bins must be in [1, %zu], got %zu", what, most, num_bins);
+    return ADLHIP_SUCCESS;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1144,6 +1277,47 @@ int adlhip_compact_if_typed(adlhip_device* d, int key_type, int cmp, const void*
     const adlhip::CompactPred pr = {(uint32_t)t.kind, (uint32_t)cmp, code};
     return ADLHIP_BY_WIDTH(t.bytes, K, ADLHIP_BY_WIDTH(value_bytes ? value_bytes : 4, V, compact_stage<K, V>(d, (const K*)keys_in, pr,
                            (const V*)vals_in, n, partition, (K*)keys_out, (V*)vals_out, index_out, num_selected_out, work)));
+}
+
+// ---- histograms --------------------------------------------------------------------------------------
+int adlhip_histogram_scratch_bytes(adlhip_device* d, int key_type, size_t n, size_t num_bins, int by_edges, size_t* work_bytes)
+{
+    if (!d) return fail("null device handle");
+    if (by_edges != 0 && by_edges != 1) return fail("histogram scratch: by_edges must be 0 (bincount) or 1 (range), got %d", by_edges);
+    TypeInfo t;
+    if (hist_check_mode("histogram scratch", key_type, num_bins, by_edges != 0, &t) || typed_check_n(n)) return ADLHIP_FAILURE;
+    if (work_bytes) *work_bytes = hist_work_bytes(d, (size_t)t.bytes, n, num_bins, by_edges != 0);
+    return ADLHIP_SUCCESS;
+}
+
+int adlhip_histogram_range_typed(adlhip_device* d, int key_type, const void* keys_in, size_t n, const void* edges_in, size_t num_bins,
+                                 int include_upper, uint32_t* counts_out, void* work, size_t work_bytes)
+{
+    const char* what = "histogram range";
+    TypeInfo t;
+    bool done;
+    if (bind(d) || hist_check_mode(what, key_type, num_bins, true, &t)) return ADLHIP_FAILURE;
+    if (include_upper != 0 && include_upper != 1) return fail("%s: include_upper must be 0 or 1, got %d", what, include_upper);
+    if (!edges_in) return fail("null buffer passed to %s", what);
+    if (check_aligned16(what, {edges_in})) return ADLHIP_FAILURE;
+    if (overlaps(counts_out, num_bins * 4, edges_in, (num_bins + 1) * (size_t)t.bytes)) return fail("%s: d_counts_out must not overlap d_edges_in", what);
+    if (const int rc = hist_check(d, what, t, keys_in, n, edges_in, num_bins, true, counts_out, work, work_bytes, &done); rc || done) return rc;
+    return ADLHIP_BY_WIDTH(t.bytes, U, hist_lds_stage<U, adlhip::kHistRange>(d, (const U*)keys_in, n, (const U*)edges_in, t.kind, num_bins, include_upper,
+                                                                            counts_out, work));
+}
+
+int adlhip_bincount_typed(adlhip_device* d, int key_type, const void* keys_in, size_t n, size_t num_bins, uint32_t* counts_out, void* work,
+                          size_t work_bytes)
+{
+    const char* what = "bincount";
+    TypeInfo t;
+    bool done;
+    if (bind(d) || hist_check_mode(what, key_type, num_bins, false, &t)) return ADLHIP_FAILURE;
+    if (const int rc = hist_check(d, what, t, keys_in, n, nullptr, num_bins, false, counts_out, work, work_bytes, &done); rc || done) return rc;
+    if (hist_lds_path(d, false, num_bins))
+        return ADLHIP_BY_WIDTH(t.bytes, U, hist_lds_stage<U, adlhip::kHistBincount>(d, (const U*)keys_in, n, (const U*)nullptr, t.kind, num_bins, 0,
+                                                                                   counts_out, work));
+    return ADLHIP_BY_WIDTH(t.bytes, U, hist_sorted_stage<U>(d, (const U*)keys_in, n, num_bins, counts_out, work));
 }
 
 }  // extern "C"

@@ -18,6 +18,8 @@
     p.scanByKey(device, keys, dst, src, n, op="sum")       # the same within every run of keys that are already grouped
     p.compactFlagged(device, flags, n, items=buf)          # -> CompactResult: the items whose flag byte is non-zero, in input order
     p.compactIf(device, keys, n, "lt", x, values=buf)      # -> CompactResult: the keys (and their values) that compare so with x
+    p.histogramRange(device, keys, n, edges, num_bins)     # -> Buffer(uint32): the keys per bin [edges[b], edges[b + 1])
+    p.binCount(device, keys, n, num_bins)                  # -> Buffer(uint32): the keys per value 0 .. num_bins - 1
 
 Like the reference object it owns lazily grown device scratch (m_u32WorkBuffer[0] = ping-pong data
 buffer, m_u32WorkBuffer[1] = histogram table; Pprims.h:44-45, Pprims.cpp:226-232, :332-337) and must be
@@ -60,6 +62,11 @@ CMP_OPS = {"lt": 0, "le": 1, "gt": 2, "ge": 3, "eq": 4, "ne": 5, "<": 0, "<=": 1
 # the number of selected elements; items (compactIf: the keys), values and index have n elements of which the first S are written --
 # all n with partition=True, the rejected elements behind the selected ones.
 CompactResult = collections.namedtuple("CompactResult", "items values index count")
+
+# ADLHIP_HISTOGRAM_MAX_RANGE_BINS and ADLHIP_HISTOGRAM_TILE (include/adlhip.h, "histograms"): the most bins histogramRange takes, and
+# the elements of a tile of its count kernel (tests place their sizes around it)
+HISTOGRAM_MAX_RANGE_BINS = 4096
+HISTOGRAM_TILE = 2048
 
 
 class Pprims:
@@ -616,6 +623,69 @@ class Pprims:
         outs, idx, cnt = self._compact(what, device, n, keys, [("keys", keys, keysOut), ("values", values, valuesOut)], indexOut, countOut,
                                        call)
         return CompactResult(outs[0], outs[1], idx, cnt)
+
+    # -- histograms (no reference counterpart; include/adlhip.h adlhip_histogram_range_typed / adlhip_bincount_typed)
+    def _histogram(self, what, device, keys, n, num_bins, by_edges, integers_only, countsOut, call):
+        if device is None:
+            raise AdlHipError("%s needs a device" % what)
+        kt = self._key_type(keys, what)
+        if integers_only and np.dtype(keys.dtype).kind == "f":
+            raise AdlHipError("%s: integer keys only (uint32, int32, uint64, int64), got %s" % (what, keys.dtype))
+        n, num_bins = int(n), int(num_bins)
+        if n < 0 or keys.getSize() < n:
+            raise AdlHipError("%s: n = %d outside [0, %d]" % (what, n, keys.getSize()))
+        most = HISTOGRAM_MAX_RANGE_BINS if by_edges else (1 << 31) - 1
+        if num_bins < 1 or num_bins > most:
+            raise AdlHipError("%s: num_bins = %d outside [1, %d]" % (what, num_bins, most))
+        if countsOut is not None and (np.dtype(countsOut.dtype) != np.uint32 or countsOut.getSize() < num_bins):
+            raise AdlHipError("%s: countsOut must hold num_bins uint32 elements" % what)
+        lib = _lib.load()
+        wb = ctypes.c_size_t()
+        check(lib.adlhip_histogram_scratch_bytes(device._h, kt, n, num_bins, 1 if by_edges else 0, ctypes.byref(wb)),
+              "adlhip_histogram_scratch_bytes")
+        self._scratch(device, 0, wb.value)
+        own = countsOut is None
+        if own:
+            countsOut = Buffer(device, num_bins, np.uint32)
+        try:
+            check(call(lib, kt, n, num_bins, countsOut.ptr()), what)
+        except AdlHipError:
+            if own:
+                countsOut.release()
+            raise
+        return countsOut
+
+    def histogramRange(self, device, keys, n, edges, num_bins=None, include_upper=False, countsOut=None):
+        """counts[b] = the keys i < n with edges[b] <= keys[i] < edges[b + 1], for the num_bins bins that the first num_bins + 1 elements
+        of `edges` (a device Buffer of the keys' type; default: all of it) bound -> a uint32 Buffer of num_bins counters (countsOut, or
+        a new one).  The edges are non-decreasing in the order of sortKeys -- integers by value, floats by totalOrder (-0 below +0,
+        NaNs at the two ends) -- and both comparisons are made in that order, on bits: nothing is compared as a float.  Keys outside
+        the edges are ignored; a key equal to repeated edges belongs to the last of them.  include_upper=True closes the last bin as
+        numpy.histogram does: a key equal to the last edge counts in the last bin that is not empty by construction.  At most
+        HISTOGRAM_MAX_RANGE_BINS bins.  The inputs are left intact.  Enqueues and returns."""
+        what = "histogramRange"
+        if edges is None or not hasattr(edges, "getSize"):
+            raise AdlHipError("%s: edges must be a device Buffer of the keys' type" % what)
+        if keys is not None and np.dtype(edges.dtype) != np.dtype(keys.dtype):
+            raise AdlHipError("%s: edges are %s, keys %s" % (what, edges.dtype, keys.dtype))
+        if num_bins is None:
+            num_bins = edges.getSize() - 1
+        if edges.getSize() < int(num_bins) + 1:
+            raise AdlHipError("%s: %d bins need %d edges, got %d" % (what, num_bins, int(num_bins) + 1, edges.getSize()))
+
+        def call(lib, kt, n_, bins, counts):
+            return lib.adlhip_histogram_range_typed(device._h, kt, keys.ptr(), n_, edges.ptr(), bins, 1 if include_upper else 0, counts,
+                                                    self.m_work.ptr(), self.m_work.getSize())
+        return self._histogram(what, device, keys, n, num_bins, True, False, countsOut, call)
+
+    def binCount(self, device, keys, n, num_bins, countsOut=None):
+        """counts[v] = the keys i < n with value v, for 0 <= v < num_bins -> a uint32 Buffer of num_bins counters (countsOut, or a new
+        one).  Integer keys only; negative keys and keys >= num_bins are ignored.  num_bins < 2^31: up to the LDS limit
+        (device.getParam("debug.histogram_lds_bins"), 8192) one read of the keys, above it a sort of a copy of them.  The keys are
+        left intact.  Enqueues and returns."""
+        def call(lib, kt, n_, bins, counts):
+            return lib.adlhip_bincount_typed(device._h, kt, keys.ptr(), n_, bins, counts, self.m_work.ptr(), self.m_work.getSize())
+        return self._histogram("binCount", device, keys, n, num_bins, False, True, countsOut, call)
 
     def copy(self, device, dst, src, n):
         """Pprims::copy (Pprims.cpp:31-67, commented out in the reference): first n elements of src -> dst."""

@@ -15,6 +15,7 @@ back-end on torch's own stream.
     sel = s.masked_select(t, mask); pos = s.nonzero(mask)                        # torch.masked_select / torch.nonzero (bool or uint8 mask)
     sel = s.select_if(t, "lt", x)                                                # t[t < x], in totalOrder; also "le", "gt", "ge", "eq", "ne"
     out, count = s.partition(t, mask)                                            # the selected elements, then the others; both in input order
+    c = s.bincount(t); c = s.histogram(t, edges); c = s.histc(t, 100, 0.0, 1.0)  # torch.bincount / numpy.histogram(t, edges)[0] / the same on linspace edges
     s.close()
 
 Always out of place and always stable.  The ONE difference from `torch.sort(t, stable=True)`: floats are ordered by
@@ -437,6 +438,73 @@ class TorchSorter:
         if return_indices:
             out += (idx32[:s].to(torch.int64) & 0xffffffff,)
         return out if len(out) > 1 else out[0]
+
+    def _counts(self, buf_call, num_bins, dev):
+        """int64 counts of num_bins bins from a call that fills a uint32 Buffer over an int32 tensor"""
+        c32 = torch.empty(num_bins, dtype=torch.int32, device=dev)   # uint32 counters in an int32 tensor
+        buf_call(self._wrap(c32, np.uint32))
+        self.device.checkFault()
+        return c32.to(torch.int64) & 0xffffffff
+
+    def bincount(self, t, num_bins=None):
+        """torch.bincount(t) for a 1-D int32 / int64 tensor: int64 counts, counts[v] = the elements equal to v for 0 <= v < num_bins.
+        num_bins omitted: max(t) + 1, as torch sizes its result -- computing it costs ONE host read, as it does in torch; with
+        num_bins given nothing reaches the host, the result always has num_bins elements, and elements >= num_bins are ignored
+        (torch's minlength only ever lengthens).  Negative elements are ignored where torch raises; a tensor of nothing but negative
+        elements gives an empty result.  Weights are not offered: for
+        sums of a second column per key use reduce_by_key, whose float sums are reproducible bit for bit."""
+        k = self._flat_input(t, "bincount", True)
+        if t.dtype not in (torch.int32, torch.int64):
+            raise TypeError("TorchSorter.bincount: integer tensors only (int32, int64), got %s" % t.dtype)
+        n = k.numel()
+        if num_bins is None:
+            num_bins = max(int(k.max().item()) + 1, 0) if n else 0   # the one host read; nothing but negative elements: no bins
+        num_bins = int(num_bins)
+        if num_bins < 0 or num_bins >= 1 << 31:
+            raise ValueError("TorchSorter.bincount: num_bins = %d outside [0, 2^31)" % num_bins)
+        if num_bins == 0:
+            return torch.empty(0, dtype=torch.int64, device=t.device)
+        kdt = _NP_DTYPE[t.dtype]
+        return self._counts(lambda c: self.pprims.binCount(self.device, self._wrap(k, kdt), n, num_bins, countsOut=c), num_bins, t.device)
+
+    def histogram(self, t, edges):
+        """numpy.histogram(t, bins=edges)[0] for a 1-D tensor t and a 1-D tensor `edges` of the same dtype and device with 2 .. 4097
+        non-decreasing elements: int64 counts of the len(edges) - 1 bins [edges[b], edges[b + 1]), the last one closed.  Equal to
+        numpy on input without NaN: the comparisons are those of sort() -- integers by value, floats by IEEE totalOrder on bits, so
+        -0 is below +0 (an edge of +0 leaves -0 outside) and NaNs lie beyond the infinities, outside any finite edges.  Nothing
+        reaches the host."""
+        k = self._flat_input(t, "histogram", True)
+        e = self._flat_input(edges, "histogram", True)
+        if e.dtype != t.dtype:
+            raise TypeError("TorchSorter.histogram: edges are %s, the tensor %s" % (e.dtype, t.dtype))
+        bins = e.numel() - 1
+        if bins < 1 or bins > 4096:
+            raise ValueError("TorchSorter.histogram: %d edges; 2 .. 4097 (1 .. 4096 bins)" % e.numel())
+        kdt = _NP_DTYPE[t.dtype]
+        return self._counts(lambda c: self.pprims.histogramRange(self.device, self._wrap(k, kdt), k.numel(), self._wrap(e, kdt), bins,
+                                                                 include_upper=True, countsOut=c), bins, t.device)
+
+    def histc(self, t, bins=100, min=0, max=0):
+        """Counts of `bins` equal-width bins between min and max, int64: the edges are torch.linspace(min, max, bins + 1) computed in
+        float64 on the CPU and cast to t's dtype, and the result equals numpy.histogram on those edges EXACTLY (histogram() above; the last bin
+        is closed, elements outside [min, max] are ignored).  torch.histc computes each element's bin by a division instead; for an
+        element within a rounding error of an edge the two can differ by one bin.  min == max (the default): the tensor's own
+        minimum and maximum, which costs one host read; if those are equal too, min - 1 and max + 1, as torch does.  For an integer
+        tensor the cast truncates the edges towards zero: the bins are then of unequal width, and edges that fall on one integer
+        give empty bins -- still numpy.histogram on those integer edges."""
+        k = self._flat_input(t, "histc", True)
+        bins = int(bins)
+        if bins < 1 or bins > 4096:
+            raise ValueError("TorchSorter.histc: bins = %d outside [1, 4096]" % bins)
+        lo, hi = float(min), float(max)
+        if lo > hi:
+            raise ValueError("TorchSorter.histc: max must be larger than min")
+        if lo == hi and k.numel():
+            lo, hi = float(k.min().item()), float(k.max().item())
+        if lo == hi:
+            lo, hi = lo - 1.0, hi + 1.0
+        edges = torch.linspace(lo, hi, bins + 1, dtype=torch.float64).to(t.dtype).to(t.device)   # (on the CPU: the same edges everywhere)
+        return self.histogram(k, edges)
 
     def sort(self, t, descending=False):
         """(values, indices) like torch.sort(t, descending=descending, stable=True); indices are int64."""

@@ -6,7 +6,8 @@
 // adlhip_unique_typed (it waits for the count), or the runs of the host argsort.  Pprims::reduceByKey: adlhip_reduce_by_key_typed (it
 // waits for the count), or a loop over the runs of the host argsort.  Pprims::scanTyped / scanByKey: adlhip_scan_typed /
 // adlhip_scan_by_key, or a plain loop, left to right.  Pprims::compactFlagged / compactIf: adlhip_compact_flagged /
-// adlhip_compact_if_typed (they wait for the count), or a plain loop.
+// adlhip_compact_if_typed (they wait for the count), or a plain loop.  Pprims::histogramRange / binCount:
+// adlhip_histogram_range_typed / adlhip_bincount_typed, or a plain loop.
 #include <Tahoe/ParallelPrimitives/Pprims.h>
 
 #include <algorithm>
@@ -647,6 +648,104 @@ TAHOE_COMPACT_KEY(u32)
 TAHOE_COMPACT_KEY(u64)
 #undef TAHOE_COMPACT_KEY
 #undef TAHOE_COMPACT
+
+// ---- histograms: adlhip_histogram_range_typed / adlhip_bincount_typed, or a plain loop ----
+template <typename T>
+void Pprims::histogramRange(const adl::Device* device, const adl::Buffer<T>& keys, const adl::Buffer<T>& edges, adl::Buffer<u32>& counts, int n,
+                            int numBins, bool includeUpper)
+{
+    ADLASSERT(n >= 0);
+    ADLASSERT(numBins >= 1 && numBins <= ADLHIP_HISTOGRAM_MAX_RANGE_BINS);
+    if (n < 0 || numBins < 1 || numBins > ADLHIP_HISTOGRAM_MAX_RANGE_BINS) return;
+    ADLASSERT(device != 0);
+    ADLASSERT((adl::u64)n <= keys.getSize() && (adl::u64)numBins + 1 <= edges.getSize() && (adl::u64)numBins <= counts.getSize());
+    if (!onDevice(device)) {
+        ADLASSERT(device->getType() == adl::TYPE_HOST);   // a HIP device never falls back to the CPU
+        if (device->getType() != adl::TYPE_HOST) return;
+        typedef typename KeyTraits<T>::Bits B;
+        T* e = edges.getHostPtr(numBins + 1);
+        T* k = n ? keys.getHostPtr(n) : 0;
+        u32* c = counts.getHostPtr(numBins);
+        adl::DeviceUtils::waitForCompletion(device);
+        std::vector<B> code((size_t)numBins + 1);
+        for (int b = 0; b <= numBins; ++b) code[b] = ordinal(e[b], false);
+        for (int b = 0; b < numBins; ++b) c[b] = 0;
+        int upperBin = numBins - 1;   // where a key equal to the last edge goes: the last bin whose lower edge is below it
+        while (upperBin > 0 && !(code[upperBin] < code[numBins])) --upperBin;
+        if (!(code[upperBin] < code[numBins])) upperBin = numBins - 1;
+        for (int i = 0; i < n; ++i) {
+            const B o = ordinal(k[i], false);
+            const int pos = (int)(std::upper_bound(code.begin(), code.end(), o) - code.begin());   // edges <= the key
+            if (pos >= 1 && pos <= numBins) ++c[pos - 1];
+            else if (pos > numBins && includeUpper && o == code[numBins]) ++c[upperBin];
+        }
+        edges.returnHostPtr(e);
+        if (k) keys.returnHostPtr(k);
+        counts.returnHostPtr(c);
+        adl::DeviceUtils::waitForCompletion(device);
+        return;
+    }
+    size_t wb = 0;
+    const int rcq = adlhip_histogram_scratch_bytes(device->hip(), KeyTraits<T>::TYPE, (size_t)n, (size_t)numBins, 1, &wb);
+    ADLASSERT(rcq == ADLHIP_SUCCESS);
+    reserve(device, 0, wb);
+    const int rc = adlhip_histogram_range_typed(device->hip(), KeyTraits<T>::TYPE, keys.m_ptr, (size_t)n, edges.m_ptr, (size_t)numBins,
+                                                includeUpper ? 1 : 0, (uint32_t*)counts.m_ptr, m_work->m_ptr, (size_t)m_work->getSize());
+    if (rc != ADLHIP_SUCCESS) TH_LOG_ERROR("Pprims::histogramRange: %s\n", adlhip_last_error());
+    ADLASSERT(rc == ADLHIP_SUCCESS);
+}
+
+template <typename T>
+void Pprims::binCount(const adl::Device* device, const adl::Buffer<T>& keys, adl::Buffer<u32>& counts, int n, int numBins)
+{
+    ADLASSERT(!KeyTraits<T>::FLOAT);
+    ADLASSERT(n >= 0 && numBins >= 1);
+    if (n < 0 || numBins < 1) return;
+    ADLASSERT(device != 0);
+    ADLASSERT((adl::u64)n <= keys.getSize() && (adl::u64)numBins <= counts.getSize());
+    if (!onDevice(device)) {
+        ADLASSERT(device->getType() == adl::TYPE_HOST);   // a HIP device never falls back to the CPU
+        if (device->getType() != adl::TYPE_HOST) return;
+        typedef typename KeyTraits<T>::Bits B;
+        T* k = n ? keys.getHostPtr(n) : 0;
+        u32* c = counts.getHostPtr(numBins);
+        adl::DeviceUtils::waitForCompletion(device);
+        for (int b = 0; b < numBins; ++b) c[b] = 0;
+        for (int i = 0; i < n; ++i) {
+            B bits;
+            memcpy(&bits, &k[i], sizeof(B));   // a negative key is a large unsigned number
+            if (bits < (B)numBins) ++c[(size_t)bits];
+        }
+        if (k) keys.returnHostPtr(k);
+        counts.returnHostPtr(c);
+        adl::DeviceUtils::waitForCompletion(device);
+        return;
+    }
+    size_t wb = 0;
+    const int rcq = adlhip_histogram_scratch_bytes(device->hip(), KeyTraits<T>::TYPE, (size_t)n, (size_t)numBins, 0, &wb);
+    ADLASSERT(rcq == ADLHIP_SUCCESS);
+    reserve(device, 0, wb);
+    const int rc = adlhip_bincount_typed(device->hip(), KeyTraits<T>::TYPE, keys.m_ptr, (size_t)n, (size_t)numBins, (uint32_t*)counts.m_ptr,
+                                         m_work->m_ptr, (size_t)m_work->getSize());
+    if (rc != ADLHIP_SUCCESS) TH_LOG_ERROR("Pprims::binCount: %s\n", adlhip_last_error());
+    ADLASSERT(rc == ADLHIP_SUCCESS);
+}
+
+#define TAHOE_HISTOGRAM(T)                                                                                                                  \
+    template void Pprims::histogramRange<T>(const adl::Device*, const adl::Buffer<T>&, const adl::Buffer<T>&, adl::Buffer<u32>&, int, int, bool);
+#define TAHOE_BINCOUNT(T) template void Pprims::binCount<T>(const adl::Device*, const adl::Buffer<T>&, adl::Buffer<u32>&, int, int);
+TAHOE_HISTOGRAM(int)
+TAHOE_HISTOGRAM(float)
+TAHOE_HISTOGRAM(long long)
+TAHOE_HISTOGRAM(double)
+TAHOE_HISTOGRAM(u32)
+TAHOE_HISTOGRAM(u64)
+TAHOE_BINCOUNT(int)
+TAHOE_BINCOUNT(long long)
+TAHOE_BINCOUNT(u32)
+TAHOE_BINCOUNT(u64)
+#undef TAHOE_BINCOUNT
+#undef TAHOE_HISTOGRAM
 
 #define TAHOE_TYPED(T)                                                                                                              \
     void Pprims::sortKeys(const adl::Device* device, const adl::Buffer<T>& inout, int n, bool descending)                         \

@@ -6,7 +6,8 @@ is followed -- while later sorts are already queued -- by the LDS-order self-tes
 behaviour "sort.rank" = 1 rests on, adlhip_selftest_lds_order), and one size class reaches past 64 Mi keys (the
 pointer-store write-out).  Half of the sorts take the automatic choice (mid-size sort, large sort with its look-back /
 cursor passes and the safety net inside its offsets kernel), with "sort.msd2" forced on for some and keys shifted down by a random number of bits.
-One kind in six is a stream compaction between the sorts (a stable partition of the keys by a comparison, values and positions along).
+One kind in seven is a stream compaction between the sorts (a stable partition of the keys by a comparison, values and positions along),
+one a histogram (range or bincount, random key type, bins and grid knob, the LDS and the sorted path).
    python tools/stress.py [--seconds 60]"""
 import argparse, os, sys, time
 import numpy as np
@@ -33,7 +34,7 @@ def checks(a):
     return int(a64.sum(dtype=np.uint64)), int(np.bitwise_xor.reduce(a64)) if a.size else 0
 while time.time() < t_end and it < args.stop_after:
     it += 1
-    kind = rng.choice(["u32", "kv", "u64", "soa", "soaw", "compact"])
+    kind = rng.choice(["u32", "kv", "u64", "soa", "soaw", "compact", "hist"])
     n = int(2 ** rng.uniform(10, 25.5)) + int(rng.randint(0, 1000))
     if it % 7 == 0: n = int(2 ** rng.uniform(21, 26.3))   # more of the large sort's range
     if kind == "u32" and it % 23 == 0: n = (1 << 26) + int(rng.randint(1, 1 << 22))     # past 256 MiB: pointer stores
@@ -52,7 +53,7 @@ while time.time() < t_end and it < args.stop_after:
             else: rng.randint(1, 4)
         continue
     if verbose: print("it %d %s n=%d algo=%d bits=%d tile=%d msd2=%d dist=%s shift=%d" % (it, kind, n, algo, bits, tile, msd2_mode, dist, shift), flush=True)
-    if kind in ("u32", "soa", "kv", "soaw", "compact"):
+    if kind in ("u32", "soa", "kv", "soaw", "compact", "hist"):
         k = oracle.keys_u32(n, seed=it)
         if dist == "heavy": k = np.where(np.arange(n) % 10 != 0, (k >> np.uint32(8)) | np.uint32(0x37000000), k).astype(np.uint32)
         elif dist == "vals4096": k = (k >> np.uint32(20)) * np.uint32(0x00100801)
@@ -103,6 +104,47 @@ while time.time() < t_end and it < args.stop_after:
         below = k.view(np.int32) < th.view(np.int32)
         order = np.concatenate([np.flatnonzero(below), np.flatnonzero(~below)])
         assert s == int(below.sum()) and np.array_equal(oi, order) and np.array_equal(ok, k[order]) and np.array_equal(ov, v[order]), (it, kind, n, dist)
+    elif kind == "hist":   # a histogram of the keys: mode, type, bins and grid knob from a generator of this iteration's own
+        hr = np.random.RandomState(args.seed + 7 * it)
+        n = min(n, 1 << 24)
+        k = k[:n]
+        wide = bool(hr.randint(0, 2))
+        if wide: k = k.astype(np.uint64) * np.uint64(0x100000001) >> np.uint64(hr.randint(0, 33))
+        d.setParam("debug.histogram_grid", int(hr.choice([0, 0, 1, 5, 64, 300])))
+        if hr.randint(0, 2):   # range: sorted edges drawn from the keys (some repeated) and from anywhere
+            tname = ["uf", "UF"][wide][hr.randint(0, 2)] if hr.randint(0, 3) else "iI"[wide]
+            dt = {"u": np.uint32, "i": np.int32, "f": np.float32, "U": np.uint64, "I": np.int64, "F": np.float64}[tname]
+            bins = int(hr.choice([1, 2, 17, 256, 1000, 4096]))
+            e = np.concatenate([k[hr.randint(0, n, size=bins // 2 + 1)], hr.randint(0, 1 << 32, size=bins - bins // 2).astype(k.dtype) << k.dtype.type(8 * k.itemsize - 32)])
+            sign = k.dtype.type(1 << (8 * k.itemsize - 1)); ones = k.dtype.type((1 << (8 * k.itemsize)) - 1)
+            def code(x): return x ^ sign if tname in "iI" else x ^ np.where(x & sign != 0, ones, sign).astype(x.dtype) if tname in "fF" else x
+            e = e[np.argsort(code(e), kind="stable")]
+            upper = bool(hr.randint(0, 2))
+            kb = Buffer(d, n, dt); eb = Buffer(d, bins + 1, dt); kb.write(k.view(dt)); eb.write(e.view(dt))
+            cb = p.histogramRange(d, kb, n, eb, bins, include_upper=upper)
+            got = cb.toHost()
+            for b in (kb, eb, cb): b.release()
+            kc, ec = code(k), code(e)
+            b_of = np.searchsorted(ec, kc, side="right").astype(np.int64) - 1
+            want = np.bincount(b_of[(b_of >= 0) & (b_of < bins)], minlength=bins)
+            if upper:
+                below = np.flatnonzero(ec[:bins] < ec[bins])
+                want[below[-1] if below.size else bins - 1] += np.count_nonzero(kc == ec[bins])
+            assert np.array_equal(got.astype(np.int64), want), (it, kind, "range", tname, n, bins, upper, dist)
+        else:                  # bincount: keys folded so that about half of them are in range; small limits reach the sorted path
+            dt = [[np.uint32, np.int32], [np.uint64, np.int64]][wide][hr.randint(0, 2)]
+            bins = int(hr.choice([1, 7, 256, 8192, 8193, 100000, 1 << 20]))
+            d.setParam("debug.histogram_lds_bins", int(hr.choice([0, 0, 64])))
+            k = np.where(k % k.dtype.type(3) == 0, k, k % k.dtype.type(2 * bins))
+            kb = Buffer(d, n, dt); kb.write(k.view(dt))
+            cb = p.binCount(d, kb, n, bins)
+            got = cb.toHost()
+            for b in (kb, cb): b.release()
+            d.setParam("debug.histogram_lds_bins", 0)
+            v = k.view(dt)
+            ok = (v >= 0) & (v < bins)
+            assert np.array_equal(got.astype(np.int64), np.bincount(v[ok].astype(np.int64), minlength=bins)), (it, kind, "bincount", dt, n, bins, dist)
+        d.setParam("debug.histogram_grid", 0)
     elif kind == "soaw":   # wide values / 64-bit keys on separate arrays (adlhip_radix_sort_soa): index sort + gather
         n = min(n, 1 << 23)
         k = k[:n]
