@@ -1,12 +1,11 @@
-// adlhip.hip -- implementation of include/adlhip.h: the HIP back-end behind the Adl/Pprims facade.
-// Replaces Adl/CL/AdlCL.inl (device, buffers, copies, map/unmap), Adl/CL/AdlKernelUtilsCL.inl
-// (kernel launch + per-launch profiling) and the GPU branches of Tahoe/ParallelPrimitives/Pprims.cpp
-// (pass drivers).  gfx950 only; kernels are compiled ahead of time into this shared object.
+// adlhip.hip -- the sorts of include/adlhip.h: the layouts, the path choice and the drivers of the per-digit, mid-size and large sorts,
+// the scan, the partitions, and what a handle owns for them (sort_state_create, the idle table).  Replaces the GPU branches of
+// Tahoe/ParallelPrimitives/Pprims.cpp (pass drivers).  The runtime under it -- handle, buffers, profiling, knobs -- is handle.hip.
+// gfx950 only; kernels are compiled ahead of time into this shared object.
 #include "adlhip_internal.hpp"
 
 #include <algorithm>
 #include <cmath>
-#include <cstdarg>
 #include <cstdlib>
 #include <cstring>
 #include <mutex>
@@ -21,7 +20,7 @@
 
 // The large sort's kernels and the per-digit passes' are instantiated in kernels_finish.hip / kernels_passes.hip / kernels_perdigit.hip (translation units of
 // their own, compiled beside this one); here they are only declared.  The primitives on top of the sorts are a unit of their own too (primitives.hip).
-// -DADLHIP_SINGLE_TU builds everything in this file, primitives.hip included at its end (what tools/gen_large_kernels.py reads the list from).
+// -DADLHIP_SINGLE_TU builds everything in this file, handle.hip and primitives.hip included at its end (what tools/gen_large_kernels.py reads the list from).
 #ifndef ADLHIP_SINGLE_TU
 #define X(...) extern template __global__ __VA_ARGS__;
 #include "finish_kernels.inc"
@@ -34,102 +33,6 @@
 using namespace adlhip_internal;
 
 namespace {
-thread_local char g_err[512] = "";
-constexpr size_t kPinnedPoolMax = size_t(512) << 20;   // pinned staging kept for re-use per device handle
-}  // namespace
-
-namespace adlhip_internal {
-
-int fail(const char* fmt, ...)
-{
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-    if (getenv("ADLHIP_VERBOSE")) fprintf(stderr, "[adlhip] error: %s\n", g_err);
-    return ADLHIP_FAILURE;
-}
-
-int bind(adlhip_device* d)
-{
-    if (!d) return fail("null device handle");
-    HIPCHK(hipSetDevice(d->idx));
-    return ADLHIP_SUCCESS;
-}
-
-hipEvent_t take_event(adlhip_device* d)
-{
-    if (!d->event_pool.empty()) {
-        hipEvent_t e = d->event_pool.back();
-        d->event_pool.pop_back();
-        return e;
-    }
-    hipEvent_t e = nullptr;
-    if (hipEventCreate(&e) != hipSuccess) return nullptr;
-    return e;
-}
-
-int trace_level()
-{
-    static const int level = getenv("ADLHIP_TRACE") ? atoi(getenv("ADLHIP_TRACE")) : 0;
-    return level;
-}
-
-// Interned kernel names (the profiler keeps the pointer until the events are folded).
-const char* intern(const std::string& s)
-{
-    static std::mutex mu;
-    static std::map<std::string, std::string*> pool;
-    std::lock_guard<std::mutex> lock(mu);
-    auto it = pool.find(s);
-    if (it == pool.end()) it = pool.emplace(s, new std::string(s)).first;
-    return it->second->c_str();
-}
-
-}  // namespace adlhip_internal
-
-namespace {
-
-int fold_profile(adlhip_device* d)
-{
-    if (d->pending.empty()) return ADLHIP_SUCCESS;
-    HIPCHK(hipStreamSynchronize(d->stream));
-    for (auto& p : d->pending) {
-        float ms = 0.f;
-        HIPCHK(hipEventElapsedTime(&ms, p.e0, p.e1));
-        auto it = d->prof.find(p.name);
-        if (it == d->prof.end()) {
-            d->prof_order.push_back(p.name);
-            it = d->prof.emplace(p.name, ProfEntry()).first;
-        }
-        it->second.launches++;
-        it->second.total_ms += ms;
-        d->event_pool.push_back(p.e0);
-        d->event_pool.push_back(p.e1);
-    }
-    d->pending.clear();
-    return ADLHIP_SUCCESS;
-}
-
-void reap_staging(adlhip_device* d, bool all_done)
-{
-    for (size_t i = 0; i < d->staging.size();) {
-        Staging& s = d->staging[i];
-        if (s.done && (all_done || hipEventQuery(s.done) == hipSuccess)) {
-            hipEventDestroy(s.done);
-            if (d->pinned_pool_bytes + s.capacity <= kPinnedPoolMax) {
-                d->pinned_pool.push_back({s.hptr, s.capacity});
-                d->pinned_pool_bytes += s.capacity;
-            } else {
-                hipHostFree(s.hptr);
-            }
-            d->staging[i] = d->staging.back();
-            d->staging.pop_back();
-        } else {
-            ++i;
-        }
-    }
-}
 
 // ---- sort configuration -------------------------------------------------------------------
 
@@ -142,6 +45,9 @@ struct TileVariant {
 };
 constexpr TileVariant kVariants[] = {{256, 16}, {512, 16}, {1024, 16}, {512, 8}, {1024, 8}, {256, 32}, {512, 32}};
 constexpr int kNumVariants = (int)(sizeof(kVariants) / sizeof(kVariants[0]));
+}  // namespace
+int adlhip_internal::num_tile_variants() { return kNumVariants; }
+namespace {
 constexpr uint32_t kMinTile = 4096;
 constexpr int kWgsPerCu = 8;   // three-kernel pass: workgroups per CU that each own a run of tiles
 
@@ -950,7 +856,6 @@ constexpr size_t kMsd2Words = 8192 + 65536 + 64;
 // hybrid_kernels.hpp kTileTicketWord0).  Reset on entry by msd2_sample_kernel, read by nothing else, and NOT part of the idle
 // table's region: tests/test_gpu_call_sequences.py pins that region's size (no word flag[64] to poke).
 constexpr size_t kMsd2TicketWords = (size_t)adlhip::kTileTicketCounters * adlhip::kTileTicketStride;
-uint32_t* net_stats(const adlhip_device* d) { return d->d_msd2 + 8192 + 65536 + 16; }
 
 // ---- what the handle-owned device words hold between sorts ("debug.idle_dirty"; DESIGN.md "Idle state of a handle") ----
 // Every word of d_msd2, d_mid_hist, d_dict and d_fault[0..15] is one of three kinds:
@@ -962,12 +867,17 @@ uint32_t* net_stats(const adlhip_device* d) { return d->d_msd2 + 8192 + 65536 + 
 enum IdleRegion { kRegionMsd2 = 1, kRegionMidHist = 2, kRegionDict = 3, kRegionFault = 4, kIdleRegions = 4 };
 enum IdleKind { kIdleValue, kResetOnEntry, kFreeRunning };
 constexpr uint32_t kMsd2Flag = 8192 + 65536;                       // flag = d_msd2 + kMsd2Flag
+constexpr uint32_t kMsd2SampleAnd = kMsd2Flag + 10, kMsd2SampleAndWords = 2;   // flag[10..11]: all ones when idle (sort_state_create)
+constexpr uint32_t kMsd2NetStats = kMsd2Flag + 16;                 // flag[16..17] the net's counters, flag[20..29] its time stamps
+uint32_t* net_stats(const adlhip_device* d) { return d->d_msd2 + kMsd2NetStats; }
 constexpr uint32_t kMidHistWords = 16 * 1024 + 8192 + 64;
 constexpr uint32_t kMidState = 16 * 1024;                          // SegSlab::state = d_mid_hist + kMidState
 constexpr uint32_t kDictSmallWords = (uint32_t)(sizeof(adlhip::DictBlock) / 4);
 constexpr uint32_t kDictWords = (uint32_t)((sizeof(adlhip::DictBlock) + sizeof(adlhip::BigDictBlock)) / 4);
 constexpr uint32_t kFaultWords = 16;
 static_assert(adlhip::kSampleRepeatsWord == 12 && adlhip::kSampleArriveWord == 13 && adlhip::kSampleThresholdWord == 14, "the idle table below");
+static_assert((sizeof(adlhip::DictBlock) + sizeof(adlhip::BigDictBlock)) % 4 == 0, "d_dict is allocated and checked in words");
+static_assert(kMsd2Words == kMsd2Flag + adlhip::kTileTicketWord0, "the idle table's region ends where the ticket counters start");
 static_assert(adlhip::kTileTicketWord0 == 64 && adlhip::kTileTicketStride == 32, "the ticket counters start behind the flag's 64 words, one 128-byte line each");
 struct IdleRange {
     int region;
@@ -985,14 +895,14 @@ constexpr IdleRange kIdleTable[] = {
     {kRegionMsd2, kMsd2Flag + 2, 1, kResetOnEntry, 0u, "flag[2] the net's grid-barrier counter: msd2_sample_kernel / msd2s_prep_kernel"},
     {kRegionMsd2, kMsd2Flag + 3, 5, kIdleValue, 0u, "flag[3..7] unused"},
     {kRegionMsd2, kMsd2Flag + 8, 2, kIdleValue, 0u, "flag[8..9] sample OR words: last workgroup of msd2_offsets_kernel / last arrival of msd2s_prep_kernel"},
-    {kRegionMsd2, kMsd2Flag + 10, 2, kIdleValue, ~0u, "flag[10..11] sample AND words: last workgroup of msd2_offsets_kernel / last arrival of msd2s_prep_kernel"},
+    {kRegionMsd2, kMsd2SampleAnd, kMsd2SampleAndWords, kIdleValue, ~0u, "flag[10..11] sample AND words: last workgroup of msd2_offsets_kernel / last arrival of msd2s_prep_kernel"},
     {kRegionMsd2, kMsd2Flag + 12, 1, kIdleValue, 0u, "flag[12] sample repeats: last workgroup of msd2_offsets_kernel / msd2s_offsets_kernel"},
     {kRegionMsd2, kMsd2Flag + 13, 1, kIdleValue, 0u, "flag[13] arrivals: last arrival of msd2s_prep_kernel"},
     {kRegionMsd2, kMsd2Flag + 14, 1, kResetOnEntry, 0u, "flag[14] repeat threshold: msd2_sample_kernel / msd2s_prep_kernel"},
     {kRegionMsd2, kMsd2Flag + 15, 1, kIdleValue, 0u, "flag[15] unused"},
-    {kRegionMsd2, kMsd2Flag + 16, 2, kFreeRunning, 0u, "flag[16..17] nets run / sorted by counting (stat.net_runs, stat.net_counting)"},
+    {kRegionMsd2, kMsd2NetStats, 2, kFreeRunning, 0u, "flag[16..17] nets run / sorted by counting (stat.net_runs, stat.net_counting)"},
     {kRegionMsd2, kMsd2Flag + 18, 2, kIdleValue, 0u, "flag[18..19] unused"},
-    {kRegionMsd2, kMsd2Flag + 20, 10, kFreeRunning, 0u, "flag[20..29] the last net's time stamps (debug.net_stamp0..9)"},
+    {kRegionMsd2, kMsd2NetStats + 4, 10, kFreeRunning, 0u, "flag[20..29] the last net's time stamps (debug.net_stamp0..9)"},
     {kRegionMsd2, kMsd2Flag + 30, 34, kIdleValue, 0u, "flag[30..63] unused"},
     // d_mid_hist: the mid-size sort
     {kRegionMidHist, 0, 16 * 1024, kIdleValue, 0u, "slice histograms [16][4][256]: last workgroup of mid_prep_kernel"},
@@ -1824,12 +1734,7 @@ int partition_msb(adlhip_device* d, const E* in, E* out, uint32_t* counts, void*
         if (n) {
             if (!in || !out) return fail("null buffer");
             HIPCHK(hipMemcpyAsync(out, in, n * sizeof(E), hipMemcpyDeviceToDevice, d->stream));
-            uint32_t nn = (uint32_t)n;
-            // counts[0] = n  (stream-ordered fill of one word)
-            int rc = launch(d, "fill_u32", [&] {
-                hipLaunchKernelGGL(adlhip::fill_u32_kernel, dim3(1), dim3(256), 0, d->stream, counts, nn, (size_t)1);
-            });
-            if (rc) return rc;
+            return adlhip_fill_u32(d, counts, (uint32_t)n, 1);   // counts[0] = n  (stream-ordered fill of one word: one workgroup)
         }
         return ADLHIP_SUCCESS;
     }
@@ -1927,22 +1832,6 @@ int soa_wide_sort(adlhip_device* d, K* keys, V* vals, K* tmp_keys, V* tmp_vals, 
 
 }  // namespace
 
-// ================================================================================================
-extern "C" {
-
-const char* adlhip_version(void) { return "adlhip 0.2 (gfx950)"; }
-const char* adlhip_last_error(void) { return g_err; }
-// internal (not in include/adlhip.h): lets the library's other translation unit (sharded.cpp) set the calling thread's
-// error text
-void adlhip_set_last_error(const char* text) { snprintf(g_err, sizeof(g_err), "%s", text ? text : ""); }
-
-int adlhip_device_count(void)
-{
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess) return 0;
-    return n;
-}
-
 // 256-thread and 1024-thread workgroups; blocks the calling thread until the result is back
 static int run_lds_order_selftest(adlhip_device* d, int workgroups, uint32_t* mismatches)
 {
@@ -1958,110 +1847,22 @@ static int run_lds_order_selftest(adlhip_device* d, int workgroups, uint32_t* mi
     return ADLHIP_SUCCESS;
 }
 
-int adlhip_selftest_lds_order(adlhip_device* d, int workgroups, uint32_t* mismatches)
+// ---- what a handle owns for the sorts (handle.hip: create_common, release_handle) ------------------------------------------------
+// The idle table's three areas at their idle values, then what the device answers.  A failure leaves what exists to sort_state_destroy.
+int adlhip_internal::sort_state_create(adlhip_device* d)
 {
-    if (bind(d)) return ADLHIP_FAILURE;
-    if (!mismatches) return fail("null out pointer");
-    if (workgroups < 1 || workgroups > 65536) return fail("selftest: workgroups must be in [1,65536]");
-    return run_lds_order_selftest(d, workgroups, mismatches);
-}
-
-int adlhip_selftest_probe_positions(adlhip_device* d, size_t n, uint32_t* max_index, uint32_t* out_of_cell)
-{
-    if (bind(d)) return ADLHIP_FAILURE;
-    if (!max_index || !out_of_cell) return fail("null out pointer");
-    if (n < 16384 || n > kMaxElems) return fail("selftest: n must be in [16384, %zu]", (size_t)kMaxElems);
-    // two words of the dictionary block's count[] serve as the result (free between sorts: a net that uses the dictionary clears
-    // count[] before it counts, kIdleTable)
-    uint32_t* res = d->d_dict->count;
-    HIPCHK(hipMemsetAsync(res, 0, 8, d->stream));
-    int rc = launch(d, "probe_positions_selftest", [&] {
-        hipLaunchKernelGGL(adlhip::probe_positions_selftest_kernel, dim3(1), dim3(1024), 0, d->stream, (uint32_t)n, res);
-    });
-    if (rc) return rc;
-    uint32_t h[2] = {0u, 0u};
-    HIPCHK(hipMemcpyAsync(h, res, 8, hipMemcpyDeviceToHost, d->stream));
-    HIPCHK(hipMemsetAsync(res, 0, 8, d->stream));
-    HIPCHK(hipStreamSynchronize(d->stream));
-    *max_index = h[0];
-    *out_of_cell = h[1];
-    return ADLHIP_SUCCESS;
-}
-
-static int create_common(int device_idx, void* stream, bool own, adlhip_device** out)
-{
-    if (!out) return fail("null out pointer");
-    *out = nullptr;
-    int n = 0;
-    hipError_t e = hipGetDeviceCount(&n);
-    if (e != hipSuccess || n <= 0)
-        return fail("no HIP device available (%s)", e == hipSuccess ? "count = 0" : hipGetErrorString(e));
-    if (device_idx < 0) device_idx = 0;
-    if (device_idx >= n) device_idx = n - 1;   // AdlCL.inl:244 clamps the same way
-    adlhip_device* d = new adlhip_device();
-    d->idx = device_idx;
-    if (hipSetDevice(device_idx) != hipSuccess || hipGetDeviceProperties(&d->prop, device_idx) != hipSuccess) {
-        delete d;
-        return fail("cannot bind HIP device %d", device_idx);
-    }
-    if (strncmp(d->prop.gcnArchName, "gfx950", 6) != 0 && !getenv("ADLHIP_ALLOW_ANY_ARCH")) {
-        std::string arch = d->prop.gcnArchName;
-        delete d;
-        return fail("adlhip is built for gfx950 only; device %d is %s", device_idx, arch.c_str());
-    }
-    d->own_stream = own;
-    if (own) {
-        if (hipStreamCreateWithFlags(&d->stream, hipStreamNonBlocking) != hipSuccess) {
-            delete d;
-            return fail("hipStreamCreate failed");
-        }
-    } else {
-        d->stream = reinterpret_cast<hipStream_t>(stream);
-    }
-    if (hipMalloc(&d->d_fault, 64) != hipSuccess || hipHostMalloc(&d->h_fault, 64) != hipSuccess ||
-        hipMemsetAsync(d->d_fault, 0, 64, d->stream) != hipSuccess) {
-        if (d->d_fault) hipFree(d->d_fault);
-        if (d->h_fault) hipHostFree(d->h_fault);
-        if (own && d->stream) hipStreamDestroy(d->stream);
-        delete d;
-        return fail("cannot allocate the fault word");
-    }
-    memset(d->h_fault, 0, 64);
-    if (hipMalloc(&d->d_mid_hist, (16 * 1024 + 8192 + 64) * 4) != hipSuccess ||
-        hipMemsetAsync(d->d_mid_hist, 0, (16 * 1024 + 8192 + 64) * 4, d->stream) != hipSuccess) {
-        if (d->d_mid_hist) hipFree(d->d_mid_hist);
-        hipFree(d->d_fault);
-        hipHostFree(d->h_fault);
-        if (own && d->stream) hipStreamDestroy(d->stream);
-        delete d;
+    if (hipMalloc(&d->d_mid_hist, kMidHistWords * 4) != hipSuccess || hipMemsetAsync(d->d_mid_hist, 0, kMidHistWords * 4, d->stream) != hipSuccess)
         return fail("cannot allocate the mid-size sort's histogram area");
-    }
     // the large sort's handle-owned words (cursors, flags: 270 KB), zero between sorts -- allocated here rather than by a handle's
     // first large sort
     if (hipMalloc(&d->d_msd2, (kMsd2Words + kMsd2TicketWords) * 4) != hipSuccess ||
         hipMemsetAsync(d->d_msd2, 0, (kMsd2Words + kMsd2TicketWords) * 4, d->stream) != hipSuccess ||
-        hipMemsetAsync(d->d_msd2 + 8192 + 65536 + 10, 0xff, 8, d->stream) != hipSuccess) {   // the sample's AND words: all ones when idle
-        if (d->d_msd2) hipFree(d->d_msd2);
-        hipFree(d->d_mid_hist);
-        hipFree(d->d_fault);
-        hipHostFree(d->h_fault);
-        if (own && d->stream) hipStreamDestroy(d->stream);
-        delete d;
+        hipMemsetAsync(d->d_msd2 + kMsd2SampleAnd, 0xff, kMsd2SampleAndWords * 4, d->stream) != hipSuccess)   // all ones when idle
         return fail("cannot allocate the large sort's cursors");
-    }
     // (the larger dictionary of dict_big_kernels.hpp lies behind the small one: the kernels find it at d_dict + 1)
     static_assert(sizeof(adlhip::DictBlock) % 16 == 0, "the second block starts aligned");
-    if (hipMalloc(&d->d_dict, sizeof(adlhip::DictBlock) + sizeof(adlhip::BigDictBlock)) != hipSuccess ||
-        hipMemsetAsync(d->d_dict, 0, sizeof(adlhip::DictBlock) + sizeof(adlhip::BigDictBlock), d->stream) != hipSuccess) {
-        if (d->d_dict) hipFree(d->d_dict);
-        hipFree(d->d_msd2);
-        hipFree(d->d_mid_hist);
-        hipFree(d->d_fault);
-        hipHostFree(d->h_fault);
-        if (own && d->stream) hipStreamDestroy(d->stream);
-        delete d;
+    if (hipMalloc(&d->d_dict, (size_t)kDictWords * 4) != hipSuccess || hipMemsetAsync(d->d_dict, 0, (size_t)kDictWords * 4, d->stream) != hipSuccess)
         return fail("cannot allocate the counting sort's dictionary");
-    }
     if (trace_level())
         fprintf(stderr, "[adlhip] handle %p: d_fault %p h_fault %p d_mid_hist %p d_msd2 %p d_dict %p\n", (void*)d, (void*)d->d_fault,
                 (void*)d->h_fault, (void*)d->d_mid_hist, (void*)d->d_msd2, (void*)d->d_dict);
@@ -2093,281 +1894,88 @@ static int create_common(int device_idx, void* stream, bool own, adlhip_device**
         d->resident_wgs_device = d->resident_wgs;
         (void)hipGetLastError();
     }
-    if (const char* a = getenv("ADLHIP_SORT_ALGO")) { int v = atoi(a); if (v >= -1 && v <= 1) d->sort_algo = v; }
-    if (const char* t = getenv("ADLHIP_SORT_TILE")) { int v = atoi(t); if (v >= -1 && v < kNumVariants) d->tile_variant = v; }
-    if (const char* r = getenv("ADLHIP_SORT_RANK")) d->rank_mode = (atoi(r) && d->lds_ordered) ? 1 : 0;
-    if (const char* m = getenv("ADLHIP_SORT_MID")) d->mid_path = atoi(m) ? 1 : 0;
-    if (const char* m = getenv("ADLHIP_SORT_MSD2")) { int v = atoi(m); if (v >= 0 && v <= 2) d->msd2_path = v; }
-    if (const char* b = getenv("ADLHIP_DIGIT_BITS")) { int v = atoi(b); d->digit_bits = (v == 4 || v == 7) ? v : 8; }
-    *out = d;
     return ADLHIP_SUCCESS;
 }
 
-int adlhip_device_create(int device_idx, adlhip_device** out) { return create_common(device_idx, nullptr, true, out); }
-
-int adlhip_device_create_on_stream(int device_idx, void* hip_stream, adlhip_device** out)
+void adlhip_internal::sort_state_destroy(adlhip_device* d)
 {
-    return create_common(device_idx, hip_stream, false, out);
-}
-
-int adlhip_device_destroy(adlhip_device* d)
-{
-    if (bind(d)) return ADLHIP_FAILURE;
-    if (d->used_bytes != 0)   // Adl.inl:102 ADLASSERT( getUsedMemory() == 0 )
-        return fail("device still has %llu live bytes; free every buffer first", (unsigned long long)d->used_bytes);
-    hipStreamSynchronize(d->stream);
-    reap_staging(d, true);
-    for (auto& s : d->staging) hipHostFree(s.hptr);
-    for (auto& b : d->pinned_pool) hipHostFree(b.hptr);
-    for (auto& p : d->pending) { hipEventDestroy(p.e0); hipEventDestroy(p.e1); }
-    for (auto e : d->event_pool) hipEventDestroy(e);
-    if (d->fault_snap) hipEventDestroy(d->fault_snap);
-    hipFree(d->d_mid_hist);
+    if (d->d_mid_hist) hipFree(d->d_mid_hist);
     if (d->d_msd2) hipFree(d->d_msd2);
     if (d->d_dict) hipFree(d->d_dict);
-    hipFree(d->d_fault);
-    hipHostFree(d->h_fault);
-    if (d->own_stream) hipStreamDestroy(d->stream);
-    delete d;
+}
+
+// ---- the knobs that are words of that state, not fields of the handle (handle.hip: adlhip_set_param, adlhip_get_param) ------------
+int adlhip_internal::sort_set_param(adlhip_device* d, const char* name, int value)
+{
+    if (strcmp(name, "debug.idle_poke")) return kNoSuchParam;
+    // the idle checker's positive control: flips bit 0 of one handle-owned word, in stream order (a second poke undoes it)
+    const int region = (int)((uint32_t)value >> 24);
+    const uint32_t word = (uint32_t)value & 0xffffffu;
+    if (region < 1 || region > kIdleRegions || word >= idle_region_words(region))
+        return fail("debug.idle_poke: no word %u in region %d (region << 24 | word; regions 1 d_msd2, 2 d_mid_hist, 3 d_dict, 4 d_fault)", word, region);
+    if (bind(d)) return ADLHIP_FAILURE;
+    hipLaunchKernelGGL(idle_poke_kernel, dim3(1), dim3(1), 0, d->stream, idle_region_base(d, region) + word);
+    HIPCHK(hipGetLastError());
     return ADLHIP_SUCCESS;
 }
 
-int adlhip_device_info(adlhip_device* d, adlhip_info* out)
+int adlhip_internal::sort_get_param(adlhip_device* d, const char* name, int* value)
 {
-    if (bind(d)) return ADLHIP_FAILURE;
-    if (!out) return fail("null info pointer");
-    memset(out, 0, sizeof(*out));
-    out->compute_units = d->prop.multiProcessorCount;
-    out->wavefront_size = d->prop.warpSize;
-    out->lds_bytes_per_cu = (int32_t)d->prop.maxSharedMemoryPerMultiProcessor;
-    out->clock_khz = d->prop.clockRate;
-    out->total_mem_bytes = d->prop.totalGlobalMem;
-    out->max_alloc_bytes = d->prop.totalGlobalMem;
-    snprintf(out->name, sizeof(out->name), "%s", d->prop.name);
-    snprintf(out->arch, sizeof(out->arch), "%s", d->prop.gcnArchName);
-    snprintf(out->vendor, sizeof(out->vendor), "Advanced Micro Devices, Inc.");
+    if (!strcmp(name, "stat.net_runs") || !strcmp(name, "stat.net_counting")) {
+        // how often the large sort's safety net has run on this handle, and how often it sorted by counting (waits for the stream)
+        uint32_t v[2] = {0u, 0u};
+        HIPCHK(hipMemcpyAsync(v, net_stats(d), 8, hipMemcpyDeviceToHost, d->stream));
+        HIPCHK(hipStreamSynchronize(d->stream));
+        *value = (int)v[name[9] == 'c' ? 1 : 0];
+    } else if (!strcmp(name, "debug.idle_dirty") || !strcmp(name, "debug.idle_first")) {
+        // handle-owned words that are not at their idle value (kIdleTable), and the first of them as region << 24 | word (0 = clean);
+        // waits for the stream, changes nothing on the device
+        uint32_t dirty = 0u, first = 0u;
+        if (idle_check(d, &dirty, &first)) return ADLHIP_FAILURE;
+        *value = (int)(name[11] == 'd' ? dirty : first);
+    } else if (!strncmp(name, "debug.net_stamp", 15) && name[15] >= '0' && name[15] <= '9' && !name[16]) {
+        // diagnostic: when workgroup 0 of the last net reached its k-th phase boundary, in 10-ns ticks (low 31 bits; tools/net_phases.py)
+        uint32_t v = 0u;
+        HIPCHK(hipMemcpyAsync(&v, net_stats(d) + 4 + (name[15] - '0'), 4, hipMemcpyDeviceToHost, d->stream));
+        HIPCHK(hipStreamSynchronize(d->stream));
+        *value = (int)(v & 0x7fffffffu);
+    } else {
+        return kNoSuchParam;
+    }
     return ADLHIP_SUCCESS;
 }
 
-uint64_t adlhip_used_bytes(adlhip_device* d) { return d ? d->used_bytes : 0; }
+// ================================================================================================
+extern "C" {
 
-void* adlhip_stream(adlhip_device* d) { return d ? (void*)d->stream : nullptr; }
-
-static int report_fault(adlhip_device* d, uint32_t code)
-{
-    hipMemsetAsync(d->d_fault, 0, 8, d->stream);
-    if (code & 0x40000u)
-        return fail("device-side fault 0x%x (a segment exceeded the LDS tile of the finishing pass); results are invalid", code);
-    return fail("device-side fault 0x%x (look-back wait exceeded its bound); results are invalid", code);
-}
-
-int adlhip_sync(adlhip_device* d)
+int adlhip_selftest_lds_order(adlhip_device* d, int workgroups, uint32_t* mismatches)
 {
     if (bind(d)) return ADLHIP_FAILURE;
-    // pick up the device-side fault words together with the drain
-    HIPCHK(hipMemcpyAsync(d->h_fault, d->d_fault, 8, hipMemcpyDeviceToHost, d->stream));
+    if (!mismatches) return fail("null out pointer");
+    if (workgroups < 1 || workgroups > 65536) return fail("selftest: workgroups must be in [1,65536]");
+    return run_lds_order_selftest(d, workgroups, mismatches);
+}
+
+int adlhip_selftest_probe_positions(adlhip_device* d, size_t n, uint32_t* max_index, uint32_t* out_of_cell)
+{
+    if (bind(d)) return ADLHIP_FAILURE;
+    if (!max_index || !out_of_cell) return fail("null out pointer");
+    if (n < 16384 || n > kMaxElems) return fail("selftest: n must be in [16384, %zu]", (size_t)kMaxElems);
+    // two words of the dictionary block's count[] serve as the result (free between sorts: a net that uses the dictionary clears
+    // count[] before it counts, kIdleTable)
+    uint32_t* res = d->d_dict->count;
+    HIPCHK(hipMemsetAsync(res, 0, 8, d->stream));
+    int rc = launch(d, "probe_positions_selftest", [&] {
+        hipLaunchKernelGGL(adlhip::probe_positions_selftest_kernel, dim3(1), dim3(1024), 0, d->stream, (uint32_t)n, res);
+    });
+    if (rc) return rc;
+    uint32_t h[2] = {0u, 0u};
+    HIPCHK(hipMemcpyAsync(h, res, 8, hipMemcpyDeviceToHost, d->stream));
+    HIPCHK(hipMemsetAsync(res, 0, 8, d->stream));
     HIPCHK(hipStreamSynchronize(d->stream));
-    reap_staging(d, true);
-    uint32_t code = d->h_fault[1];
-    if (d->fault_snap) {   // a snapshot taken before this drain has landed too
-        code |= d->h_fault[4];
-        d->h_fault[4] = 0;
-        hipEventDestroy(d->fault_snap);
-        d->fault_snap = nullptr;
-    }
-    if (code != 0) {
-        d->h_fault[0] = d->h_fault[1] = 0;
-        return report_fault(d, code);
-    }
+    *max_index = h[0];
+    *out_of_cell = h[1];
     return ADLHIP_SUCCESS;
-}
-
-int adlhip_fault_check(adlhip_device* d)
-{
-    if (bind(d)) return ADLHIP_FAILURE;
-    uint32_t code = 0;
-    if (d->fault_snap) {
-        if (hipEventQuery(d->fault_snap) != hipSuccess) return ADLHIP_SUCCESS;   // the last snapshot is still in flight
-        code = d->h_fault[4];
-        d->h_fault[4] = 0;
-    } else {
-        HIPCHK(hipEventCreateWithFlags(&d->fault_snap, hipEventDisableTiming));
-    }
-    if (code != 0) report_fault(d, code);   // clears the device words BEFORE the next snapshot is taken: reported once
-    HIPCHK(hipMemcpyAsync(d->h_fault + 4, d->d_fault + 1, 4, hipMemcpyDeviceToHost, d->stream));
-    HIPCHK(hipEventRecord(d->fault_snap, d->stream));
-    return code != 0 ? ADLHIP_FAILURE : ADLHIP_SUCCESS;
-}
-
-int adlhip_flush(adlhip_device* d) { return bind(d); }
-
-int adlhip_malloc(adlhip_device* d, size_t bytes, void** dptr)
-{
-    if (bind(d)) return ADLHIP_FAILURE;
-    if (!dptr) return fail("null out pointer");
-    *dptr = nullptr;
-    if (bytes == 0) return ADLHIP_SUCCESS;
-    hipError_t e = hipMalloc(dptr, bytes);
-    if (e != hipSuccess) {   // AdlCL.inl:390-406: log, leave m_ptr = 0
-        *dptr = nullptr;
-        return fail("hipMalloc(%zu) failed: %s", bytes, hipGetErrorString(e));
-    }
-    d->used_bytes += bytes;
-    if (trace_level()) fprintf(stderr, "[adlhip] malloc %p + %zu\n", *dptr, bytes);
-    return ADLHIP_SUCCESS;
-}
-
-int adlhip_free(adlhip_device* d, void* dptr, size_t bytes)
-{
-    if (bind(d)) return ADLHIP_FAILURE;
-    if (!dptr) return ADLHIP_SUCCESS;
-    if (trace_level()) fprintf(stderr, "[adlhip] free %p + %zu\n", dptr, bytes);
-    HIPCHK(hipStreamSynchronize(d->stream));   // queued work may still use it
-    HIPCHK(hipFree(dptr));
-    d->used_bytes -= std::min<uint64_t>(bytes, d->used_bytes);
-    return ADLHIP_SUCCESS;
-}
-
-int adlhip_memcpy_h2d(adlhip_device* d, void* dst, const void* src, size_t bytes)
-{
-    if (bind(d)) return ADLHIP_FAILURE;
-    if (bytes == 0) return ADLHIP_SUCCESS;
-    if (trace_level()) fprintf(stderr, "[adlhip] h2d %p <- %p + %zu\n", dst, src, bytes);
-    HIPCHK(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, d->stream));
-    return ADLHIP_SUCCESS;
-}
-
-int adlhip_memcpy_d2h(adlhip_device* d, void* dst, const void* src, size_t bytes)
-{
-    if (bind(d)) return ADLHIP_FAILURE;
-    if (bytes == 0) return ADLHIP_SUCCESS;
-    if (trace_level()) fprintf(stderr, "[adlhip] d2h %p <- %p + %zu\n", dst, src, bytes);
-    HIPCHK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, d->stream));
-    return ADLHIP_SUCCESS;
-}
-
-int adlhip_memcpy_d2d(adlhip_device* d, void* dst, const void* src, size_t bytes)
-{
-    if (bind(d)) return ADLHIP_FAILURE;
-    if (bytes == 0) return ADLHIP_SUCCESS;
-    HIPCHK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, d->stream));
-    return ADLHIP_SUCCESS;
-}
-
-int adlhip_memset(adlhip_device* d, void* dptr, int byte_value, size_t bytes)
-{
-    if (bind(d)) return ADLHIP_FAILURE;
-    if (bytes == 0) return ADLHIP_SUCCESS;
-    HIPCHK(hipMemsetAsync(dptr, byte_value, bytes, d->stream));
-    return ADLHIP_SUCCESS;
-}
-
-int adlhip_fill_u32(adlhip_device* d, void* dptr, uint32_t pattern, size_t count)
-{
-    if (bind(d)) return ADLHIP_FAILURE;
-    if (count == 0) return ADLHIP_SUCCESS;
-    const int grid = (int)std::min<size_t>((count + 255) / 256, (size_t)d->prop.multiProcessorCount * 8);
-    return launch(d, "fill_u32", [&] {
-        hipLaunchKernelGGL(adlhip::fill_u32_kernel, dim3(grid), dim3(256), 0, d->stream, (uint32_t*)dptr, pattern, count);
-    });
-}
-
-int adlhip_fill_pattern(adlhip_device* d, void* dptr, const void* pattern, size_t pattern_bytes, size_t count)
-{
-    if (bind(d)) return ADLHIP_FAILURE;
-    if (pattern_bytes != 4 && pattern_bytes != 8 && pattern_bytes != 16) return fail("fill: pattern of %zu bytes (4, 8 or 16)", pattern_bytes);
-    if (count == 0) return ADLHIP_SUCCESS;
-    if (!dptr || !pattern) return fail("fill: null pointer");
-    if (reinterpret_cast<uintptr_t>(dptr) % pattern_bytes) return fail("fill: destination not aligned to the pattern size");
-    if (pattern_bytes == 4) {
-        uint32_t v;
-        memcpy(&v, pattern, 4);
-        return adlhip_fill_u32(d, dptr, v, count);
-    }
-    uint4 p16;
-    uint2 p8 = make_uint2(0u, 0u);
-    uint2* tail = nullptr;
-    uint4* dst = reinterpret_cast<uint4*>(dptr);
-    size_t vecs = count;
-    if (pattern_bytes == 16) {
-        memcpy(&p16, pattern, 16);
-    } else {
-        memcpy(&p8, pattern, 8);
-        p16 = make_uint4(p8.x, p8.y, p8.x, p8.y);
-        uint2* d8 = reinterpret_cast<uint2*>(dptr);
-        size_t c = count;
-        if (reinterpret_cast<uintptr_t>(dptr) & 8u) {   // leading odd element: written through the tail slot of a first launch
-            int rc = launch(d, "fill_pattern", [&] {
-                hipLaunchKernelGGL(adlhip::fill_pattern16_kernel, dim3(1), dim3(256), 0, d->stream, (uint4*)nullptr, p16, (size_t)0, d8, p8);
-            });
-            if (rc) return rc;
-            ++d8;
-            if (--c == 0) return ADLHIP_SUCCESS;
-        }
-        dst = reinterpret_cast<uint4*>(d8);
-        vecs = c / 2;
-        if (c & 1) tail = d8 + (c - 1);
-    }
-    const int grid = (int)std::max<size_t>(1, std::min<size_t>((vecs + 255) / 256, (size_t)d->prop.multiProcessorCount * 8));
-    return launch(d, "fill_pattern", [&] {
-        hipLaunchKernelGGL(adlhip::fill_pattern16_kernel, dim3(grid), dim3(256), 0, d->stream, dst, p16, vecs, tail, p8);
-    });
-}
-
-int adlhip_map(adlhip_device* d, void* dptr, size_t bytes, void** hptr)
-{
-    if (bind(d)) return ADLHIP_FAILURE;
-    if (!hptr) return fail("null out pointer");
-    *hptr = nullptr;
-    reap_staging(d, false);
-    if (bytes == 0) return ADLHIP_SUCCESS;
-    void* h = nullptr;
-    size_t cap = bytes;
-    for (size_t i = 0; i < d->pinned_pool.size(); ++i) {   // smallest pooled block that fits without wasting more than half
-        const PinnedBlock b = d->pinned_pool[i];
-        if (b.capacity >= bytes && b.capacity <= 2 * bytes + 4096 && (!h || b.capacity < cap)) {
-            h = b.hptr;
-            cap = b.capacity;
-        }
-    }
-    if (h) {
-        for (size_t i = 0; i < d->pinned_pool.size(); ++i)
-            if (d->pinned_pool[i].hptr == h) {
-                d->pinned_pool[i] = d->pinned_pool.back();
-                d->pinned_pool.pop_back();
-                break;
-            }
-        d->pinned_pool_bytes -= cap;
-    } else {
-        HIPCHK(hipHostMalloc(&h, bytes));
-    }
-    hipError_t e = hipMemcpyAsync(h, dptr, bytes, hipMemcpyDeviceToHost, d->stream);
-    if (e != hipSuccess) {
-        hipHostFree(h);
-        return fail("map: device->host copy failed: %s", hipGetErrorString(e));
-    }
-    d->staging.push_back({h, bytes, nullptr, cap});
-    *hptr = h;
-    return ADLHIP_SUCCESS;
-}
-
-int adlhip_unmap(adlhip_device* d, void* dptr, void* hptr, size_t bytes)
-{
-    if (bind(d)) return ADLHIP_FAILURE;
-    if (!hptr) return ADLHIP_SUCCESS;
-    for (auto& s : d->staging) {
-        if (s.hptr == hptr && !s.done) {
-            if (bytes > s.bytes) return fail("unmap: %zu bytes exceeds the mapped %zu", bytes, s.bytes);
-            if (bytes == 0) bytes = s.bytes;   // 0 = the whole mapping (Buffer::returnHostPtr carries no size)
-            HIPCHK(hipMemcpyAsync(dptr, hptr, bytes, hipMemcpyHostToDevice, d->stream));
-            hipEvent_t ev;
-            HIPCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-            HIPCHK(hipEventRecord(ev, d->stream));
-            s.done = ev;
-            return ADLHIP_SUCCESS;
-        }
-    }
-    return fail("unmap: pointer %p was not returned by adlhip_map", hptr);
 }
 
 // ---- sort ---------------------------------------------------------------------------------------
@@ -2560,259 +2168,6 @@ int adlhip_partition_top_byte_kv32(adlhip_device* d, const void* in, void* out, 
                                               work_bytes, n);
 }
 
-// ---- synthetic inputs ---------------------------------------------------------------------------
-
-int adlhip_generate_keys(adlhip_device* d, int elem_kind, void* dptr, size_t n, uint64_t seed, uint64_t first_index)
-{
-    if (bind(d)) return ADLHIP_FAILURE;
-    if (elem_kind < ADLHIP_ELEM_U32 || elem_kind > ADLHIP_ELEM_U64) return fail("bad element kind %d", elem_kind);
-    if (n == 0) return ADLHIP_SUCCESS;
-    if (!dptr) return fail("null buffer");
-    const uint64_t base = seed * 0x9E3779B97F4A7C15ull + first_index;
-    const int grid = (int)std::min<size_t>((n + 255) / 256, (size_t)d->prop.multiProcessorCount * 16);
-    return launch(d, "generate_keys", [&] {
-        hipLaunchKernelGGL(adlhip::generate_keys_kernel, dim3(grid), dim3(256), 0, d->stream, dptr, n, base, first_index, elem_kind);
-    });
-}
-
-// ---- knobs ------------------------------------------------------------------------------------
-
-int adlhip_set_param(adlhip_device* d, const char* name, int value)
-{
-    if (!d || !name) return fail("null argument");
-    if (!strcmp(name, "sort.algo")) {
-        if (value < -1 || value > 1) return fail("sort.algo must be -1, 0 or 1");
-        d->sort_algo = value;
-    } else if (!strcmp(name, "sort.digit_bits")) {
-        if (value != 4 && value != 7 && value != 8) return fail("sort.digit_bits must be 4, 7 or 8");
-        d->digit_bits = value;
-    } else if (!strcmp(name, "sort.tile")) {
-        if (value < -1 || value >= kNumVariants) return fail("sort.tile must be in [-1,%d)", kNumVariants);
-        d->tile_variant = value;
-
-    } else if (!strcmp(name, "sort.mid")) {
-        if (value < 0 || value > 3) return fail("sort.mid must be 0 (off), 1 (on), 2 (keys: always the two-launch form) or 3 (always the three-launch form)");
-        d->mid_path = value;
-    } else if (!strcmp(name, "sort.msd2")) {
-        if (value < 0 || value > 5)
-            return fail("sort.msd2 must be 0 (off), 1 (on), 2 (always, from 1 Mi elements; forms by size), 3 (always the stable passes), "
-                        "4 (always the cursor passes for whole keys) or 5 (always the hybrid form for whole keys)");
-        d->msd2_path = value;
-    } else if (!strcmp(name, "sort.persist")) {
-        if (value != 0 && value != 1) return fail("sort.persist must be 0 (one tile per workgroup, round 3) or 1 (persistent prefetching passes + 16-bit finish)");
-        d->persist = value;
-    } else if (!strcmp(name, "sort.net_lookback")) {
-        d->net_lookback = value ? 1 : 0;
-    } else if (!strcmp(name, "partition.lookback")) {
-        d->partition_lookback = value ? 1 : 0;
-    } else if (!strcmp(name, "sort.dict")) {
-        if (value != 0 && value != 1) return fail("sort.dict must be 0 (off) or 1 (counting sort for keys that take few distinct values)");
-        d->dict_path = value;
-    } else if (!strcmp(name, "sort.binfinish")) {
-        if (value < 0 || value > 2) return fail("sort.binfinish must be 0 (LSD finish), 1 (binning finish for whole u64 keys from 24 Mi keys up) or 2 (always, u32 keys too)");
-        d->bin_finish = value;
-    } else if (!strcmp(name, "topk.algo")) {
-        if (value < -1 || value > 1) return fail("topk.algo must be -1 (by k), 0 (always the full argsort) or 1 (always the selection)");
-        d->topk_algo = value;
-    } else if (!strcmp(name, "topk.rows_algo")) {
-        if (value < -1 || value > 1) return fail("topk.rows_algo must be -1 (by k and cols), 0 (always the per-row loop) or 1 (always the row kernel)");
-        d->topk_rows_algo = value;
-    } else if (!strcmp(name, "debug.topk_rows_grid")) {
-        if (value < 0) return fail("debug.topk_rows_grid must be >= 0");
-        d->topk_rows_grid = value;
-    } else if (!strcmp(name, "unique.algo")) {
-        if (value != -1 && value != 1) return fail("unique.algo must be -1 (by the outputs asked) or 1 (always the index path)");
-        d->unique_algo = value;
-    } else if (!strcmp(name, "debug.unique_grid")) {
-        if (value < 0) return fail("debug.unique_grid must be >= 0");
-        d->unique_grid = value;
-    } else if (!strcmp(name, "debug.reduce_grid")) {
-        if (value < 0) return fail("debug.reduce_grid must be >= 0");
-        d->reduce_grid = value;
-    } else if (!strcmp(name, "debug.scan_grid")) {
-        if (value < 0) return fail("debug.scan_grid must be >= 0");
-        d->scan_grid = value;
-    } else if (!strcmp(name, "debug.compact_grid")) {
-        if (value < 0) return fail("debug.compact_grid must be >= 0");
-        d->compact_grid = value;
-    } else if (!strcmp(name, "debug.histogram_grid")) {
-        if (value < 0) return fail("debug.histogram_grid must be >= 0");
-        d->histogram_grid = value;
-    } else if (!strcmp(name, "debug.histogram_lds_bins")) {
-        if (value < 0 || value > kHistogramLdsBinsMax) return fail("debug.histogram_lds_bins must be in [1, %d], or 0 for the default", kHistogramLdsBinsMax);
-        d->histogram_lds_bins = value ? value : kHistogramLdsBinsMax;
-    } else if (!strcmp(name, "debug.persist_grid")) {
-        if (value < 0 || value > 4096) return fail("debug.persist_grid must be in [0, 4096]");
-        d->persist_grid = value;
-    } else if (!strcmp(name, "debug.resident_wgs")) {
-        // what the paths with a grid-wide barrier (the safety nets) and the one-workgroup-per-bucket finish may count on;
-        // 0 = ask the device again.  Tests use it to stand in for a small partition.
-        if (value < 0) return fail("debug.resident_wgs must be >= 0");
-        d->resident_wgs = value ? value : d->resident_wgs_device;
-    } else if (!strcmp(name, "debug.idle_poke")) {
-        // the idle checker's positive control: flips bit 0 of one handle-owned word, in stream order (a second poke undoes it)
-        const int region = (int)((uint32_t)value >> 24);
-        const uint32_t word = (uint32_t)value & 0xffffffu;
-        if (region < 1 || region > kIdleRegions || word >= idle_region_words(region))
-            return fail("debug.idle_poke: no word %u in region %d (region << 24 | word; regions 1 d_msd2, 2 d_mid_hist, 3 d_dict, 4 d_fault)", word, region);
-        if (bind(d)) return ADLHIP_FAILURE;
-        hipLaunchKernelGGL(idle_poke_kernel, dim3(1), dim3(1), 0, d->stream, idle_region_base(d, region) + word);
-        HIPCHK(hipGetLastError());
-    } else if (!strcmp(name, "sort.rank")) {
-        if (value != 0 && value != 1) return fail("sort.rank must be 0 or 1");
-        if (value == 1 && !d->lds_ordered) return fail("sort.rank = 1 needs lane-ordered DS atomics; the device self-test failed");
-        d->rank_mode = value;
-    } else if (!strcmp(name, "profile")) {
-        if (bind(d)) return ADLHIP_FAILURE;
-        if (!value && fold_profile(d)) return ADLHIP_FAILURE;
-        d->profile = value ? 1 : 0;
-    } else {
-        return fail("unknown parameter '%s'", name);
-    }
-    return ADLHIP_SUCCESS;
-}
-
-int adlhip_get_param(adlhip_device* d, const char* name, int* value)
-{
-    if (!d || !name || !value) return fail("null argument");
-    if (!strcmp(name, "sort.algo")) *value = d->sort_algo;
-    else if (!strcmp(name, "sort.digit_bits")) *value = d->digit_bits;
-    else if (!strcmp(name, "sort.tile")) *value = d->tile_variant;
-    else if (!strcmp(name, "sort.rank")) *value = d->rank_mode;
-    else if (!strcmp(name, "sort.mid")) *value = d->mid_path;
-    else if (!strcmp(name, "sort.msd2")) *value = d->msd2_path;
-    else if (!strcmp(name, "sort.binfinish")) *value = d->bin_finish;
-    else if (!strcmp(name, "sort.persist")) *value = d->persist;
-    else if (!strcmp(name, "sort.dict")) *value = d->dict_path;
-    else if (!strcmp(name, "topk.algo")) *value = d->topk_algo;
-    else if (!strcmp(name, "topk.rows_algo")) *value = d->topk_rows_algo;
-    else if (!strcmp(name, "debug.topk_rows_grid")) *value = d->topk_rows_grid;
-    else if (!strcmp(name, "unique.algo")) *value = d->unique_algo;
-    else if (!strcmp(name, "debug.unique_grid")) *value = d->unique_grid;
-    else if (!strcmp(name, "debug.reduce_grid")) *value = d->reduce_grid;
-    else if (!strcmp(name, "debug.scan_grid")) *value = d->scan_grid;
-    else if (!strcmp(name, "debug.compact_grid")) *value = d->compact_grid;
-    else if (!strcmp(name, "debug.histogram_grid")) *value = d->histogram_grid;
-    else if (!strcmp(name, "debug.histogram_lds_bins")) *value = d->histogram_lds_bins;
-    else if (!strcmp(name, "debug.persist_grid")) *value = d->persist_grid;
-    else if (!strcmp(name, "partition.lookback")) *value = d->partition_lookback;
-    else if (!strcmp(name, "sort.net_lookback")) *value = d->net_lookback;
-    else if (!strcmp(name, "debug.resident_wgs")) *value = d->resident_wgs;
-    else if (!strcmp(name, "stat.net_runs") || !strcmp(name, "stat.net_counting")) {
-        // how often the large sort's safety net has run on this handle, and how often it sorted by counting (waits for the stream)
-        uint32_t v[2] = {0u, 0u};
-        HIPCHK(hipMemcpyAsync(v, net_stats(d), 8, hipMemcpyDeviceToHost, d->stream));
-        HIPCHK(hipStreamSynchronize(d->stream));
-        *value = (int)v[name[9] == 'c' ? 1 : 0];
-    }
-    else if (!strcmp(name, "debug.idle_dirty") || !strcmp(name, "debug.idle_first")) {
-        // handle-owned words that are not at their idle value (kIdleTable), and the first of them as region << 24 | word (0 = clean);
-        // waits for the stream, changes nothing on the device
-        uint32_t dirty = 0u, first = 0u;
-        if (idle_check(d, &dirty, &first)) return ADLHIP_FAILURE;
-        *value = (int)(name[11] == 'd' ? dirty : first);
-    }
-    else if (!strncmp(name, "debug.net_stamp", 15) && name[15] >= '0' && name[15] <= '9' && !name[16]) {
-        // diagnostic: when workgroup 0 of the last net reached its k-th phase boundary, in 10-ns ticks (low 31 bits; tools/net_phases.py)
-        uint32_t v = 0u;
-        HIPCHK(hipMemcpyAsync(&v, net_stats(d) + 4 + (name[15] - '0'), 4, hipMemcpyDeviceToHost, d->stream));
-        HIPCHK(hipStreamSynchronize(d->stream));
-        *value = (int)(v & 0x7fffffffu);
-    }
-    else if (!strcmp(name, "sort.lds_ordered")) *value = d->lds_ordered;
-    else if (!strcmp(name, "profile")) *value = d->profile;
-    else return fail("unknown parameter '%s'", name);
-    return ADLHIP_SUCCESS;
-}
-
-// ---- events / profiling ---------------------------------------------------------------------------
-
-int adlhip_event_create(adlhip_device* d, adlhip_event** out)
-{
-    if (bind(d)) return ADLHIP_FAILURE;
-    if (!out) return fail("null out pointer");
-    adlhip_event* e = new adlhip_event();
-    if (hipEventCreate(&e->ev) != hipSuccess) {
-        delete e;
-        return fail("hipEventCreate failed");
-    }
-    *out = e;
-    return ADLHIP_SUCCESS;
-}
-
-int adlhip_event_record(adlhip_device* d, adlhip_event* ev)
-{
-    if (bind(d)) return ADLHIP_FAILURE;
-    if (!ev) return fail("null event");
-    HIPCHK(hipEventRecord(ev->ev, d->stream));
-    return ADLHIP_SUCCESS;
-}
-
-int adlhip_event_elapsed_ms(adlhip_device* d, adlhip_event* a, adlhip_event* b, float* ms)
-{
-    if (bind(d)) return ADLHIP_FAILURE;
-    if (!a || !b || !ms) return fail("null argument");
-    HIPCHK(hipEventSynchronize(b->ev));
-    HIPCHK(hipEventElapsedTime(ms, a->ev, b->ev));
-    return ADLHIP_SUCCESS;
-}
-
-int adlhip_event_synchronize(adlhip_device* d, adlhip_event* ev)
-{
-    if (bind(d)) return ADLHIP_FAILURE;
-    if (!ev) return fail("null event");
-    HIPCHK(hipEventSynchronize(ev->ev));   // (an event that was never recorded is complete)
-    return ADLHIP_SUCCESS;
-}
-
-int adlhip_event_query(adlhip_device* d, adlhip_event* ev, int* done)
-{
-    if (bind(d)) return ADLHIP_FAILURE;
-    if (!ev || !done) return fail("null argument");
-    const hipError_t e = hipEventQuery(ev->ev);
-    if (e != hipSuccess && e != hipErrorNotReady) return fail("hipEventQuery failed: %s", hipGetErrorString(e));
-    (void)hipGetLastError();   // hipErrorNotReady is an answer, not an error to leave behind
-    *done = e == hipSuccess ? 1 : 0;
-    return ADLHIP_SUCCESS;
-}
-
-int adlhip_event_destroy(adlhip_device* d, adlhip_event* ev)
-{
-    if (bind(d)) return ADLHIP_FAILURE;
-    if (!ev) return ADLHIP_SUCCESS;
-    hipEventDestroy(ev->ev);
-    delete ev;
-    return ADLHIP_SUCCESS;
-}
-
-int adlhip_profile_reset(adlhip_device* d)
-{
-    if (bind(d)) return ADLHIP_FAILURE;
-    if (fold_profile(d)) return ADLHIP_FAILURE;
-    d->prof.clear();
-    d->prof_order.clear();
-    return ADLHIP_SUCCESS;
-}
-
-int adlhip_profile_count(adlhip_device* d)
-{
-    if (bind(d)) return -1;
-    if (fold_profile(d)) return -1;
-    return (int)d->prof_order.size();
-}
-
-int adlhip_profile_get(adlhip_device* d, int i, char name_out[64], uint64_t* launches, double* total_ms)
-{
-    if (!d) return fail("null device handle");
-    if (i < 0 || i >= (int)d->prof_order.size()) return fail("profile index %d out of range", i);
-    const std::string& nm = d->prof_order[i];
-    const ProfEntry& e = d->prof[nm];
-    if (name_out) snprintf(name_out, 64, "%s", nm.c_str());
-    if (launches) *launches = e.launches;
-    if (total_ms) *total_ms = e.total_ms;
-    return ADLHIP_SUCCESS;
-}
-
 #ifdef ADLHIP_STAMPS
 // Diagnostic build only: point the phase-stamp side buffer at caller-provided device memory ([tiles][16] u64).
 int adlhip_debug_set_stamp_buffer(adlhip_device* d, void* dptr)
@@ -2823,84 +2178,9 @@ int adlhip_debug_set_stamp_buffer(adlhip_device* d, void* dptr)
 }
 #endif
 
-int adlhip_profile_write_csv(adlhip_device* d, const char* path)
-{
-    if (bind(d)) return ADLHIP_FAILURE;
-    if (!path) return fail("null path");
-    if (fold_profile(d)) return ADLHIP_FAILURE;
-    FILE* probe = fopen(path, "r");
-    const bool fresh = probe == nullptr;
-    if (probe) fclose(probe);
-    FILE* f = fopen(path, "a");
-    if (!f) return fail("cannot open %s for appending", path);
-    if (fresh) fprintf(f, "\"kernel\",\"launches\",\"total_ms\",\"avg_ms\"\n");
-    for (const std::string& nm : d->prof_order) {
-        const ProfEntry& e = d->prof[nm];
-        fprintf(f, "\"%s\",%llu,%.6f,%.6f\n", nm.c_str(), (unsigned long long)e.launches, e.total_ms,
-                e.launches ? e.total_ms / (double)e.launches : 0.0);
-    }
-    fclose(f);
-    return ADLHIP_SUCCESS;
-}
-
-// ---- probes ---------------------------------------------------------------------------------------
-
-int adlhip_probe_copy(adlhip_device* d, void* dst, const void* src, size_t bytes)
-{
-    if (bind(d)) return ADLHIP_FAILURE;
-    const size_t nvec = bytes / 16;
-    if (nvec == 0) return ADLHIP_SUCCESS;
-    const int grid = (int)std::min<size_t>((nvec + 255) / 256, (size_t)d->prop.multiProcessorCount * 8);
-    return launch(d, "probe_copy", [&] {
-        hipLaunchKernelGGL(adlhip::probe_copy_kernel, dim3(grid), dim3(256), 0, d->stream, (uint4*)dst, (const uint4*)src, nvec);
-    });
-}
-
-// hints: bit 0 = non-temporal loads, bit 1 = non-temporal stores; grid_per_cu workgroups of 256 threads per CU (0 = 8)
-int adlhip_probe_copy_ex(adlhip_device* d, void* dst, const void* src, size_t bytes, int hints, int grid_per_cu)
-{
-    if (bind(d)) return ADLHIP_FAILURE;
-    if (hints < 0 || hints > 3 || grid_per_cu < 0 || grid_per_cu > 64) return fail("bad probe variant");
-    const size_t nvec = bytes / 16;
-    if (nvec == 0) return ADLHIP_SUCCESS;
-    const int grid = (int)std::min<size_t>((nvec + 255) / 256, (size_t)d->prop.multiProcessorCount * (grid_per_cu ? grid_per_cu : 8));
-    return launch(d, "probe_copy", [&] {
-        switch (hints) {
-        case 0: hipLaunchKernelGGL((adlhip::probe_copy_hint_kernel<false, false>), dim3(grid), dim3(256), 0, d->stream, (uint4*)dst, (const uint4*)src, nvec); break;
-        case 1: hipLaunchKernelGGL((adlhip::probe_copy_hint_kernel<true, false>), dim3(grid), dim3(256), 0, d->stream, (uint4*)dst, (const uint4*)src, nvec); break;
-        case 2: hipLaunchKernelGGL((adlhip::probe_copy_hint_kernel<false, true>), dim3(grid), dim3(256), 0, d->stream, (uint4*)dst, (const uint4*)src, nvec); break;
-        default: hipLaunchKernelGGL((adlhip::probe_copy_hint_kernel<true, true>), dim3(grid), dim3(256), 0, d->stream, (uint4*)dst, (const uint4*)src, nvec); break;
-        }
-    });
-}
-
-int adlhip_probe_read_ex(adlhip_device* d, const void* src, size_t bytes, void* sink8, int hints, int grid_per_cu)
-{
-    if (bind(d)) return ADLHIP_FAILURE;
-    if (hints < 0 || hints > 1 || grid_per_cu < 0 || grid_per_cu > 64) return fail("bad probe variant");
-    const size_t nvec = bytes / 16;
-    if (nvec == 0) return ADLHIP_SUCCESS;
-    const int grid = (int)std::min<size_t>((nvec + 255) / 256, (size_t)d->prop.multiProcessorCount * (grid_per_cu ? grid_per_cu : 8));
-    return launch(d, "probe_read", [&] {
-        if (hints) hipLaunchKernelGGL((adlhip::probe_read_hint_kernel<true>), dim3(grid), dim3(256), 0, d->stream, (const uint4*)src, nvec, (unsigned long long*)sink8);
-        else hipLaunchKernelGGL((adlhip::probe_read_hint_kernel<false>), dim3(grid), dim3(256), 0, d->stream, (const uint4*)src, nvec, (unsigned long long*)sink8);
-    });
-}
-
-int adlhip_probe_read(adlhip_device* d, const void* src, size_t bytes, void* sink8)
-{
-    if (bind(d)) return ADLHIP_FAILURE;
-    const size_t nvec = bytes / 16;
-    if (nvec == 0) return ADLHIP_SUCCESS;
-    const int grid = (int)std::min<size_t>((nvec + 255) / 256, (size_t)d->prop.multiProcessorCount * 8);
-    return launch(d, "probe_read", [&] {
-        hipLaunchKernelGGL(adlhip::probe_read_kernel, dim3(grid), dim3(256), 0, d->stream, (const uint4*)src, nvec,
-                           (unsigned long long*)sink8);
-    });
-}
-
 }  // extern "C"
 
 #ifdef ADLHIP_SINGLE_TU
+#include "handle.hip"
 #include "primitives.hip"
 #endif

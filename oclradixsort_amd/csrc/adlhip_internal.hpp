@@ -1,5 +1,8 @@
-// adlhip_internal.hpp -- what the library's two host units share: adlhip.hip (handle, buffers, profiling, the sorts, scan, knobs) and
-// primitives.hip (typed sort, top-k, unique, reduce by key: everything built on top of the sorts).  Not installed; nothing here is ABI.
+// adlhip_internal.hpp -- what the library's three host units share.  handle.hip defines the runtime under everything: the error text,
+// the handle (create, teardown, sync, buffers, map / unmap, events, profiling), the probes and the knob table.  adlhip.hip defines
+// the sorts, the scan and the partitions, and what a handle owns for them (sort_state_create / sort_state_destroy, the idle table).
+// primitives.hip defines what is built on top of the sorts (typed sort, top-k, unique, reduce by key, scans, compaction, histograms).
+// Not installed; nothing here is ABI.
 #pragma once
 #include "../../include/adlhip.h"
 
@@ -46,46 +49,52 @@ struct adlhip_device {
     bool own_stream = true;
     hipDeviceProp_t prop;
     uint64_t used_bytes = 0;
-    // knobs
-    int sort_algo = -1;       // -1 automatic by size, 0 onesweep, 1 three-kernel pass
-    int digit_bits = 8;       // 8 or 4
-    int profile = 0;
-    int tile_variant = -1;    // index into kVariants; -1 = best known per element size
-    int rank_mode = 1;        // 1 = lane-ordered DS atomic ranking (needs lds_ordered), 0 = ballot match
-    int lds_ordered = 0;      // result of the device self-test at creation
-    int resident_wgs_device = 0;
-    int resident_wgs = 0;     // workgroups of <= 80 KiB LDS / 512 threads that are certainly resident at once (2 per CU); the paths
-                              // whose kernels hold a grid-wide barrier over 256 workgroups are taken only when this is >= 256
-    int mid_path = 1;         // 16 Ki < n <= 2 Mi: MSD pass + LDS finish (three launches) instead of per-digit passes
+    // ---- knobs: one row each in kKnobs (handle.hip), in this order ---------------------------------------------------------------
+    int sort_algo = -1;       // "sort.algo": -1 automatic by size, 0 onesweep, 1 three-kernel pass
+    int mid_path = 1;         // "sort.mid": 16 Ki < n <= 2 Mi: MSD pass + LDS finish (three launches) instead of per-digit passes
+    int msd2_path = 1;        // "sort.msd2": the large sort (msd2_sort for keys, msd2s_sort for pairs); 2 = forced (tests)
+    int persist = 1;          // "sort.persist": the cursor passes of the large sort as persistent, prefetching kernels + the 16-bit finish
+    int dict_path = 1;        // "sort.dict": the large sort's safety net first tries the counting sort for keys that take at most
+                              // 256 values (dict_kernels.hpp); 0 = off
+    int bin_finish = 1;       // "sort.binfinish": the large keys-only sort finishes its segments with one counting pass + compares
+                              // (1: u64 keys, 2: u32 keys too, 0: the wave-per-segment LSD finish)
+    int topk_algo = -1;       // "topk.algo": -1 selection up to kTopkSelectMaxFraction of n, the full argsort above; 0 / 1 force
+                              // the argsort / the selection
+    int topk_rows_algo = -1;  // "topk.rows_algo": -1 the row kernel while k <= kRowMaxK and cols <= kTopkRowsMaxCols, the per-row
+                              // loop above; 0 / 1 force the loop / the row kernel
+    int topk_rows_grid = 0;   // "debug.topk_rows_grid": workgroups of the row kernel at most (0: kTopkRowsWgsPerCu per CU)
+    int unique_grid = 0;      // "debug.unique_grid": workgroups of the run stage at most (0: kUniqueWgsPerCu per CU)
+    int reduce_grid = 0;      // "debug.reduce_grid": workgroups of the reduce stage at most (0: kReduceWgsPerCu per CU)
+    int scan_grid = 0;        // "debug.scan_grid": workgroups of the scan stage at most (0: kScanWgsPerCu per CU)
+    int compact_grid = 0;     // "debug.compact_grid": workgroups of the compaction at most (0: kCompactWgsPerCu per CU)
+    int histogram_grid = 0;   // "debug.histogram_grid": workgroups of the histogram's count kernel at most (0: hist_grid_cap)
+    int persist_grid = 0;     // "debug.persist_grid": workgroups of the large sort's persistent passes, rounded up to a
+                              // multiple of 8 (0: two per CU)
+    // (with a rule of their own)
+    int digit_bits = 8;       // "sort.digit_bits": 8, 7 or 4
+    int unique_algo = -1;     // "unique.algo": -1 the keys path unless first_index or inverse is asked, 1 always the index path
+    int tile_variant = -1;    // "sort.tile": index into kVariants; -1 = best known per element size
+    int net_lookback = 1;     // "sort.net_lookback": the large sort's safety net runs look-back passes (0: count-scan-scatter passes)
+    int partition_lookback = 1;   // "partition.lookback": the MSB partition as one look-back pass where it pays (0: always three kernels)
+    int profile = 0;          // "profile": an event pair around every launch
+    int histogram_lds_bins = adlhip_internal::kHistogramLdsBinsMax;   // "debug.histogram_lds_bins": bincount takes the LDS path up to this many bins
+    int resident_wgs = 0;     // "debug.resident_wgs": workgroups of <= 80 KiB LDS / 512 threads that are certainly resident at once (2 per
+                              // CU); the paths whose kernels hold a grid-wide barrier over 256 workgroups are taken only when this is >= 256
+    int rank_mode = 1;        // "sort.rank": 1 = lane-ordered DS atomic ranking (needs lds_ordered), 0 = ballot match
+    int lds_ordered = 0;      // "sort.lds_ordered" (read only): result of the device self-test at creation
+    // ---- not knobs ----------------------------------------------------------------------------------------------------------------
+    int resident_wgs_device = 0;   // what the device answered at creation ("debug.resident_wgs" = 0 restores it)
     int mid_skip = 0;         // eligible sorts still to be sent down the per-digit passes after a skewed input (see mid_eligible)
     int mid2_skip = 0;        // keys-only sorts still to take the three-launch form after a slab overflow (see mid_sort_keys)
     int mid_backoff = 32, mid2_backoff = 64;
-    int bin_finish = 1;       // "sort.binfinish": the large keys-only sort finishes its segments with one counting pass + compares
-                              // (1: u64 keys, 2: u32 keys too, 0: the wave-per-segment LSD finish)
-    int persist = 1;          // "sort.persist": the cursor passes of the large sort as persistent, prefetching kernels + the 16-bit finish
-    int msd2_path = 1;        // "sort.msd2": the large sort (msd2_sort for keys, msd2s_sort for pairs); 2 = forced (tests)
-    int net_lookback = 1;                   // "sort.net_lookback": the large sort's safety net runs look-back passes (0: count-scan-scatter passes)
-    int partition_lookback = 1;             // "partition.lookback": the MSB partition as one look-back pass where it pays (0: always three kernels)
-    int dict_path = 1;                      // "sort.dict": the large sort's safety net first tries the counting sort for keys that take at most
-                                            // 256 values (dict_kernels.hpp); 0 = off
-    int topk_algo = -1;                     // "topk.algo": -1 selection up to kTopkSelectMaxFraction of n, the full argsort above; 0 / 1 force
-                                            // the argsort / the selection
-    int topk_rows_algo = -1;                // "topk.rows_algo": -1 the row kernel while k <= kRowMaxK and cols <= kTopkRowsMaxCols, the per-row
-                                            // loop above; 0 / 1 force the loop / the row kernel
-    int topk_rows_grid = 0;                 // "debug.topk_rows_grid": workgroups of the row kernel at most (0: kTopkRowsWgsPerCu per CU)
-    int unique_algo = -1;                   // "unique.algo": -1 the keys path unless first_index or inverse is asked, 1 always the index path
-    int unique_grid = 0;                    // "debug.unique_grid": workgroups of the run stage at most (0: kUniqueWgsPerCu per CU)
-    int reduce_grid = 0;                    // "debug.reduce_grid": workgroups of the reduce stage at most (0: kReduceWgsPerCu per CU)
-    int scan_grid = 0;                      // "debug.scan_grid": workgroups of the scan stage at most (0: kScanWgsPerCu per CU)
-    int compact_grid = 0;                   // "debug.compact_grid": workgroups of the compaction at most (0: kCompactWgsPerCu per CU)
-    int histogram_grid = 0;                 // "debug.histogram_grid": workgroups of the histogram's count kernel at most (0: hist_grid_cap)
-    int histogram_lds_bins = adlhip_internal::kHistogramLdsBinsMax;   // "debug.histogram_lds_bins": bincount takes the LDS path up to this many bins
-    int persist_grid = 0;                   // "debug.persist_grid": workgroups of the large sort's persistent passes, rounded up to a
-                                            // multiple of 8 (0: two per CU)
-    adlhip::DictBlock* d_dict = nullptr;    // its dictionary and counters (handle-owned; rebuilt by every net that uses them)
+    // the sorts' device state (sort_state_create / sort_state_destroy, adlhip.hip)
+    adlhip::DictBlock* d_dict = nullptr;    // the net's dictionary and counters (rebuilt by every net that uses them)
     uint32_t* d_msd2 = nullptr;   // the large sort's handle-owned words, allocated with the handle: cursors of pass 1 (256, one
                                   // 128-byte line each) and pass 2 (65536), overflow flag, done counter, the safety net's barrier
                                   // counter, the four sample words, ...; what each holds between sorts: kIdleTable
+    uint32_t* d_mid_hist = nullptr;    // [16][4][256] slice histograms of the mid-size sort + 512 words of bucket cursors / flags
+                                       // of its keys-only form (hybrid_kernels.hpp SegSlab): zero between sorts, but for the
+                                       // barrier counter its first kernel clears (kIdleTable)
     // profiling
     std::vector<adlhip_internal::PendingProf> pending;
     std::vector<hipEvent_t> event_pool;
@@ -101,12 +110,9 @@ struct adlhip_device {
     uint32_t* d_fault = nullptr;
     uint32_t* h_fault = nullptr;   // pinned: [0..1] filled by adlhip_sync, [4] by the last adlhip_fault_check snapshot
     hipEvent_t fault_snap = nullptr;   // recorded behind the last snapshot copy; null = none pending
-    uint32_t* d_mid_hist = nullptr;    // [16][4][256] slice histograms of the mid-size sort + 512 words of bucket cursors / flags
-                                       // of its keys-only form (hybrid_kernels.hpp SegSlab): zero between sorts, but for the
-                                       // barrier counter its first kernel clears (kIdleTable)
 };
 
-// the calling thread's error text (adlhip.hip; not in include/adlhip.h: sharded.cpp sets it too).  typed_keys_sort saves the text
+// the calling thread's error text (handle.hip; not in include/adlhip.h: sharded.cpp sets it too).  typed_keys_sort saves the text
 // with adlhip_last_error and puts it back with this
 extern "C" void adlhip_set_last_error(const char* text);
 
@@ -119,12 +125,27 @@ struct V16 {
 }  // namespace
 
 namespace adlhip_internal {
-// ---- defined in adlhip.hip --------------------------------------------------------------------------------------------------------
+// ---- defined in handle.hip --------------------------------------------------------------------------------------------------------
 int fail(const char* fmt, ...);             // sets the error text; returns ADLHIP_FAILURE
 int bind(adlhip_device* d);
 hipEvent_t take_event(adlhip_device* d);
 int trace_level();                          // ADLHIP_TRACE
 const char* intern(const std::string& s);   // kernel names (the profiler keeps the pointer until the events are folded)
+
+// ---- defined in adlhip.hip --------------------------------------------------------------------------------------------------------
+// What a handle owns for the sorts: d_mid_hist, d_msd2, d_dict, and what the device answers at creation (lds_ordered / rank_mode,
+// resident_wgs).  create sets the error text and leaves what it has allocated to destroy, which frees whatever exists and calls
+// neither fail nor HIPCHK (it is part of the handle's one teardown)
+#pragma GCC visibility push(hidden)   // called between the library's own units only: kept out of its dynamic symbol table
+int sort_state_create(adlhip_device* d);
+void sort_state_destroy(adlhip_device* d);
+int num_tile_variants();   // "sort.tile" accepts -1 .. num_tile_variants() - 1
+// the knobs that are no field of the handle but words of the sorts' device state: "debug.idle_poke" (set), "stat.net_runs",
+// "stat.net_counting", "debug.idle_dirty", "debug.idle_first", "debug.net_stamp0".."9" (get).  kNoSuchParam for any other name
+constexpr int kNoSuchParam = -1;
+int sort_set_param(adlhip_device* d, const char* name, int value);
+int sort_get_param(adlhip_device* d, const char* name, int* value);
+#pragma GCC visibility pop
 
 struct SoaWideLayout {
     size_t off_pairs_a, off_pairs_b, off_kv, kv_bytes, total;

@@ -26,8 +26,8 @@ U32, KV32, U64, SOA32 = 0, 1, 2, 3   # ADLHIP_ELEM_*
 # ---------------------------------------------------------------------------------------------
 # mirror of the host's capacities (oclradixsort_amd/csrc/adlhip.hip)
 # ---------------------------------------------------------------------------------------------
-FULL_PCT, LEAN_PCT = 50, 12   # kFullHeadroomPct, kLeanHeadroomPct (adlhip.hip:1057)
-STRIDE0 = 1536                # kMsd2Stride0 (adlhip.hip:1006)
+FULL_PCT, LEAN_PCT = 50, 12   # kFullHeadroomPct, kLeanHeadroomPct (adlhip.hip)
+STRIDE0 = 1536                # kMsd2Stride0 (adlhip.hip)
 
 
 def _align_up(x, a):
@@ -43,7 +43,7 @@ def _sd(mean):
 
 
 def msd2_tier_b(n, slots=65536, fine=False):
-    """adlhip.hip:1011 msd2_tier_b: the finish's tile that holds the mean segment + 7.5 sd"""
+    """adlhip.hip msd2_tier_b: the finish's tile that holds the mean segment + 7.5 sd"""
     mean = (n + slots - 1) // slots
     need = mean + (15 * _sd(mean) + 1) // 2
     if fine and 2560 < need <= 4096:
@@ -54,7 +54,7 @@ def msd2_tier_b(n, slots=65536, fine=False):
 
 
 def msd2_stride_b(n, slots=65536, fine=False, lean=False):
-    """adlhip.hip:1025 msd2_stride_b: mean + 50 % (lean: the mean), or mean + 7.5 sd where that is more, + 8, in steps of 64,
+    """adlhip.hip msd2_stride_b: mean + 50 % (lean: the mean), or mean + 7.5 sd where that is more, + 8, in steps of 64,
     at most the tile"""
     mean = (n + slots - 1) // slots
     want = _align_up(max(mean if lean else mean + mean // 2, mean + (15 * _sd(mean) + 1) // 2) + 8, 64)
@@ -62,7 +62,7 @@ def msd2_stride_b(n, slots=65536, fine=False, lean=False):
 
 
 def msd2_seg_shift(n, bin_finish):
-    """adlhip.hip:1043 msd2_seg_shift: width w of the second digit (256 << w segments)"""
+    """adlhip.hip msd2_seg_shift: width w of the second digit (256 << w segments)"""
     max_n = (1 << 40) if bin_finish else (16 << 20)
     if n >= max_n:
         return 8
@@ -73,7 +73,7 @@ def msd2_seg_shift(n, bin_finish):
 
 
 def msd2_layout(n, elem_bytes, headroom_pct=FULL_PCT):
-    """adlhip.hip:1113 msd2_layout (cursor form): bucket slab stride_a, segment slabs stride_b, finish tile tier_b"""
+    """adlhip.hip msd2_layout (cursor form): bucket slab stride_a, segment slabs stride_b, finish tile tier_b"""
     w = msd2_seg_shift(n, elem_bytes == 8)
     fine = elem_bytes == 4 and w == 8
     return dict(stride_a=_align_up(n // 256 + (n // 256) * headroom_pct // 100 + 4096, 64), seg_shift=w,
@@ -81,9 +81,9 @@ def msd2_layout(n, elem_bytes, headroom_pct=FULL_PCT):
 
 
 def msd2s_layout(n, elem_bytes=8, slab16=False, lean=False):
-    """adlhip.hip:1267 msd2s_layout (stable and hybrid forms): 16 chains, each a slice of the input; one sub-slab of stride_a per
+    """adlhip.hip msd2s_layout (stable and hybrid forms): 16 chains, each a slice of the input; one sub-slab of stride_a per
     (bucket, chain); slab16 = whole u32 keys (65536 segments, 16-bit second slab)"""
-    tile = 8192 if elem_bytes == 8 else 16384   # msd2s_tile (adlhip.hip:1253)
+    tile = 8192 if elem_bytes == 8 else 16384   # msd2s_tile (adlhip.hip)
     pieces = 16
     slice_ = _align_up((n + pieces - 1) // pieces, tile)
     mean = slice_ // 256
@@ -93,12 +93,12 @@ def msd2s_layout(n, elem_bytes=8, slab16=False, lean=False):
 
 
 def mid_stride(n):
-    """adlhip.hip:839 mid_layout().stride: the mid-size sort's bucket slab (= its LDS tile; adlhip.hip:921 uses the same cap)"""
+    """adlhip.hip mid_layout().stride: the mid-size sort's bucket slab (= its LDS tile; adlhip.hip mid_sort uses the same cap)"""
     return 4096 if n <= (512 << 10) else 8192 if n <= MI else 16384
 
 
 def large_sort_form(kind, n, sort_bits, knob, rank=1, persist=1):
-    """adlhip.hip:1336 large_sort_form: 'cursor' / 'stable' / 'hybrid' / None for a sort of n elements of `kind` with the
+    """adlhip.hip large_sort_form: 'cursor' / 'stable' / 'hybrid' / None for a sort of n elements of `kind` with the
     "sort.msd2" knob (default device: 8-bit digits, automatic algorithm, at least 256 resident workgroups)"""
     if knob == 0 or sort_bits < 16:
         return None
@@ -128,9 +128,9 @@ def large_sort_form(kind, n, sort_bits, knob, rank=1, persist=1):
 
 
 def finish_names(kind, form, w, tier_b, whole=True):
-    """The finish's launches (adlhip.hip:1367 launch_large_finish, default knobs): the workgroup-per-segment finish for whole u32
+    """The finish's launches (adlhip.hip launch_large_finish, default knobs): the workgroup-per-segment finish for whole u32
     keys with 65536 segments and a tile of 3072 and more (or beyond 5120), the binning finish + its listed hand-over for whole
-    u64 keys (use_bin_finish, adlhip.hip:1457: n >= 24 Mi, or any n with a narrow second digit), else the wave LSD finish
+    u64 keys (adlhip.hip use_bin_finish: n >= 24 Mi, or any n with a narrow second digit), else the wave LSD finish
     (wave_finish16_kernel for the 16-bit second slab, 1280 / 1536 / 2560)."""
     if kind == U32:
         return {"segment_sort_wg_u32"} if (tier_b > 5120 or (whole and w == 8 and tier_b >= 3072)) else {"segment_sort_wave_u32"}
@@ -614,7 +614,7 @@ def test_stable_and_hybrid_slab_edges(dev, kind, n, bits, knob, rank, level, see
 # ---------------------------------------------------------------------------------------------
 def _mid_overflowed(d, form):
     """Whether the last forced mid-size sort on handle d overflowed a bucket: it reports into pinned memory, and the automatic
-    choice of the next eligible sort steers by that report (adlhip.hip:870 choose_mid_form) -- a two-launch overflow keeps the
+    choice of the next eligible sort steers by that report (adlhip.hip choose_mid_form) -- a two-launch overflow keeps the
     next u32 sort off the two-launch form, a three-launch overflow keeps the next {key, value} sort (which has no two-launch
     form) off the three-launch form."""
     d.setParam("sort.mid", 1)
@@ -637,7 +637,7 @@ def test_mid_size_bucket_slab_edges(n, form):
     """One top-byte bucket of exactly the slab (4096 / 8192 / 16384 keys), one less and one more; the others share the rest.
     Each sort runs on a fresh handle, whose next automatic sort shows whether it overflowed."""
     cap = mid_stride(n)
-    assert cap == max(4096, 2 * ((n + 255) // 256))   # the three-launch form's bound (adlhip.hip:921) is the same slab
+    assert cap == max(4096, 2 * ((n + 255) // 256))   # the three-launch form's bound (adlhip.hip mid_sort) is the same slab
     b = 201
     counts = even_counts(n, 256, {b: cap}, w=0)
     K = Keys(n, 32, 0, 32, counts, 40 + form, full=[b])
