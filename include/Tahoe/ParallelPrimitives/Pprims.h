@@ -192,6 +192,25 @@ public:
     template <typename T>
     void binCount(const adl::Device* device, const adl::Buffer<T>& keys, adl::Buffer<u32>& counts, int n, int numBins);
 
+    // merge of sorted sequences: the first na keys of keysA and the first nb keys of keysB, each sorted in the order of
+    // sortKeys(descending), merged stably into keysOut[0 .. na + nb) -- what sortKeys gives for the concatenation, with one read and one
+    // write per element.  Where keys are equal (same bits) those of keysA come first.  valuesA / valuesB / valuesOut (all or none; V
+    // independently of K) travel with their keys; indexOut, where given, receives every output element's position in A || B (i for
+    // A[i], na + i for B[i]).  K, V: int, float, long long, double, u32, u64.  The inputs are left intact and may be the same
+    // Buffer; no output may be an input.  Inputs that are not sorted give an output in unspecified order.  Enqueues and returns.  A
+    // TYPE_HOST device runs a plain two-pointer loop
+    template <typename K, typename V>
+    void mergePairs(const adl::Device* device, const adl::Buffer<K>& keysA, const adl::Buffer<V>* valuesA, const adl::Buffer<K>& keysB,
+                    const adl::Buffer<V>* valuesB, adl::Buffer<K>& keysOut, adl::Buffer<V>* valuesOut, adl::Buffer<u32>* indexOut, int na, int nb,
+                    bool descending = false);
+    template <typename K>
+    void mergeKeys(const adl::Device* device, const adl::Buffer<K>& keysA, const adl::Buffer<K>& keysB, adl::Buffer<K>& keysOut,
+                   adl::Buffer<u32>* indexOut, int na, int nb, bool descending = false)
+    {
+        mergePairs<K, u32>(device, keysA, (const adl::Buffer<u32>*)0, keysB, (const adl::Buffer<u32>*)0, keysOut, (adl::Buffer<u32>*)0, indexOut, na,
+                           nb, descending);
+    }
+
 private:
     template <typename T> int uniqueTyped(const adl::Device* device, const adl::Buffer<T>& keys, adl::Buffer<T>& uniqueOut, adl::Buffer<u32>& countsOut,
                                           int n, bool descending);

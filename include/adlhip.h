@@ -583,6 +583,54 @@ int adlhip_histogram_range_typed(adlhip_device* dev, int key_type, const void* d
 int adlhip_bincount_typed(adlhip_device* dev, int key_type, const void* d_keys_in, size_t n, size_t num_bins, uint32_t* d_counts_out,
                           void* d_work, size_t work_bytes);
 
+/* ---- merge of sorted sequences (no reference counterpart) ---- */
+
+/* The stable merge of two sequences that are already sorted: thrust's merge / merge_by_key, cub's DeviceMerge, and what
+ * torch.sort(torch.cat((a, b)), stable=True) gives for sorted a and b -- with one read of every input element and one write of every
+ * output element instead of a sort of the concatenation.
+ *
+ * Order.  A (d_keys_a, na keys) and B (d_keys_b, nb keys) are each sorted in `order` in the order of the typed sorts: integers by value,
+ *   floats by IEEE totalOrder (-NaN < -inf < ... < -0 < +0 < ... < +inf < +NaN), descending the reverse.  Precisely: a sequence is
+ *   sorted when the codes adlhip_key_encode(key_type, order) gives for its elements are non-decreasing as unsigned numbers.
+ * Result.  The stable merge of the na + nb elements: the elements of one input keep their order, and where codes are equal every
+ *   element of A comes before every element of B, in both orders.  This is, bit for bit, what the stable typed sort
+ *   (adlhip_sort_pairs_typed, adlhip_argsort_typed) gives for the concatenation A || B.
+ *     d_keys_out[j]   the j-th key, bit for bit (NaN payloads, -0)
+ *     d_vals_out[j]   its value (value_bytes 4 or 8: d_vals_a, d_vals_b and d_vals_out are all given; value_bytes 0: all NULL)
+ *     d_index_out[j]  its position in A || B: i for A[i], na + i for B[i]
+ *   At least one output is given; each holds na + nb elements and every one of them is written.
+ *
+ * Contract.  na + nb < 2^32; either count may be 0 (the array of an empty input is not looked at).  The inputs are never written; A
+ * and B may overlap or be the same array.  No output may overlap an input, another output or d_work.  The outputs and d_work are
+ * 16-byte aligned.  The INPUTS need only the alignment of their element (4 or 8 bytes; values: value_bytes): a tile's share of A
+ * and of B starts at an arbitrary element anyway, so a view that starts at any element of a larger array is merged where it lies.
+ * na + nb == 0 succeeds and enqueues nothing.  A NULL required pointer, a misaligned pointer, an overlap, an unknown key_type, order
+ * or value_bytes, value arrays that do not agree with value_bytes, no output at all, na + nb >= 2^32 and a work buffer one byte
+ * short (the message names the needed size and adlhip_merge_scratch_bytes) fail before anything is enqueued, each with a message
+ * that names the argument.  The call enqueues and returns: nothing data-dependent reaches the host (launch grids depend on na + nb
+ * alone), nothing is remembered between calls, all state lives in d_work -- whose contents on entry are arbitrary -- and the handle
+ * owns no device word of it.  No kernel waits on another workgroup or uses an atomic to global memory.
+ *
+ * Inputs that are NOT sorted: the order of the output is unspecified (elements may even repeat or be missing), but the call
+ * succeeds and terminates, every read stays inside [A, A + na) and [B, B + nb), and every write inside the na + nb elements of the
+ * outputs (merge_kernels.hpp proves it: every search result lies in its search range whatever the comparisons answer, and a tile's
+ * share of A is clamped to the tile).
+ *
+ * Work bytes:
+ *   adlhip_merge_scratch_bytes = 4 x (tiles + 1) rounded up to 256, tiles = ceil((na + nb) / ADLHIP_MERGE_TILE): the number of
+ *   elements of A in front of every tile boundary.  key_type and value_bytes are checked and do not change the value.
+ *
+ * Two launches over tiles of ADLHIP_MERGE_TILE output elements: one thread per tile boundary searches its diagonal of the merge
+ * path; then the workgroups take tiles in turns -- the tile's share of A and B goes to LDS as codes, every thread finds the
+ * diagonal of its 8 outputs there and merges them, the tile is put in output order in LDS and stored densely. */
+#define ADLHIP_MERGE_TILE 2048
+int adlhip_merge_scratch_bytes(adlhip_device* dev, int key_type, int value_bytes, size_t na, size_t nb, size_t* work_bytes);
+int adlhip_merge_typed(adlhip_device* dev, int key_type, int order,
+                       const void* d_keys_a, const void* d_vals_a_or_null, size_t na,
+                       const void* d_keys_b, const void* d_vals_b_or_null, size_t nb,
+                       int value_bytes, void* d_keys_out_or_null, void* d_vals_out_or_null, uint32_t* d_index_out_or_null,
+                       void* d_work, size_t work_bytes);
+
 /* ---- segments finished in LDS (no reference counterpart) ------------------------------------- */
 
 /* Sorts, stably and in place, every segment [d_seg_start[s], d_seg_start[s + 1]) of an array of u32 keys
@@ -757,6 +805,8 @@ int adlhip_generate_keys(adlhip_device* dev, int elem_kind, void* dptr, size_t n
  *   "debug.histogram_grid" workgroups the count kernel of adlhip_histogram_range_typed / adlhip_bincount_typed is launched with at
  *                      most (0 [default]: the G of the histogram block; larger values change nothing); tests set it to make few
  *                      workgroups take many tiles
+ *   "debug.merge_grid" workgroups the tile kernel of adlhip_merge_typed is launched with at most (0 [default]: 8 per CU; larger values
+ *                      change nothing); tests set it to make few workgroups take many tiles in turns.  The result does not depend on it
  *   "debug.histogram_lds_bins" the largest num_bins for which adlhip_bincount_typed takes the LDS path (1 .. 8192, default 8192; 0
  *                      sets the default); tests lower it to reach the sorted path with few keys.  adlhip_get_param reports the limit
  *   "debug.persist_grid" workgroups both persistent passes of the large keys-only sort (cursor form) are launched with, rounded up to

@@ -215,6 +215,7 @@ const Knob kKnobs[] = {
     {"debug.scan_grid", &adlhip_device::scan_grid, 0, kNoMax, "debug.scan_grid must be >= 0", nullptr},
     {"debug.compact_grid", &adlhip_device::compact_grid, 0, kNoMax, "debug.compact_grid must be >= 0", nullptr},
     {"debug.histogram_grid", &adlhip_device::histogram_grid, 0, kNoMax, "debug.histogram_grid must be >= 0", nullptr},
+    {"debug.merge_grid", &adlhip_device::merge_grid, 0, kNoMax, "debug.merge_grid must be >= 0", nullptr},
     {"debug.persist_grid", &adlhip_device::persist_grid, 0, 4096, "debug.persist_grid must be in [0, 4096]", nullptr},
     // ---- with a rule of their own
     {"sort.digit_bits", &adlhip_device::digit_bits, 0, 0, nullptr,

@@ -1,5 +1,5 @@
 // primitives.hip -- the host side of what is built on top of the sorts: typed keys and argsort, top-k, row-wise top-k, unique /
-// run-length encode, reduce by key, typed scans, stream compaction, histograms.  No reference counterpart.  It reaches the sorts through adlhip_internal.hpp alone (sort_elements,
+// run-length encode, reduce by key, typed scans, stream compaction, histograms, merges.  No reference counterpart.  It reaches the sorts through adlhip_internal.hpp alone (sort_elements,
 // sort_work_bytes, soa_wide_layout) and never sees their kernels.
 #include "adlhip_internal.hpp"
 
@@ -21,9 +21,10 @@
 #include "scan_kernels.hpp"
 #include "compact_kernels.hpp"
 #include "histogram_kernels.hpp"
+#include "merge_kernels.hpp"
 
 // instantiated in kernels_select.hip / kernels_toprows.hip / kernels_unique.hip / kernels_reduce.hip / kernels_scan.hip /
-// kernels_compact.hip / kernels_histogram.hip; here they are only declared
+// kernels_compact.hip / kernels_histogram.hip / kernels_merge.hip; here they are only declared
 #ifndef ADLHIP_SINGLE_TU
 #define X(...) extern template __global__ __VA_ARGS__;
 #include "select_kernels.inc"
@@ -33,6 +34,7 @@
 #include "scan_kernels.inc"
 #include "compact_kernels.inc"
 #include "histogram_kernels.inc"
+#include "merge_kernels.inc"
 #undef X
 #endif
 
@@ -903,6 +905,87 @@ int hist_check_mode(const char* what, int key_type, size_t num_bins, bool by_edg
     return ADLHIP_SUCCESS;
 }
 
+// ---- merge of sorted sequences (merge_kernels.hpp) -------------------------------------------------------------
+static_assert(ADLHIP_MERGE_TILE == adlhip::kRedTile, "the header states the tile of the merge");
+// grid of the tile kernel per CU at most ("debug.merge_grid" lowers it): its LDS (12 or 20 KiB) admits that many workgroups, and the
+// searches and the serial merge are chains of dependent LDS reads that only other waves hide
+constexpr int kMergeWgsPerCu = 8;
+constexpr size_t kMergeMaxElems = 0xFFFFFFFFull;   // na + nb: positions in A || B fit a dword
+
+// na + nb, refused when it does not fit
+int merge_total(const char* what, size_t na, size_t nb, size_t* n)
+{
+    if (na > kMergeMaxElems || nb > kMergeMaxElems - na)
+        return fail("%s: na + nb = %zu + %zu exceeds the supported maximum %zu", what, na, nb, (size_t)kMergeMaxElems);
+    *n = na + nb;
+    return ADLHIP_SUCCESS;
+}
+// Work of the merge: [split: one u32 per tile boundary], rounded up to 256 bytes
+size_t merge_work_bytes(size_t n)
+{
+    const size_t tiles = (n + adlhip::kRedTile - 1) / adlhip::kRedTile;
+    return align_up(4 * (tiles + 1), 256);
+}
+int merge_check_value_bytes(const char* what, int value_bytes)
+{
+    if (value_bytes != 0 && value_bytes != 4 && value_bytes != 8) return fail("%s: value_bytes must be 0, 4 or 8, got %d", what, value_bytes);
+    return ADLHIP_SUCCESS;
+}
+
+// check_buffers for the merge: every message names the argument; an input needs `align` bytes of alignment only (its element's: a
+// tile's share of it starts at an arbitrary element anyway), the inputs may overlap one another, and no output may overlap an input,
+// another output or the work buffer
+struct MergeBuf {
+    const void* p;
+    size_t bytes;
+    const char* name;
+    bool required;
+    size_t align;
+};
+int merge_check_buffers(const char* what, std::initializer_list<MergeBuf> ins, std::initializer_list<MergeBuf> outs)
+{
+    for (const auto& list : {ins, outs})
+        for (const MergeBuf& b : list) {
+            if (b.required && !b.p) return fail("%s: %s is required", what, b.name);
+            if (reinterpret_cast<uintptr_t>(b.p) & (b.align - 1)) return fail("%s: %s must be %zu-byte aligned", what, b.name, b.align);
+        }
+    for (auto o = outs.begin(); o != outs.end(); ++o) {
+        for (const MergeBuf& in : ins)
+            if (in.p && overlaps(o->p, o->bytes, in.p, in.bytes)) return fail("%s: %s must not overlap %s", what, o->name, in.name);
+        for (auto q = o + 1; q != outs.end(); ++q)
+            if (q->p && overlaps(o->p, o->bytes, q->p, q->bytes)) return fail("%s: %s must not overlap %s", what, o->name, q->name);
+    }
+    return ADLHIP_SUCCESS;
+}
+
+// the merge of n = na + nb > 0 elements; V: the values' unsigned type, vals_out null = none
+template <typename K, typename V>
+int merge_stage(adlhip_device* d, adlhip::RedCodec codec, const K* a, const V* va, size_t na, const K* b, const V* vb, size_t nb, K* keys_out,
+                V* vals_out, uint32_t* index_out, void* work)
+{
+    uint32_t* split = static_cast<uint32_t*>(work);
+    const size_t n = na + nb;
+    const uint32_t tiles = (uint32_t)((n + adlhip::kRedTile - 1) / adlhip::kRedTile);   // (at most 2^21)
+    const uint32_t pwgs = (tiles + 1 + (uint32_t)adlhip::kSelNT - 1) / (uint32_t)adlhip::kSelNT;
+    size_t cap = (size_t)d->prop.multiProcessorCount * kMergeWgsPerCu;
+    if (d->merge_grid > 0) cap = std::min(cap, (size_t)d->merge_grid);
+    const uint32_t wgs = (uint32_t)std::min((size_t)tiles, cap);
+    const uint32_t ua = (uint32_t)na, ub = (uint32_t)nb;
+    int rc = launch(d, "merge_partition", [&] {
+        hipLaunchKernelGGL((adlhip::merge_partition_kernel<K>), dim3(pwgs), dim3(adlhip::kSelNT), 0, d->stream, a, ua, b, ub, codec, tiles, split);
+    });
+    if (rc) return rc;
+    return launch(d, "merge_tiles", [&] {
+        if (vals_out)
+            hipLaunchKernelGGL((adlhip::merge_tiles_kernel<K, V>), dim3(wgs), dim3(adlhip::kSelNT), 0, d->stream, a, va, ua, b, vb, ub, codec,
+                               (const uint32_t*)split, tiles, keys_out, vals_out, index_out);
+        else
+            hipLaunchKernelGGL((adlhip::merge_tiles_kernel<K, adlhip::MergeNone>), dim3(wgs), dim3(adlhip::kSelNT), 0, d->stream, a,
+                               (const adlhip::MergeNone*)nullptr, ua, b, (const adlhip::MergeNone*)nullptr, ub, codec, (const uint32_t*)split,
+                               tiles, keys_out, (adlhip::MergeNone*)nullptr, index_out);
+    });
+}
+
 }  // namespace
 
 extern "C" {
@@ -1318,6 +1401,45 @@ int adlhip_bincount_typed(adlhip_device* d, int key_type, const void* keys_in, s
         return ADLHIP_BY_WIDTH(t.bytes, U, hist_lds_stage<U, adlhip::kHistBincount>(d, (const U*)keys_in, n, (const U*)nullptr, t.kind, num_bins, 0,
                                                                                    counts_out, work));
     return ADLHIP_BY_WIDTH(t.bytes, U, hist_sorted_stage<U>(d, (const U*)keys_in, n, num_bins, counts_out, work));
+}
+
+// ---- merge of sorted sequences -------------------------------------------------------------------------
+int adlhip_merge_scratch_bytes(adlhip_device* d, int key_type, int value_bytes, size_t na, size_t nb, size_t* work_bytes)
+{
+    const char* what = "merge scratch";
+    if (!d) return fail("null device handle");
+    TypeInfo t;
+    size_t n;
+    if (type_info("key_type", key_type, &t) || merge_check_value_bytes(what, value_bytes) || merge_total(what, na, nb, &n)) return ADLHIP_FAILURE;
+    if (work_bytes) *work_bytes = merge_work_bytes(n);
+    return ADLHIP_SUCCESS;
+}
+
+int adlhip_merge_typed(adlhip_device* d, int key_type, int order, const void* keys_a, const void* vals_a, size_t na, const void* keys_b,
+                       const void* vals_b, size_t nb, int value_bytes, void* keys_out, void* vals_out, uint32_t* index_out, void* work,
+                       size_t work_bytes)
+{
+    const char* what = "merge";
+    TypeInfo t;
+    size_t n;
+    if (bind(d) || key_type_info(key_type, order, &t) || merge_check_value_bytes(what, value_bytes) || merge_total(what, na, nb, &n))
+        return ADLHIP_FAILURE;
+    if (value_bytes == 0 && (vals_a || vals_b || vals_out))
+        return fail("%s: value_bytes is 0, so d_vals_a, d_vals_b and d_vals_out must be NULL", what);
+    if (!keys_out && !vals_out && !index_out) return fail("%s: at least one of d_keys_out, d_vals_out and d_index_out must be given", what);
+    if (n == 0) return ADLHIP_SUCCESS;
+    const size_t kb = (size_t)t.bytes, vb = (size_t)value_bytes, va = vb ? vb : 1;
+    if (merge_check_buffers(what,
+                            {{keys_a, na * kb, "d_keys_a", na != 0, kb}, {keys_b, nb * kb, "d_keys_b", nb != 0, kb},
+                             {vals_a, na * vb, "d_vals_a", vb && na, va}, {vals_b, nb * vb, "d_vals_b", vb && nb, va}},
+                            {{keys_out, n * kb, "d_keys_out", false, 16}, {vals_out, n * vb, "d_vals_out", vb != 0, 16},
+                             {index_out, n * 4, "d_index_out", false, 16}, {work, work_bytes, "d_work", true, 16}}))
+        return ADLHIP_FAILURE;
+    const size_t need = merge_work_bytes(n);
+    if (work_bytes < need) return fail("work buffer too small: %zu < %zu (adlhip_merge_scratch_bytes)", work_bytes, need);
+    const adlhip::RedCodec codec = {(uint32_t)t.kind, (uint32_t)order};
+    return ADLHIP_BY_WIDTH(t.bytes, K, ADLHIP_BY_WIDTH(value_bytes ? value_bytes : 4, V, merge_stage<K, V>(d, codec, (const K*)keys_a,
+                           (const V*)vals_a, na, (const K*)keys_b, (const V*)vals_b, nb, (K*)keys_out, (V*)vals_out, index_out, work)));
 }
 
 }  // extern "C"

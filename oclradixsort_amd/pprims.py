@@ -20,6 +20,7 @@
     p.compactIf(device, keys, n, "lt", x, values=buf)      # -> CompactResult: the keys (and their values) that compare so with x
     p.histogramRange(device, keys, n, edges, num_bins)     # -> Buffer(uint32): the keys per bin [edges[b], edges[b + 1])
     p.binCount(device, keys, n, num_bins)                  # -> Buffer(uint32): the keys per value 0 .. num_bins - 1
+    p.mergeKeys(device, a, b, out, na, nb)                 # the stable merge of two sorted key Buffers (mergePairs: with values)
 
 Like the reference object it owns lazily grown device scratch (m_u32WorkBuffer[0] = ping-pong data
 buffer, m_u32WorkBuffer[1] = histogram table; Pprims.h:44-45, Pprims.cpp:226-232, :332-337) and must be
@@ -686,6 +687,71 @@ class Pprims:
         def call(lib, kt, n_, bins, counts):
             return lib.adlhip_bincount_typed(device._h, kt, keys.ptr(), n_, bins, counts, self.m_work.ptr(), self.m_work.getSize())
         return self._histogram("binCount", device, keys, n, num_bins, False, True, countsOut, call)
+
+    # -- merge of sorted sequences (no reference counterpart; include/adlhip.h adlhip_merge_typed)
+    def _merge(self, what, device, a, va, b, vb, out, vout, na, nb, descending, indexOut):
+        if device is None:
+            raise AdlHipError("%s needs a device" % what)
+        if a is None or b is None:
+            raise AdlHipError("%s: both inputs are required (an empty one with its count 0)" % what)
+        kt = self._key_type(a, what)
+        if np.dtype(b.dtype) != np.dtype(a.dtype):
+            raise AdlHipError("%s: a is %s, b %s" % (what, a.dtype, b.dtype))
+        na, nb = int(na), int(nb)
+        for name, buf, n in (("na", a, na), ("nb", b, nb)):
+            if n < 0 or buf.getSize() < n:
+                raise AdlHipError("%s: %s = %d outside [0, %d]" % (what, name, n, buf.getSize()))
+        n = na + nb
+        if n >= 1 << 32:
+            raise AdlHipError("%s: na + nb = %d; fewer than 2^32 elements" % (what, n))
+        if out is not None and (not hasattr(out, "getSize") or np.dtype(out.dtype) != np.dtype(a.dtype) or out.getSize() < n):
+            raise AdlHipError("%s: out must hold na + nb elements of %s" % (what, a.dtype))
+        vbytes = 0
+        if va is not None or vb is not None or vout is not None:
+            if va is None or vb is None or vout is None:
+                raise AdlHipError("%s: the values of a, of b and valuesOut go together" % what)
+            vbytes = np.dtype(va.dtype).itemsize
+            if vbytes not in (4, 8):
+                raise AdlHipError("%s: unsupported values type %s (4 or 8 bytes)" % (what, va.dtype))
+            if np.dtype(vb.dtype) != np.dtype(va.dtype) or np.dtype(vout.dtype) != np.dtype(va.dtype):
+                raise AdlHipError("%s: the values are %s, %s and %s" % (what, va.dtype, vb.dtype, vout.dtype))
+            if va.getSize() < na or vb.getSize() < nb or vout.getSize() < n:
+                raise AdlHipError("%s: the values must hold na, nb and na + nb elements" % what)
+        if out is None and vout is None and (indexOut is None or indexOut is False):
+            raise AdlHipError("%s: nothing asked (out, valuesOut or indexOut)" % what)
+        (idx,), own = self._runs_outputs(what, device, n, [("indexOut", indexOut, n)])
+        try:
+            lib = _lib.load()
+            wb = ctypes.c_size_t()
+            check(lib.adlhip_merge_scratch_bytes(device._h, kt, vbytes, na, nb, ctypes.byref(wb)), "adlhip_merge_scratch_bytes")
+            self._scratch(device, 0, wb.value)
+
+            def p(buf):
+                return buf.ptr() if buf is not None else None
+            check(lib.adlhip_merge_typed(device._h, kt, 1 if descending else 0, p(a), p(va), na, p(b), p(vb), nb, vbytes, p(out), p(vout),
+                                         p(idx), self.m_work.ptr(), self.m_work.getSize()), what)
+        except AdlHipError:
+            for buf in own:
+                buf.release()
+            raise
+        return idx
+
+    def mergeKeys(self, device, a, b, out, na, nb, descending=False, indexOut=None):
+        """The stable merge of the first na keys of `a` and the first nb keys of `b` -- Buffers of one key type (uint32, int32, float32,
+        uint64, int64, float64), each sorted in the order of sortKeys(descending) -- into out[0 .. na + nb): what sortKeys gives for the
+        concatenation, with one read and one write per element.  Where keys compare equal (same code: same bits) those of `a` come
+        first.  indexOut: True for a new uint32 Buffer, or one to fill: the position in a || b (i for a[i], na + i for b[i]) of every
+        output element; it is returned (None when not asked).  out may be None when only the positions are wanted.  The caller sizes
+        the Buffers; the inputs are left intact and may be the same Buffer; out may be neither.  Inputs that are not sorted give an
+        output in unspecified order, never an access outside the Buffers.  Enqueues and returns."""
+        return self._merge("mergeKeys", device, a, None, b, None, out, None, na, nb, descending, indexOut)
+
+    def mergePairs(self, device, keysA, valuesA, keysB, valuesB, keysOut, valuesOut, na, nb, descending=False, indexOut=None):
+        """mergeKeys with a value per key (any element type of 4 or 8 bytes, one type for valuesA, valuesB and valuesOut, whatever the
+        keys' width): valuesOut[j] is the value of the key keysOut[j].  keysOut may be None (values and / or positions only)."""
+        if valuesA is None or valuesB is None or valuesOut is None:
+            raise AdlHipError("mergePairs: valuesA, valuesB and valuesOut are required (mergeKeys merges keys alone)")
+        return self._merge("mergePairs", device, keysA, valuesA, keysB, valuesB, keysOut, valuesOut, na, nb, descending, indexOut)
 
     def copy(self, device, dst, src, n):
         """Pprims::copy (Pprims.cpp:31-67, commented out in the reference): first n elements of src -> dst."""

@@ -16,6 +16,7 @@ back-end on torch's own stream.
     sel = s.select_if(t, "lt", x)                                                # t[t < x], in totalOrder; also "le", "gt", "ge", "eq", "ne"
     out, count = s.partition(t, mask)                                            # the selected elements, then the others; both in input order
     c = s.bincount(t); c = s.histogram(t, edges); c = s.histc(t, 100, 0.0, 1.0)  # torch.bincount / numpy.histogram(t, edges)[0] / the same on linspace edges
+    m = s.merge(a, b); m, v, i = s.merge(a, b, values=(va, vb), return_indices=True)   # torch.sort(torch.cat((a, b)), stable=True) of sorted a, b
     s.close()
 
 Always out of place and always stable.  The ONE difference from `torch.sort(t, stable=True)`: floats are ordered by
@@ -505,6 +506,68 @@ class TorchSorter:
             lo, hi = lo - 1.0, hi + 1.0
         edges = torch.linspace(lo, hi, bins + 1, dtype=torch.float64).to(t.dtype).to(t.device)   # (on the CPU: the same edges everywhere)
         return self.histogram(k, edges)
+
+    def _merge_input(self, t, what):
+        """the checks of _flat_input for a 1-D input of merge(); contiguous, but at ANY element offset: the merge takes its inputs
+        at their element's alignment, so a view such as t[1:] goes through without a copy (a strided one is copied)"""
+        if not isinstance(t, torch.Tensor):
+            raise TypeError("TorchSorter: expected a torch.Tensor, got %s" % type(t).__name__)
+        if t.dtype not in _NP_DTYPE:
+            raise TypeError("TorchSorter: dtype %s unsupported (int32, int64, float32, float64)" % t.dtype)
+        if t.dim() != 1:
+            raise ValueError("TorchSorter.%s: 1-D tensors only, got %d dimensions" % (what, t.dim()))
+        if t.device != self.torch_device:
+            raise ValueError("TorchSorter: tensor is on %s, the sorter on %s" % (t.device, self.torch_device))
+        return t.contiguous()
+
+    def merge(self, a, b, descending=False, values=None, return_indices=False):
+        """What torch.sort(torch.cat((a, b)), descending=descending, stable=True) returns for 1-D tensors a and b of one dtype that
+        are each sorted that way already -- by one merge instead of a sort: the merged values, then -- where given -- the merged
+        `values` (a pair of 1-D tensors of a's and b's lengths and one dtype, int32 / int64 / float32 / float64 whatever the keys'),
+        then -- where asked -- the int64 indices into the concatenation; one tensor or a tuple.  Equal elements keep the order of the
+        concatenation: a's before b's.  The order is that of sort(): floats by totalOrder, so inputs must be sorted with -0 before
+        +0 and NaNs by sign at the two ends; without NaN and -0 that is torch's order.  Inputs that are not sorted give an output
+        in unspecified order.  Contiguous views at any element offset are read where they lie, without a copy.  Nothing reaches
+        the host."""
+        ka, kb = self._merge_input(a, "merge"), self._merge_input(b, "merge")
+        if ka.dtype != kb.dtype:
+            raise TypeError("TorchSorter.merge: a is %s, b %s" % (ka.dtype, kb.dtype))
+        va = vb = None
+        if values is not None:
+            if not isinstance(values, (tuple, list)) or len(values) != 2:
+                raise ValueError("TorchSorter.merge: values is a pair (values of a, values of b)")
+            va, vb = self._merge_input(values[0], "merge"), self._merge_input(values[1], "merge")
+            if va.dtype != vb.dtype:
+                raise TypeError("TorchSorter.merge: the values are %s and %s" % (va.dtype, vb.dtype))
+            if va.numel() != ka.numel() or vb.numel() != kb.numel():
+                raise ValueError("TorchSorter.merge: %d and %d elements but %d and %d values" % (ka.numel(), kb.numel(), va.numel(), vb.numel()))
+        if torch.cuda.current_stream(self.torch_device).cuda_stream != self.raw_stream:
+            raise RuntimeError("TorchSorter: bound to the stream that was current at construction; another stream is current now")
+        na, nb = ka.numel(), kb.numel()
+        n = na + nb
+        if n >= 1 << 32:
+            raise ValueError("TorchSorter: fewer than 2^32 elements")
+        dev = ka.device
+        kout = torch.empty(n, dtype=ka.dtype, device=dev)
+        vout = torch.empty(n, dtype=va.dtype, device=dev) if va is not None else None
+        idx32 = torch.empty(n, dtype=torch.int32, device=dev) if return_indices else None   # uint32 positions in an int32 tensor
+        if n:
+            kdt = _NP_DTYPE[ka.dtype]
+            if va is not None:
+                vdt = _NP_DTYPE[va.dtype]
+                self.pprims.mergePairs(self.device, self._wrap(ka, kdt), self._wrap(va, vdt), self._wrap(kb, kdt), self._wrap(vb, vdt),
+                                       self._wrap(kout, kdt), self._wrap(vout, vdt), na, nb, descending=bool(descending),
+                                       indexOut=self._wrap(idx32, np.uint32) if return_indices else None)
+            else:
+                self.pprims.mergeKeys(self.device, self._wrap(ka, kdt), self._wrap(kb, kdt), self._wrap(kout, kdt), na, nb,
+                                      descending=bool(descending), indexOut=self._wrap(idx32, np.uint32) if return_indices else None)
+            self.device.checkFault()
+        out = (kout,)
+        if va is not None:
+            out += (vout,)
+        if return_indices:
+            out += (idx32.to(torch.int64) & 0xffffffff,)
+        return out if len(out) > 1 else out[0]
 
     def sort(self, t, descending=False):
         """(values, indices) like torch.sort(t, descending=descending, stable=True); indices are int64."""

@@ -7,7 +7,8 @@
 // waits for the count), or a loop over the runs of the host argsort.  Pprims::scanTyped / scanByKey: adlhip_scan_typed /
 // adlhip_scan_by_key, or a plain loop, left to right.  Pprims::compactFlagged / compactIf: adlhip_compact_flagged /
 // adlhip_compact_if_typed (they wait for the count), or a plain loop.  Pprims::histogramRange / binCount:
-// adlhip_histogram_range_typed / adlhip_bincount_typed, or a plain loop.
+// adlhip_histogram_range_typed / adlhip_bincount_typed, or a plain loop.  Pprims::mergeKeys / mergePairs: adlhip_merge_typed, or a
+// plain two-pointer loop in which a tie takes the first input.
 #include <Tahoe/ParallelPrimitives/Pprims.h>
 
 #include <algorithm>
@@ -746,6 +747,78 @@ TAHOE_BINCOUNT(u32)
 TAHOE_BINCOUNT(u64)
 #undef TAHOE_BINCOUNT
 #undef TAHOE_HISTOGRAM
+
+// ---- merge of sorted sequences: adlhip_merge_typed, or a plain two-pointer loop ----
+template <typename K, typename V>
+void Pprims::mergePairs(const adl::Device* device, const adl::Buffer<K>& keysA, const adl::Buffer<V>* valuesA, const adl::Buffer<K>& keysB,
+                        const adl::Buffer<V>* valuesB, adl::Buffer<K>& keysOut, adl::Buffer<V>* valuesOut, adl::Buffer<u32>* indexOut, int na,
+                        int nb, bool descending)
+{
+    ADLASSERT(na >= 0 && nb >= 0);
+    ADLASSERT((valuesA != 0) == (valuesOut != 0) && (valuesB != 0) == (valuesOut != 0));
+    ADLASSERT((long long)na + nb <= 0x7fffffffLL);   // (the facade counts in int)
+    if (na < 0 || nb < 0 || (long long)na + nb > 0x7fffffffLL || na + nb == 0) return;
+    const int n = na + nb;
+    ADLASSERT(device != 0);
+    ADLASSERT((adl::u64)na <= keysA.getSize() && (adl::u64)nb <= keysB.getSize() && (adl::u64)n <= keysOut.getSize() &&
+              (!valuesA || (adl::u64)na <= valuesA->getSize()) && (!valuesB || (adl::u64)nb <= valuesB->getSize()) &&
+              (!valuesOut || (adl::u64)n <= valuesOut->getSize()) && (!indexOut || (adl::u64)n <= indexOut->getSize()));
+    if (!onDevice(device)) {
+        ADLASSERT(device->getType() == adl::TYPE_HOST);   // a HIP device never falls back to the CPU
+        if (device->getType() != adl::TYPE_HOST) return;
+        K* a = na ? keysA.getHostPtr(na) : 0;
+        K* b = nb ? keysB.getHostPtr(nb) : 0;
+        V* va = valuesA && na ? valuesA->getHostPtr(na) : 0;
+        V* vb = valuesB && nb ? valuesB->getHostPtr(nb) : 0;
+        K* out = keysOut.getHostPtr(n);
+        V* vout = valuesOut ? valuesOut->getHostPtr(n) : 0;
+        u32* idx = indexOut ? indexOut->getHostPtr(n) : 0;
+        adl::DeviceUtils::waitForCompletion(device);
+        int i = 0, j = 0;
+        for (int o = 0; o < n; ++o) {   // b goes first only where it is strictly in front: a tie takes a
+            const bool takeB = i >= na || (j < nb && ordinal(b[j], descending) < ordinal(a[i], descending));
+            out[o] = takeB ? b[j] : a[i];
+            if (vout) vout[o] = takeB ? vb[j] : va[i];
+            if (idx) idx[o] = takeB ? (u32)(na + j) : (u32)i;
+            if (takeB) ++j;
+            else ++i;
+        }
+        if (a) keysA.returnHostPtr(a);
+        if (b) keysB.returnHostPtr(b);
+        if (va) valuesA->returnHostPtr(va);
+        if (vb) valuesB->returnHostPtr(vb);
+        keysOut.returnHostPtr(out);
+        if (vout) valuesOut->returnHostPtr(vout);
+        if (idx) indexOut->returnHostPtr(idx);
+        adl::DeviceUtils::waitForCompletion(device);
+        return;
+    }
+    const int vbytes = valuesOut ? (int)sizeof(V) : 0;
+    size_t wb = 0;
+    const int rcq = adlhip_merge_scratch_bytes(device->hip(), KeyTraits<K>::TYPE, vbytes, (size_t)na, (size_t)nb, &wb);
+    ADLASSERT(rcq == ADLHIP_SUCCESS);
+    reserve(device, 0, wb);
+    const int rc = adlhip_merge_typed(device->hip(), KeyTraits<K>::TYPE, descending ? ADLHIP_ORDER_DESCENDING : ADLHIP_ORDER_ASCENDING,
+                                      keysA.m_ptr, valuesA ? valuesA->m_ptr : 0, (size_t)na, keysB.m_ptr, valuesB ? valuesB->m_ptr : 0,
+                                      (size_t)nb, vbytes, keysOut.m_ptr, valuesOut ? valuesOut->m_ptr : 0,
+                                      indexOut ? (uint32_t*)indexOut->m_ptr : 0, m_work->m_ptr, (size_t)m_work->getSize());
+    if (rc != ADLHIP_SUCCESS) TH_LOG_ERROR("Pprims::merge: %s\n", adlhip_last_error());
+    ADLASSERT(rc == ADLHIP_SUCCESS);
+}
+
+#define TAHOE_MERGE(K, V)                                                                                                           \
+    template void Pprims::mergePairs<K, V>(const adl::Device*, const adl::Buffer<K>&, const adl::Buffer<V>*, const adl::Buffer<K>&, \
+                                           const adl::Buffer<V>*, adl::Buffer<K>&, adl::Buffer<V>*, adl::Buffer<u32>*, int, int, bool);
+#define TAHOE_MERGE_KEY(K) \
+    TAHOE_MERGE(K, int) TAHOE_MERGE(K, float) TAHOE_MERGE(K, long long) TAHOE_MERGE(K, double) TAHOE_MERGE(K, u32) TAHOE_MERGE(K, u64)
+TAHOE_MERGE_KEY(int)
+TAHOE_MERGE_KEY(float)
+TAHOE_MERGE_KEY(long long)
+TAHOE_MERGE_KEY(double)
+TAHOE_MERGE_KEY(u32)
+TAHOE_MERGE_KEY(u64)
+#undef TAHOE_MERGE_KEY
+#undef TAHOE_MERGE
 
 #define TAHOE_TYPED(T)                                                                                                              \
     void Pprims::sortKeys(const adl::Device* device, const adl::Buffer<T>& inout, int n, bool descending)                         \

@@ -6,8 +6,9 @@ is followed -- while later sorts are already queued -- by the LDS-order self-tes
 behaviour "sort.rank" = 1 rests on, adlhip_selftest_lds_order), and one size class reaches past 64 Mi keys (the
 pointer-store write-out).  Half of the sorts take the automatic choice (mid-size sort, large sort with its look-back /
 cursor passes and the safety net inside its offsets kernel), with "sort.msd2" forced on for some and keys shifted down by a random number of bits.
-One kind in seven is a stream compaction between the sorts (a stable partition of the keys by a comparison, values and positions along),
-one a histogram (range or bincount, random key type, bins and grid knob, the LDS and the sorted path).
+One kind in eight is a stream compaction between the sorts (a stable partition of the keys by a comparison, values and positions along),
+one a histogram (range or bincount, random key type, bins and grid knob, the LDS and the sorted path), one a merge (the keys cut in
+two, each part sorted by the library as int32 or float32 keys in either order, then merged with positions and 8-byte values along).
    python tools/stress.py [--seconds 60]"""
 import argparse, os, sys, time
 import numpy as np
@@ -34,7 +35,7 @@ def checks(a):
     return int(a64.sum(dtype=np.uint64)), int(np.bitwise_xor.reduce(a64)) if a.size else 0
 while time.time() < t_end and it < args.stop_after:
     it += 1
-    kind = rng.choice(["u32", "kv", "u64", "soa", "soaw", "compact", "hist"])
+    kind = rng.choice(["u32", "kv", "u64", "soa", "soaw", "compact", "hist", "merge"])
     n = int(2 ** rng.uniform(10, 25.5)) + int(rng.randint(0, 1000))
     if it % 7 == 0: n = int(2 ** rng.uniform(21, 26.3))   # more of the large sort's range
     if kind == "u32" and it % 23 == 0: n = (1 << 26) + int(rng.randint(1, 1 << 22))     # past 256 MiB: pointer stores
@@ -53,7 +54,7 @@ while time.time() < t_end and it < args.stop_after:
             else: rng.randint(1, 4)
         continue
     if verbose: print("it %d %s n=%d algo=%d bits=%d tile=%d msd2=%d dist=%s shift=%d" % (it, kind, n, algo, bits, tile, msd2_mode, dist, shift), flush=True)
-    if kind in ("u32", "soa", "kv", "soaw", "compact", "hist"):
+    if kind in ("u32", "soa", "kv", "soaw", "compact", "hist", "merge"):
         k = oracle.keys_u32(n, seed=it)
         if dist == "heavy": k = np.where(np.arange(n) % 10 != 0, (k >> np.uint32(8)) | np.uint32(0x37000000), k).astype(np.uint32)
         elif dist == "vals4096": k = (k >> np.uint32(20)) * np.uint32(0x00100801)
@@ -104,6 +105,27 @@ while time.time() < t_end and it < args.stop_after:
         below = k.view(np.int32) < th.view(np.int32)
         order = np.concatenate([np.flatnonzero(below), np.flatnonzero(~below)])
         assert s == int(below.sum()) and np.array_equal(oi, order) and np.array_equal(ok, k[order]) and np.array_equal(ov, v[order]), (it, kind, n, dist)
+    elif kind == "merge":   # two sorted parts of the keys merged, against the stable argsort of the codes of their concatenation
+        mr = np.random.RandomState(args.seed + 11 * it)
+        n = min(n, 1 << 24)
+        na = int(mr.choice([0, 1, n // 2, n - 1, n, int(mr.randint(0, n + 1))])); nb = n - na
+        dt, desc = [np.int32, np.float32][mr.randint(0, 2)], bool(mr.randint(0, 2))
+        d.setParam("debug.merge_grid", int(mr.choice([0, 0, 1, 7, 300])))
+        ka = Buffer(d, max(na, 1), dt); kb = Buffer(d, max(nb, 1), dt); ko = Buffer(d, n, dt)
+        va = Buffer(d, max(na, 1), np.uint64); vb = Buffer(d, max(nb, 1), np.uint64); vo = Buffer(d, n, np.uint64)
+        v = np.arange(n, dtype=np.uint64) * np.uint64(0x9E3779B97F4A7C15)
+        if na: ka.write(k[:na].view(dt)); va.write(v[:na]); p.sortPairs(d, ka, va, na, descending=desc)
+        if nb: kb.write(k[na:n].view(dt)); vb.write(v[na:n]); p.sortPairs(d, kb, vb, nb, descending=desc)
+        oi = p.mergePairs(d, ka, va, kb, vb, ko, vo, na, nb, descending=desc, indexOut=True)
+        sa, sb, sva, svb = ka.toHost()[:na].view(np.uint32), kb.toHost()[:nb].view(np.uint32), va.toHost()[:na], vb.toHost()[:nb]
+        ok, ov, gi = ko.toHost().view(np.uint32), vo.toHost(), oi.toHost()
+        for b in (ka, kb, ko, va, vb, vo, oi): b.release()
+        d.setParam("debug.merge_grid", 0)
+        cat = np.concatenate([sa, sb])
+        code = cat ^ np.uint32(0x80000000) if dt == np.int32 else cat ^ np.where(cat & np.uint32(0x80000000) != 0, np.uint32(0xffffffff), np.uint32(0x80000000))
+        order = np.argsort(~code if desc else code, kind="stable")
+        assert np.array_equal(gi, order) and np.array_equal(ok, cat[order]) and np.array_equal(ov, np.concatenate([sva, svb])[order]), (it, kind, n, na, dt, desc, dist)
+        assert np.array_equal(np.sort(ov), np.sort(v)), (it, kind, "the values are not a permutation")
     elif kind == "hist":   # a histogram of the keys: mode, type, bins and grid knob from a generator of this iteration's own
         hr = np.random.RandomState(args.seed + 7 * it)
         n = min(n, 1 << 24)
