@@ -211,6 +211,19 @@ public:
                            nb, descending);
     }
 
+    // set operations on sorted sequences: op = ADLHIP_SETOP_INTERSECTION / UNION / DIFFERENCE / SYMMETRIC_DIFFERENCE of the first na keys
+    // of keysA and the first nb keys of keysB, each sorted in the order of sortKeys(descending), with thrust's multiset semantics: of
+    // a key that occurs m times in A and n times in B the result holds min(m, n) copies (the first of A's), max(m, n) (A's, then the
+    // last of B's), max(m - n, 0) (the last of A's) or |m - n| (the last of A's or of B's).  Keys are equal when their bits are.
+    // Returns the number S of result elements (it waits for it): keysOut[0 .. S) in the order of mergeKeys, valuesOut[0 .. S) the kept
+    // elements' own values (valuesA / valuesB / valuesOut: all or none), indexOut[0 .. S) their positions in A || B.  The outputs
+    // hold na elements for intersection and difference, na + nb for the other two.  K, V: int, float, long long, double, u32, u64.
+    // A TYPE_HOST device runs thrust's two-pointer loops
+    template <typename K, typename V>
+    int setOp(const adl::Device* device, int op, const adl::Buffer<K>& keysA, const adl::Buffer<V>* valuesA, const adl::Buffer<K>& keysB,
+              const adl::Buffer<V>* valuesB, adl::Buffer<K>& keysOut, adl::Buffer<V>* valuesOut, adl::Buffer<u32>* indexOut, int na, int nb,
+              bool descending = false);
+
 private:
     template <typename T> int uniqueTyped(const adl::Device* device, const adl::Buffer<T>& keys, adl::Buffer<T>& uniqueOut, adl::Buffer<u32>& countsOut,
                                           int n, bool descending);

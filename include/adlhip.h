@@ -631,6 +631,68 @@ int adlhip_merge_typed(adlhip_device* dev, int key_type, int order,
                        int value_bytes, void* d_keys_out_or_null, void* d_vals_out_or_null, uint32_t* d_index_out_or_null,
                        void* d_work, size_t work_bytes);
 
+/* ---- set operations on sorted sequences (no reference counterpart) ---- */
+
+/* Intersection, union, difference and symmetric difference of two sequences that are already sorted: thrust's set_intersection /
+ * set_union / set_difference / set_symmetric_difference and their _by_key forms, and -- for inputs without duplicates -- numpy's
+ * intersect1d / union1d / setdiff1d / setxor1d, without merging, counting runs and compacting.
+ *
+ * Order.  A (d_keys_a, na keys) and B (d_keys_b, nb keys) are each sorted in `order` as adlhip_merge_typed asks: the codes
+ *   adlhip_key_encode(key_type, order) gives for their elements are non-decreasing.  Keys are equal when their bits are: -0 is not
+ *   +0, NaNs are equal by payload.
+ * Result.  Duplicates are allowed, with thrust's multiset semantics.  For a key x that occurs m times in A and n times in B:
+ *     op                                    copies of x     which elements
+ *     ADLHIP_SETOP_INTERSECTION             min(m, n)       the first min(m, n) of A's
+ *     ADLHIP_SETOP_UNION                    max(m, n)       all of A's, then the last max(n - m, 0) of B's
+ *     ADLHIP_SETOP_DIFFERENCE               max(m - n, 0)   the last max(m - n, 0) of A's
+ *     ADLHIP_SETOP_SYMMETRIC_DIFFERENCE     |m - n|         the last m - n of A's, or the last n - m of B's
+ *   That is, with r an element's rank inside its own input's run of x: an element of A is kept by intersection when r < n, by
+ *   difference and symmetric difference when r >= n, by union always; an element of B is kept by union and symmetric difference when
+ *   r >= m, never otherwise.  The result is the kept elements in the order of the stable merge (ties: A before B): it is sorted in
+ *   `order`, and it is exactly the subsequence these rules select of what adlhip_merge_typed returns for the same inputs.
+ *     *d_num_out      S, the number of result elements; it stays on the device
+ *     d_keys_out[j]   the j-th kept key, bit for bit, j < S
+ *     d_vals_out[j]   the kept element's own value: A's for an element of A, B's for one of B (value_bytes 4 or 8: d_vals_a, d_vals_b
+ *                     and d_vals_out are all given; value_bytes 0: all NULL)
+ *     d_index_out[j]  its position in A || B: i for A[i], na + i for B[i]
+ *   At least one output besides the count word is given.  Each given output holds cap elements: cap = na for intersection and
+ *   difference, na + nb for union and symmetric difference.  Elements at S and beyond are never written.
+ *
+ * Contract.  That of adlhip_merge_typed: na + nb < 2^32; either count may be 0 (the array of an empty input is not looked at).  The
+ * inputs are never written, need only the alignment of their element and may overlap or be the same array.  No output, nor the count
+ * word, nor d_work may overlap an input or one another.  The outputs and d_work are 16-byte aligned, the count word 4-byte aligned.
+ * na + nb == 0 succeeds and enqueues only a clear of the count word (d_work may then be NULL).  A NULL required pointer, a misaligned
+ * pointer, an overlap, an unknown key_type, order, op or value_bytes, value arrays that do not agree with value_bytes, no output at
+ * all, na + nb >= 2^32 and a work buffer one byte short (the message names the needed size and adlhip_set_op_scratch_bytes) fail
+ * before anything is enqueued, each with a message that names the argument.  The call enqueues and returns: nothing data-dependent
+ * reaches the host (launch grids depend on na + nb alone), nothing is remembered between calls, all state lives in d_work -- whose
+ * contents on entry are arbitrary.  No kernel waits on another workgroup or uses an atomic to global memory.
+ *
+ * Inputs that are NOT sorted: the result is unspecified, but the call succeeds and terminates, every read stays inside
+ * [A, A + na) and [B, B + nb), *d_num_out <= cap and no write lands at cap or beyond (setop_kernels.hpp proves the reads and clamps
+ * the writes and the count).
+ *
+ * Work bytes:
+ *   adlhip_set_op_scratch_bytes = (4 x 8 x CUs rounded up to 256) + (4 x (tiles + 1) rounded up to 256),
+ *   tiles = ceil((na + nb) / ADLHIP_SETOP_TILE): the number of kept elements per workgroup, and the number of elements of A in front
+ *   of every tile boundary.  key_type and value_bytes are checked and do not change the value.
+ *
+ * Four launches over tiles of ADLHIP_SETOP_TILE elements of the merged order: the merge's partition; a count -- every workgroup
+ * merges its chunk of tiles in LDS as adlhip_merge_typed does and decides per element whether it is kept, by one look at the other
+ * input at the element's rank in its run; a scan of the workgroups' counts, whose total is S; and an emit that repeats the walk,
+ * ranks the kept elements of a tile with a workgroup scan, puts them in rank order in LDS and stores them densely. */
+#define ADLHIP_SETOP_TILE 2048
+#define ADLHIP_SETOP_INTERSECTION 0
+#define ADLHIP_SETOP_UNION 1
+#define ADLHIP_SETOP_DIFFERENCE 2
+#define ADLHIP_SETOP_SYMMETRIC_DIFFERENCE 3
+int adlhip_set_op_scratch_bytes(adlhip_device* dev, int key_type, int value_bytes, size_t na, size_t nb, size_t* work_bytes);
+int adlhip_set_op_typed(adlhip_device* dev, int key_type, int order, int op,
+                        const void* d_keys_a, const void* d_vals_a_or_null, size_t na,
+                        const void* d_keys_b, const void* d_vals_b_or_null, size_t nb,
+                        int value_bytes, void* d_keys_out_or_null, void* d_vals_out_or_null, uint32_t* d_index_out_or_null,
+                        uint32_t* d_num_out, void* d_work, size_t work_bytes);
+
 /* ---- segments finished in LDS (no reference counterpart) ------------------------------------- */
 
 /* Sorts, stably and in place, every segment [d_seg_start[s], d_seg_start[s + 1]) of an array of u32 keys
@@ -807,6 +869,8 @@ int adlhip_generate_keys(adlhip_device* dev, int elem_kind, void* dptr, size_t n
  *                      workgroups take many tiles
  *   "debug.merge_grid" workgroups the tile kernel of adlhip_merge_typed is launched with at most (0 [default]: 8 per CU; larger values
  *                      change nothing); tests set it to make few workgroups take many tiles in turns.  The result does not depend on it
+ *   "debug.setop_grid" workgroups the count and emit kernels of adlhip_set_op_typed are launched with at most (0 [default]: 8 per CU;
+ *                      larger values change nothing); tests set it to make few workgroups take many tiles.  The result does not depend on it
  *   "debug.histogram_lds_bins" the largest num_bins for which adlhip_bincount_typed takes the LDS path (1 .. 8192, default 8192; 0
  *                      sets the default); tests lower it to reach the sorted path with few keys.  adlhip_get_param reports the limit
  *   "debug.persist_grid" workgroups both persistent passes of the large keys-only sort (cursor form) are launched with, rounded up to

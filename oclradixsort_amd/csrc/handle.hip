@@ -216,6 +216,7 @@ const Knob kKnobs[] = {
     {"debug.compact_grid", &adlhip_device::compact_grid, 0, kNoMax, "debug.compact_grid must be >= 0", nullptr},
     {"debug.histogram_grid", &adlhip_device::histogram_grid, 0, kNoMax, "debug.histogram_grid must be >= 0", nullptr},
     {"debug.merge_grid", &adlhip_device::merge_grid, 0, kNoMax, "debug.merge_grid must be >= 0", nullptr},
+    {"debug.setop_grid", &adlhip_device::setop_grid, 0, kNoMax, "debug.setop_grid must be >= 0", nullptr},
     {"debug.persist_grid", &adlhip_device::persist_grid, 0, 4096, "debug.persist_grid must be in [0, 4096]", nullptr},
     // ---- with a rule of their own
     {"sort.digit_bits", &adlhip_device::digit_bits, 0, 0, nullptr,

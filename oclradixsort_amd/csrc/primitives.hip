@@ -1,5 +1,5 @@
 // primitives.hip -- the host side of what is built on top of the sorts: typed keys and argsort, top-k, row-wise top-k, unique /
-// run-length encode, reduce by key, typed scans, stream compaction, histograms, merges.  No reference counterpart.  It reaches the sorts through adlhip_internal.hpp alone (sort_elements,
+// run-length encode, reduce by key, typed scans, stream compaction, histograms, merges, set operations.  No reference counterpart.  It reaches the sorts through adlhip_internal.hpp alone (sort_elements,
 // sort_work_bytes, soa_wide_layout) and never sees their kernels.
 #include "adlhip_internal.hpp"
 
@@ -22,9 +22,10 @@
 #include "compact_kernels.hpp"
 #include "histogram_kernels.hpp"
 #include "merge_kernels.hpp"
+#include "setop_kernels.hpp"
 
 // instantiated in kernels_select.hip / kernels_toprows.hip / kernels_unique.hip / kernels_reduce.hip / kernels_scan.hip /
-// kernels_compact.hip / kernels_histogram.hip / kernels_merge.hip; here they are only declared
+// kernels_compact.hip / kernels_histogram.hip / kernels_merge.hip / kernels_setop.hip; here they are only declared
 #ifndef ADLHIP_SINGLE_TU
 #define X(...) extern template __global__ __VA_ARGS__;
 #include "select_kernels.inc"
@@ -35,6 +36,7 @@
 #include "compact_kernels.inc"
 #include "histogram_kernels.inc"
 #include "merge_kernels.inc"
+#include "setop_kernels.inc"
 #undef X
 #endif
 
@@ -986,6 +988,58 @@ int merge_stage(adlhip_device* d, adlhip::RedCodec codec, const K* a, const V* v
     });
 }
 
+// ---- set operations on sorted sequences (setop_kernels.hpp) ----------------------------------------------------
+static_assert(ADLHIP_SETOP_TILE == adlhip::kRedTile, "the header states the tile of the set operations");
+static_assert(ADLHIP_SETOP_INTERSECTION == adlhip::kSetIntersection && ADLHIP_SETOP_UNION == adlhip::kSetUnion &&
+              ADLHIP_SETOP_DIFFERENCE == adlhip::kSetDifference && ADLHIP_SETOP_SYMMETRIC_DIFFERENCE == adlhip::kSetSymmetricDifference,
+              "the kernels' operations are the public ones");
+// grid of the count and emit kernels per CU at most ("debug.setop_grid" lowers it): the merge's, for the merge's reason
+constexpr int kSetopWgsPerCu = 8;
+// Work of a set operation: [kept counts: one u32 per workgroup of the largest grid], rounded up to 256 bytes, then [split: one u32 per
+// tile boundary], rounded up to 256 bytes
+size_t setop_chunk_bytes(const adlhip_device* d)
+{
+    return align_up((size_t)d->prop.multiProcessorCount * kSetopWgsPerCu * 4, 256);
+}
+size_t setop_work_bytes(const adlhip_device* d, size_t n)
+{
+    return setop_chunk_bytes(d) + merge_work_bytes(n);
+}
+
+// the set operation on n = na + nb > 0 elements; V: the values' unsigned type, vals_out null = none; cap: what every output holds
+template <typename K, typename V>
+int setop_stage(adlhip_device* d, adlhip::RedCodec codec, uint32_t op, const K* a, const V* va, size_t na, const K* b, const V* vb, size_t nb,
+                size_t cap, K* keys_out, V* vals_out, uint32_t* index_out, uint32_t* num_out, void* work)
+{
+    uint32_t* chunk = static_cast<uint32_t*>(work);
+    uint32_t* split = reinterpret_cast<uint32_t*>(static_cast<char*>(work) + setop_chunk_bytes(d));
+    const ChunkSplit cs = chunk_split(d, na + nb, (size_t)adlhip::kRedTile, kSetopWgsPerCu, d->setop_grid);
+    const uint32_t wgs = cs.wgs, tiles = cs.tiles, tpw = cs.tiles_per_wg;
+    const uint32_t pwgs = (tiles + 1 + (uint32_t)adlhip::kSelNT - 1) / (uint32_t)adlhip::kSelNT;
+    const uint32_t ua = (uint32_t)na, ub = (uint32_t)nb;
+    int rc = launch(d, "setop_partition", [&] {
+        hipLaunchKernelGGL((adlhip::merge_partition_kernel<K>), dim3(pwgs), dim3(adlhip::kSelNT), 0, d->stream, a, ua, b, ub, codec, tiles, split);
+    });
+    if (rc) return rc;
+    rc = launch(d, sizeof(K) == 4 ? "setop_count_k32" : "setop_count_k64", [&] {
+        hipLaunchKernelGGL((adlhip::setop_count_kernel<K>), dim3(wgs), dim3(adlhip::kSelNT), 0, d->stream, a, ua, b, ub, codec, op,
+                           (const uint32_t*)split, tiles, tpw, chunk);
+    });
+    if (rc) return rc;
+    rc = launch_scan_single(d, "setop_scan", chunk, chunk, wgs, num_out);   // in place; the total is the number kept
+    if (rc) return rc;
+    const int vbits = vals_out ? 8 * (int)sizeof(V) : 0;
+    return launch(d, intern(std::string("setop_emit_k") + std::to_string(8 * sizeof(K)) + "_v" + std::to_string(vbits)), [&] {
+        if (vals_out)
+            hipLaunchKernelGGL((adlhip::setop_emit_kernel<K, V>), dim3(wgs), dim3(adlhip::kSelNT), 0, d->stream, a, va, ua, b, vb, ub, codec, op,
+                               (const uint32_t*)split, tiles, tpw, (const uint32_t*)chunk, (uint32_t)cap, num_out, keys_out, vals_out, index_out);
+        else
+            hipLaunchKernelGGL((adlhip::setop_emit_kernel<K, adlhip::MergeNone>), dim3(wgs), dim3(adlhip::kSelNT), 0, d->stream, a,
+                               (const adlhip::MergeNone*)nullptr, ua, b, (const adlhip::MergeNone*)nullptr, ub, codec, op, (const uint32_t*)split,
+                               tiles, tpw, (const uint32_t*)chunk, (uint32_t)cap, num_out, keys_out, (adlhip::MergeNone*)nullptr, index_out);
+    });
+}
+
 }  // namespace
 
 extern "C" {
@@ -1440,6 +1494,55 @@ int adlhip_merge_typed(adlhip_device* d, int key_type, int order, const void* ke
     const adlhip::RedCodec codec = {(uint32_t)t.kind, (uint32_t)order};
     return ADLHIP_BY_WIDTH(t.bytes, K, ADLHIP_BY_WIDTH(value_bytes ? value_bytes : 4, V, merge_stage<K, V>(d, codec, (const K*)keys_a,
                            (const V*)vals_a, na, (const K*)keys_b, (const V*)vals_b, nb, (K*)keys_out, (V*)vals_out, index_out, work)));
+}
+
+// ---- set operations on sorted sequences ----------------------------------------------------------------
+int adlhip_set_op_scratch_bytes(adlhip_device* d, int key_type, int value_bytes, size_t na, size_t nb, size_t* work_bytes)
+{
+    const char* what = "set op scratch";
+    if (!d) return fail("null device handle");
+    TypeInfo t;
+    size_t n;
+    if (type_info("key_type", key_type, &t) || merge_check_value_bytes(what, value_bytes) || merge_total(what, na, nb, &n)) return ADLHIP_FAILURE;
+    if (work_bytes) *work_bytes = setop_work_bytes(d, n);
+    return ADLHIP_SUCCESS;
+}
+
+int adlhip_set_op_typed(adlhip_device* d, int key_type, int order, int op, const void* keys_a, const void* vals_a, size_t na, const void* keys_b,
+                        const void* vals_b, size_t nb, int value_bytes, void* keys_out, void* vals_out, uint32_t* index_out, uint32_t* num_out,
+                        void* work, size_t work_bytes)
+{
+    const char* what = "set op";
+    TypeInfo t;
+    size_t n;
+    if (bind(d) || key_type_info(key_type, order, &t)) return ADLHIP_FAILURE;
+    if (op < ADLHIP_SETOP_INTERSECTION || op > ADLHIP_SETOP_SYMMETRIC_DIFFERENCE)
+        return fail("%s: op must be one of ADLHIP_SETOP_INTERSECTION .. ADLHIP_SETOP_SYMMETRIC_DIFFERENCE (0..3), got %d", what, op);
+    if (merge_check_value_bytes(what, value_bytes) || merge_total(what, na, nb, &n)) return ADLHIP_FAILURE;
+    if (value_bytes == 0 && (vals_a || vals_b || vals_out))
+        return fail("%s: value_bytes is 0, so d_vals_a, d_vals_b and d_vals_out must be NULL", what);
+    if (!keys_out && !vals_out && !index_out) return fail("%s: at least one of d_keys_out, d_vals_out and d_index_out must be given", what);
+    if (!num_out) return fail("%s: d_num_out is required", what);
+    const bool both = op == ADLHIP_SETOP_UNION || op == ADLHIP_SETOP_SYMMETRIC_DIFFERENCE;
+    const size_t cap = both ? n : na;   // what every output holds
+    const size_t kb = (size_t)t.bytes, vb = (size_t)value_bytes, va = vb ? vb : 1;
+    if (merge_check_buffers(what,
+                            {{keys_a, na * kb, "d_keys_a", na != 0, kb}, {keys_b, nb * kb, "d_keys_b", nb != 0, kb},
+                             {vals_a, na * vb, "d_vals_a", vb && na, va}, {vals_b, nb * vb, "d_vals_b", vb && nb, va}},
+                            {{keys_out, cap * kb, "d_keys_out", false, 16}, {vals_out, cap * vb, "d_vals_out", vb && cap, 16},
+                             {index_out, cap * 4, "d_index_out", false, 16}, {num_out, 4, "d_num_out", true, 4},
+                             {work, work_bytes, "d_work", n != 0, 16}}))
+        return ADLHIP_FAILURE;
+    const size_t need = n ? setop_work_bytes(d, n) : 0;
+    if (work_bytes < need) return fail("work buffer too small: %zu < %zu (adlhip_set_op_scratch_bytes)", work_bytes, need);
+    if (n == 0) {
+        HIPCHK(hipMemsetAsync(num_out, 0, 4, d->stream));
+        return ADLHIP_SUCCESS;
+    }
+    const adlhip::RedCodec codec = {(uint32_t)t.kind, (uint32_t)order};
+    return ADLHIP_BY_WIDTH(t.bytes, K, ADLHIP_BY_WIDTH(value_bytes ? value_bytes : 4, V, setop_stage<K, V>(d, codec, (uint32_t)op,
+                           (const K*)keys_a, (const V*)vals_a, na, (const K*)keys_b, (const V*)vals_b, nb, cap, (K*)keys_out, (V*)vals_out,
+                           index_out, num_out, work)));
 }
 
 }  // extern "C"

@@ -21,6 +21,7 @@
     p.histogramRange(device, keys, n, edges, num_bins)     # -> Buffer(uint32): the keys per bin [edges[b], edges[b + 1])
     p.binCount(device, keys, n, num_bins)                  # -> Buffer(uint32): the keys per value 0 .. num_bins - 1
     p.mergeKeys(device, a, b, out, na, nb)                 # the stable merge of two sorted key Buffers (mergePairs: with values)
+    p.setOp(device, "intersection", a, b, out, na, nb)     # -> SetOpResult: also "union", "difference", "symmetric_difference"
 
 Like the reference object it owns lazily grown device scratch (m_u32WorkBuffer[0] = ping-pong data
 buffer, m_u32WorkBuffer[1] = histogram table; Pprims.h:44-45, Pprims.cpp:226-232, :332-337) and must be
@@ -63,6 +64,13 @@ CMP_OPS = {"lt": 0, "le": 1, "gt": 2, "ge": 3, "eq": 4, "ne": 5, "<": 0, "<=": 1
 # the number of selected elements; items (compactIf: the keys), values and index have n elements of which the first S are written --
 # all n with partition=True, the rejected elements behind the selected ones.
 CompactResult = collections.namedtuple("CompactResult", "items values index count")
+
+# ADLHIP_SETOP_* (include/adlhip.h, "set operations on sorted sequences")
+SET_OPS = {"intersection": 0, "union": 1, "difference": 2, "symmetric_difference": 3}
+
+# What setOp returns: device Buffers (None where not asked).  `count` is a one-element uint32 Buffer that holds S, the number of result
+# elements; keys, values and index hold na (intersection, difference) or na + nb elements, of which the first S are written.
+SetOpResult = collections.namedtuple("SetOpResult", "keys values index count")
 
 # ADLHIP_HISTOGRAM_MAX_RANGE_BINS and ADLHIP_HISTOGRAM_TILE (include/adlhip.h, "histograms"): the most bins histogramRange takes, and
 # the elements of a tile of its count kernel (tests place their sizes around it)
@@ -752,6 +760,73 @@ class Pprims:
         if valuesA is None or valuesB is None or valuesOut is None:
             raise AdlHipError("mergePairs: valuesA, valuesB and valuesOut are required (mergeKeys merges keys alone)")
         return self._merge("mergePairs", device, keysA, valuesA, keysB, valuesB, keysOut, valuesOut, na, nb, descending, indexOut)
+
+    # -- set operations on sorted sequences (no reference counterpart; include/adlhip.h adlhip_set_op_typed)
+    def setOp(self, device, op, a, b, out, na, nb, descending=False, valuesA=None, valuesB=None, valuesOut=None, indexOut=None,
+              countOut=None):
+        """op ("intersection", "union", "difference", "symmetric_difference") of the first na keys of `a` and the first nb keys of `b`
+        -- Buffers of one key type, each sorted in the order of sortKeys(descending) -- with thrust's multiset semantics: of a key
+        that occurs m times in a and n times in b the result holds min(m, n) (the first of a's), max(m, n) (a's, then the last of
+        b's), max(m - n, 0) (the last of a's) or |m - n| copies.  Keys are equal when their bits are.  -> SetOpResult: with S result
+        elements (result.count, on the device) out[0 .. S) are the kept keys in the order of mergeKeys, valuesOut[0 .. S) the kept
+        elements' own values (valuesA, valuesB and valuesOut go together: any element type of 4 or 8 bytes) and index[0 .. S) their
+        positions in a || b (indexOut: True for a new uint32 Buffer, or one to fill).  out may be None when only values or positions
+        are wanted.  Every output holds na elements for intersection and difference, na + nb for the other two; nothing at S and
+        beyond is written.  The inputs are left intact and may be the same Buffer.  Inputs that are not sorted give an unspecified
+        result, never an access outside the Buffers.  Enqueues and returns; read result.count (toHost) to learn S."""
+        what = "setOp"
+        if device is None:
+            raise AdlHipError("%s needs a device" % what)
+        if op not in SET_OPS:
+            raise AdlHipError("%s: op must be 'intersection', 'union', 'difference' or 'symmetric_difference', got %r" % (what, op))
+        if a is None or b is None:
+            raise AdlHipError("%s: both inputs are required (an empty one with its count 0)" % what)
+        kt = self._key_type(a, what)
+        if np.dtype(b.dtype) != np.dtype(a.dtype):
+            raise AdlHipError("%s: a is %s, b %s" % (what, a.dtype, b.dtype))
+        na, nb = int(na), int(nb)
+        for name, buf, n in (("na", a, na), ("nb", b, nb)):
+            if n < 0 or buf.getSize() < n:
+                raise AdlHipError("%s: %s = %d outside [0, %d]" % (what, name, n, buf.getSize()))
+        if na + nb >= 1 << 32:
+            raise AdlHipError("%s: na + nb = %d; fewer than 2^32 elements" % (what, na + nb))
+        cap = na + nb if op in ("union", "symmetric_difference") else na
+        if out is not None and (not hasattr(out, "getSize") or np.dtype(out.dtype) != np.dtype(a.dtype) or out.getSize() < cap):
+            raise AdlHipError("%s: out must hold %d elements of %s" % (what, cap, a.dtype))
+        vbytes = 0
+        if valuesA is not None or valuesB is not None or valuesOut is not None:
+            if valuesA is None or valuesB is None or valuesOut is None:
+                raise AdlHipError("%s: valuesA, valuesB and valuesOut go together" % what)
+            vbytes = np.dtype(valuesA.dtype).itemsize
+            if vbytes not in (4, 8):
+                raise AdlHipError("%s: unsupported values type %s (4 or 8 bytes)" % (what, valuesA.dtype))
+            if np.dtype(valuesB.dtype) != np.dtype(valuesA.dtype) or np.dtype(valuesOut.dtype) != np.dtype(valuesA.dtype):
+                raise AdlHipError("%s: the values are %s, %s and %s" % (what, valuesA.dtype, valuesB.dtype, valuesOut.dtype))
+            if valuesA.getSize() < na or valuesB.getSize() < nb or valuesOut.getSize() < cap:
+                raise AdlHipError("%s: the values must hold na, nb and %d elements" % (what, cap))
+        if countOut is not None and (np.dtype(countOut.dtype) != np.uint32 or countOut.getSize() < 1):
+            raise AdlHipError("%s: countOut must hold one uint32 element" % what)
+        if out is None and valuesOut is None and (indexOut is None or indexOut is False):
+            raise AdlHipError("%s: nothing asked (out, valuesOut or indexOut)" % what)
+        (idx,), own = self._runs_outputs(what, device, max(cap, 1), [("indexOut", indexOut, cap)])
+        try:
+            lib = _lib.load()
+            wb = ctypes.c_size_t()
+            check(lib.adlhip_set_op_scratch_bytes(device._h, kt, vbytes, na, nb, ctypes.byref(wb)), "adlhip_set_op_scratch_bytes")
+            self._scratch(device, 0, wb.value)
+            if countOut is None:
+                countOut = Buffer(device, 1, np.uint32)
+                own.append(countOut)
+
+            def p(buf):
+                return buf.ptr() if buf is not None else None
+            check(lib.adlhip_set_op_typed(device._h, kt, 1 if descending else 0, SET_OPS[op], p(a), p(valuesA), na, p(b), p(valuesB), nb, vbytes,
+                                          p(out), p(valuesOut), p(idx), countOut.ptr(), self.m_work.ptr(), self.m_work.getSize()), what)
+        except AdlHipError:
+            for buf in own:
+                buf.release()
+            raise
+        return SetOpResult(out, valuesOut, idx, countOut)
 
     def copy(self, device, dst, src, n):
         """Pprims::copy (Pprims.cpp:31-67, commented out in the reference): first n elements of src -> dst."""

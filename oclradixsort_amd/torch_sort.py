@@ -17,6 +17,7 @@ back-end on torch's own stream.
     out, count = s.partition(t, mask)                                            # the selected elements, then the others; both in input order
     c = s.bincount(t); c = s.histogram(t, edges); c = s.histc(t, 100, 0.0, 1.0)  # torch.bincount / numpy.histogram(t, edges)[0] / the same on linspace edges
     m = s.merge(a, b); m, v, i = s.merge(a, b, values=(va, vb), return_indices=True)   # torch.sort(torch.cat((a, b)), stable=True) of sorted a, b
+    i = s.intersect(a, b); u = s.union(a, b); d = s.difference(a, b); x = s.symmetric_difference(a, b)   # of sorted a, b: numpy.intersect1d / union1d / setdiff1d / setxor1d
     s.close()
 
 Always out of place and always stable.  The ONE difference from `torch.sort(t, stable=True)`: floats are ordered by
@@ -568,6 +569,73 @@ class TorchSorter:
         if return_indices:
             out += (idx32.to(torch.int64) & 0xffffffff,)
         return out if len(out) > 1 else out[0]
+
+    def _set_op(self, op, what, a, b, descending, values, return_indices):
+        ka, kb = self._merge_input(a, what), self._merge_input(b, what)
+        if ka.dtype != kb.dtype:
+            raise TypeError("TorchSorter.%s: a is %s, b %s" % (what, ka.dtype, kb.dtype))
+        va = vb = None
+        if values is not None:
+            if not isinstance(values, (tuple, list)) or len(values) != 2:
+                raise ValueError("TorchSorter.%s: values is a pair (values of a, values of b)" % what)
+            va, vb = self._merge_input(values[0], what), self._merge_input(values[1], what)
+            if va.dtype != vb.dtype:
+                raise TypeError("TorchSorter.%s: the values are %s and %s" % (what, va.dtype, vb.dtype))
+            if va.numel() != ka.numel() or vb.numel() != kb.numel():
+                raise ValueError("TorchSorter.%s: %d and %d elements but %d and %d values" % (what, ka.numel(), kb.numel(), va.numel(), vb.numel()))
+        if torch.cuda.current_stream(self.torch_device).cuda_stream != self.raw_stream:
+            raise RuntimeError("TorchSorter: bound to the stream that was current at construction; another stream is current now")
+        na, nb = ka.numel(), kb.numel()
+        if na + nb >= 1 << 32:
+            raise ValueError("TorchSorter: fewer than 2^32 elements")
+        cap = na + nb if op in ("union", "symmetric_difference") else na
+        dev = ka.device
+        kout = torch.empty(cap, dtype=ka.dtype, device=dev)
+        vout = torch.empty(cap, dtype=va.dtype, device=dev) if va is not None else None
+        idx32 = torch.empty(cap, dtype=torch.int32, device=dev) if return_indices else None   # uint32 positions in an int32 tensor
+        s = 0
+        if cap:
+            count = torch.empty(1, dtype=torch.int32, device=dev)
+            kdt = _NP_DTYPE[ka.dtype]
+            vdt = _NP_DTYPE[va.dtype] if va is not None else None
+            self.pprims.setOp(self.device, op, self._wrap(ka, kdt), self._wrap(kb, kdt), self._wrap(kout, kdt), na, nb,
+                              descending=bool(descending), valuesA=self._wrap(va, vdt) if va is not None else None,
+                              valuesB=self._wrap(vb, vdt) if va is not None else None,
+                              valuesOut=self._wrap(vout, vdt) if va is not None else None,
+                              indexOut=self._wrap(idx32, np.uint32) if return_indices else None, countOut=self._wrap(count, np.uint32))
+            self.device.checkFault()
+            s = int(count.item()) & 0xffffffff   # the one host read
+        out = (kout[:s].clone(),)
+        if va is not None:
+            out += (vout[:s].clone(),)
+        if return_indices:
+            out += (idx32[:s].to(torch.int64) & 0xffffffff,)
+        return out if len(out) > 1 else out[0]
+
+    def intersect(self, a, b, descending=False, values=None, return_indices=False):
+        """The elements of the sorted 1-D tensor a that the sorted 1-D tensor b of the same dtype holds too: for inputs without
+        duplicates, NaN or -0 what numpy.intersect1d(a, b, assume_unique=True) returns (descending=True: in descending order).
+        With duplicates the semantics are thrust's set_intersection: of an element that occurs m times in a and n times in b the
+        first min(m, n) of a's.  Elements are equal when their bits are; the order is that of merge().  Returns the result, then --
+        where given -- the kept elements' own `values` (a pair of 1-D tensors of a's and b's lengths and one dtype), then -- where
+        asked -- their int64 indices into torch.cat((a, b)); one tensor or a tuple.  Contiguous views at any element offset are read
+        where they lie.  ONE host read, of the size of the result."""
+        return self._set_op("intersection", "intersect", a, b, descending, values, return_indices)
+
+    def union(self, a, b, descending=False, values=None, return_indices=False):
+        """numpy.union1d(a, b) of sorted 1-D tensors without duplicates; with duplicates thrust's set_union: max(m, n) copies, all
+        of a's and then the last n - m of b's.  Everything else as intersect()."""
+        return self._set_op("union", "union", a, b, descending, values, return_indices)
+
+    def difference(self, a, b, descending=False, values=None, return_indices=False):
+        """numpy.setdiff1d(a, b, assume_unique=True) of sorted 1-D tensors without duplicates; with duplicates thrust's
+        set_difference: the last max(m - n, 0) of a's copies.  Everything else as intersect()."""
+        return self._set_op("difference", "difference", a, b, descending, values, return_indices)
+
+    def symmetric_difference(self, a, b, descending=False, values=None, return_indices=False):
+        """numpy.setxor1d(a, b, assume_unique=True) of sorted 1-D tensors without duplicates; with duplicates thrust's
+        set_symmetric_difference: |m - n| copies, the last of a's or of b's.  Everything else as intersect()."""
+        return self._set_op("symmetric_difference", "symmetric_difference", a, b, descending, values, return_indices)
 
     def sort(self, t, descending=False):
         """(values, indices) like torch.sort(t, descending=descending, stable=True); indices are int64."""

@@ -8,7 +8,8 @@
 // adlhip_scan_by_key, or a plain loop, left to right.  Pprims::compactFlagged / compactIf: adlhip_compact_flagged /
 // adlhip_compact_if_typed (they wait for the count), or a plain loop.  Pprims::histogramRange / binCount:
 // adlhip_histogram_range_typed / adlhip_bincount_typed, or a plain loop.  Pprims::mergeKeys / mergePairs: adlhip_merge_typed, or a
-// plain two-pointer loop in which a tie takes the first input.
+// plain two-pointer loop in which a tie takes the first input.  Pprims::setOp: adlhip_set_op_typed (it waits for the count), or
+// thrust's two-pointer loops.
 #include <Tahoe/ParallelPrimitives/Pprims.h>
 
 #include <algorithm>
@@ -819,6 +820,98 @@ TAHOE_MERGE_KEY(u32)
 TAHOE_MERGE_KEY(u64)
 #undef TAHOE_MERGE_KEY
 #undef TAHOE_MERGE
+
+// ---- set operations on sorted sequences: adlhip_set_op_typed, or thrust's two-pointer loops ----
+template <typename K, typename V>
+int Pprims::setOp(const adl::Device* device, int op, const adl::Buffer<K>& keysA, const adl::Buffer<V>* valuesA, const adl::Buffer<K>& keysB,
+                  const adl::Buffer<V>* valuesB, adl::Buffer<K>& keysOut, adl::Buffer<V>* valuesOut, adl::Buffer<u32>* indexOut, int na, int nb,
+                  bool descending)
+{
+    ADLASSERT(na >= 0 && nb >= 0);
+    ADLASSERT(op >= ADLHIP_SETOP_INTERSECTION && op <= ADLHIP_SETOP_SYMMETRIC_DIFFERENCE);
+    ADLASSERT((valuesA != 0) == (valuesOut != 0) && (valuesB != 0) == (valuesOut != 0));
+    ADLASSERT((long long)na + nb <= 0x7fffffffLL);   // (the facade counts in int)
+    if (na < 0 || nb < 0 || (long long)na + nb > 0x7fffffffLL || na + nb == 0) return 0;
+    if (op < ADLHIP_SETOP_INTERSECTION || op > ADLHIP_SETOP_SYMMETRIC_DIFFERENCE) return 0;
+    const bool both = op == ADLHIP_SETOP_UNION || op == ADLHIP_SETOP_SYMMETRIC_DIFFERENCE;
+    const int cap = both ? na + nb : na;
+    ADLASSERT(device != 0);
+    ADLASSERT((adl::u64)na <= keysA.getSize() && (adl::u64)nb <= keysB.getSize() && (adl::u64)cap <= keysOut.getSize() &&
+              (!valuesA || (adl::u64)na <= valuesA->getSize()) && (!valuesB || (adl::u64)nb <= valuesB->getSize()) &&
+              (!valuesOut || (adl::u64)cap <= valuesOut->getSize()) && (!indexOut || (adl::u64)cap <= indexOut->getSize()));
+    if (!onDevice(device)) {
+        ADLASSERT(device->getType() == adl::TYPE_HOST);   // a HIP device never falls back to the CPU
+        if (device->getType() != adl::TYPE_HOST) return 0;
+        if (cap == 0) return 0;
+        K* a = na ? keysA.getHostPtr(na) : 0;
+        K* b = nb ? keysB.getHostPtr(nb) : 0;
+        V* va = valuesA && na ? valuesA->getHostPtr(na) : 0;
+        V* vb = valuesB && nb ? valuesB->getHostPtr(nb) : 0;
+        K* out = keysOut.getHostPtr(cap);
+        V* vout = valuesOut ? valuesOut->getHostPtr(cap) : 0;
+        u32* idx = indexOut ? indexOut->getHostPtr(cap) : 0;
+        adl::DeviceUtils::waitForCompletion(device);
+        const bool keepOnlyA = op != ADLHIP_SETOP_INTERSECTION;   // an element of A with nothing equal left in B
+        const bool keepEqual = op == ADLHIP_SETOP_INTERSECTION || op == ADLHIP_SETOP_UNION;   // a pair of equal elements: A's
+        int i = 0, j = 0, o = 0;
+        while (i < na || j < nb) {
+            const bool onlyA = j >= nb || (i < na && ordinal(a[i], descending) < ordinal(b[j], descending));
+            const bool onlyB = !onlyA && (i >= na || ordinal(b[j], descending) < ordinal(a[i], descending));
+            const bool fromB = onlyB;
+            const bool keep = onlyA ? keepOnlyA : (onlyB ? both : keepEqual);
+            if (keep) {
+                out[o] = fromB ? b[j] : a[i];
+                if (vout) vout[o] = fromB ? vb[j] : va[i];
+                if (idx) idx[o] = fromB ? (u32)(na + j) : (u32)i;
+                ++o;
+            }
+            if (!onlyB) ++i;
+            if (!onlyA) ++j;
+        }
+        if (a) keysA.returnHostPtr(a);
+        if (b) keysB.returnHostPtr(b);
+        if (va) valuesA->returnHostPtr(va);
+        if (vb) valuesB->returnHostPtr(vb);
+        keysOut.returnHostPtr(out);
+        if (vout) valuesOut->returnHostPtr(vout);
+        if (idx) indexOut->returnHostPtr(idx);
+        adl::DeviceUtils::waitForCompletion(device);
+        return o;
+    }
+    const int vbytes = valuesOut ? (int)sizeof(V) : 0;
+    size_t wb = 0;
+    const int rcq = adlhip_set_op_scratch_bytes(device->hip(), KeyTraits<K>::TYPE, vbytes, (size_t)na, (size_t)nb, &wb);
+    ADLASSERT(rcq == ADLHIP_SUCCESS);
+    reserve(device, 16, wb);   // m_tmp holds the count word
+    const int rc = adlhip_set_op_typed(device->hip(), KeyTraits<K>::TYPE, descending ? ADLHIP_ORDER_DESCENDING : ADLHIP_ORDER_ASCENDING, op,
+                                       keysA.m_ptr, valuesA ? valuesA->m_ptr : 0, (size_t)na, keysB.m_ptr, valuesB ? valuesB->m_ptr : 0,
+                                       (size_t)nb, vbytes, keysOut.m_ptr, valuesOut ? valuesOut->m_ptr : 0,
+                                       indexOut ? (uint32_t*)indexOut->m_ptr : 0, (uint32_t*)m_tmp->m_ptr, m_work->m_ptr,
+                                       (size_t)m_work->getSize());
+    if (rc != ADLHIP_SUCCESS) TH_LOG_ERROR("Pprims::setOp: %s\n", adlhip_last_error());
+    ADLASSERT(rc == ADLHIP_SUCCESS);
+    if (rc != ADLHIP_SUCCESS) return 0;
+    unsigned char word[4] = {0, 0, 0, 0};
+    m_tmp->read(word, 4);
+    adl::DeviceUtils::waitForCompletion(device);
+    u32 kept = 0;
+    memcpy(&kept, word, 4);
+    return (int)kept;
+}
+
+#define TAHOE_SETOP(K, V)                                                                                                           \
+    template int Pprims::setOp<K, V>(const adl::Device*, int, const adl::Buffer<K>&, const adl::Buffer<V>*, const adl::Buffer<K>&, \
+                                     const adl::Buffer<V>*, adl::Buffer<K>&, adl::Buffer<V>*, adl::Buffer<u32>*, int, int, bool);
+#define TAHOE_SETOP_KEY(K) \
+    TAHOE_SETOP(K, int) TAHOE_SETOP(K, float) TAHOE_SETOP(K, long long) TAHOE_SETOP(K, double) TAHOE_SETOP(K, u32) TAHOE_SETOP(K, u64)
+TAHOE_SETOP_KEY(int)
+TAHOE_SETOP_KEY(float)
+TAHOE_SETOP_KEY(long long)
+TAHOE_SETOP_KEY(double)
+TAHOE_SETOP_KEY(u32)
+TAHOE_SETOP_KEY(u64)
+#undef TAHOE_SETOP_KEY
+#undef TAHOE_SETOP
 
 #define TAHOE_TYPED(T)                                                                                                              \
     void Pprims::sortKeys(const adl::Device* device, const adl::Buffer<T>& inout, int n, bool descending)                         \

@@ -6,15 +6,19 @@ is followed -- while later sorts are already queued -- by the LDS-order self-tes
 behaviour "sort.rank" = 1 rests on, adlhip_selftest_lds_order), and one size class reaches past 64 Mi keys (the
 pointer-store write-out).  Half of the sorts take the automatic choice (mid-size sort, large sort with its look-back /
 cursor passes and the safety net inside its offsets kernel), with "sort.msd2" forced on for some and keys shifted down by a random number of bits.
-One kind in eight is a stream compaction between the sorts (a stable partition of the keys by a comparison, values and positions along),
+One kind in nine is a stream compaction between the sorts (a stable partition of the keys by a comparison, values and positions along),
 one a histogram (range or bincount, random key type, bins and grid knob, the LDS and the sorted path), one a merge (the keys cut in
-two, each part sorted by the library as int32 or float32 keys in either order, then merged with positions and 8-byte values along).
+two, each part sorted by the library as int32 or float32 keys in either order, then merged with positions and 8-byte values along),
+one a set operation (the keys folded onto a random number of distinct values and cut in two, each part sorted by the library, then
+a random one of the four operations with positions and 8-byte values along, checked against tests/setop_oracle.py).
    python tools/stress.py [--seconds 60]"""
 import argparse, os, sys, time
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import oracle
 import ctypes
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+import setop_oracle   # the numpy oracle of the set operation tests
 from oclradixsort_amd import Buffer, DeviceUtils, Pprims, _lib
 from oclradixsort_amd._lib import check
 ap = argparse.ArgumentParser(); ap.add_argument("--seconds", type=float, default=60.0)
@@ -35,7 +39,7 @@ def checks(a):
     return int(a64.sum(dtype=np.uint64)), int(np.bitwise_xor.reduce(a64)) if a.size else 0
 while time.time() < t_end and it < args.stop_after:
     it += 1
-    kind = rng.choice(["u32", "kv", "u64", "soa", "soaw", "compact", "hist", "merge"])
+    kind = rng.choice(["u32", "kv", "u64", "soa", "soaw", "compact", "hist", "merge", "setop"])
     n = int(2 ** rng.uniform(10, 25.5)) + int(rng.randint(0, 1000))
     if it % 7 == 0: n = int(2 ** rng.uniform(21, 26.3))   # more of the large sort's range
     if kind == "u32" and it % 23 == 0: n = (1 << 26) + int(rng.randint(1, 1 << 22))     # past 256 MiB: pointer stores
@@ -54,7 +58,7 @@ while time.time() < t_end and it < args.stop_after:
             else: rng.randint(1, 4)
         continue
     if verbose: print("it %d %s n=%d algo=%d bits=%d tile=%d msd2=%d dist=%s shift=%d" % (it, kind, n, algo, bits, tile, msd2_mode, dist, shift), flush=True)
-    if kind in ("u32", "soa", "kv", "soaw", "compact", "hist", "merge"):
+    if kind in ("u32", "soa", "kv", "soaw", "compact", "hist", "merge", "setop"):
         k = oracle.keys_u32(n, seed=it)
         if dist == "heavy": k = np.where(np.arange(n) % 10 != 0, (k >> np.uint32(8)) | np.uint32(0x37000000), k).astype(np.uint32)
         elif dist == "vals4096": k = (k >> np.uint32(20)) * np.uint32(0x00100801)
@@ -126,6 +130,28 @@ while time.time() < t_end and it < args.stop_after:
         order = np.argsort(~code if desc else code, kind="stable")
         assert np.array_equal(gi, order) and np.array_equal(ok, cat[order]) and np.array_equal(ov, np.concatenate([sva, svb])[order]), (it, kind, n, na, dt, desc, dist)
         assert np.array_equal(np.sort(ov), np.sort(v)), (it, kind, "the values are not a permutation")
+    elif kind == "setop":   # a set operation on two sorted parts of the keys, against the oracle of the tests
+        sr = np.random.RandomState(args.seed + 13 * it)
+        n = min(n, 1 << 22)
+        na = int(sr.choice([0, 1, n // 2, n - 1, n, int(sr.randint(0, n + 1))])); nb = n - na
+        tname, desc, opname = ["i32", "f32"][sr.randint(0, 2)], bool(sr.randint(0, 2)), setop_oracle.OPS[sr.randint(0, 4)]
+        dt = {"i32": np.int32, "f32": np.float32}[tname]
+        k = k[:n] % np.uint32(sr.choice([1, 3, 1000, max(n // 2, 1), 1 << 31]))   # from one run to hardly a key shared
+        d.setParam("debug.setop_grid", int(sr.choice([0, 0, 1, 7, 300])))
+        cap = n if opname in ("union", "symmetric_difference") else na
+        ka = Buffer(d, max(na, 1), dt); kb = Buffer(d, max(nb, 1), dt); ko = Buffer(d, max(cap, 1), dt)
+        va = Buffer(d, max(na, 1), np.uint64); vb = Buffer(d, max(nb, 1), np.uint64); vo = Buffer(d, max(cap, 1), np.uint64)
+        v = np.arange(n, dtype=np.uint64) * np.uint64(0x9E3779B97F4A7C15)
+        if na: ka.write(k[:na].view(dt)); va.write(v[:na]); p.sortPairs(d, ka, va, na, descending=desc)
+        if nb: kb.write(k[na:n].view(dt)); vb.write(v[na:n]); p.sortPairs(d, kb, vb, nb, descending=desc)
+        r = p.setOp(d, opname, ka, kb, ko, na, nb, descending=desc, valuesA=va, valuesB=vb, valuesOut=vo, indexOut=True)
+        sa, sb, sva, svb = ka.toHost()[:na].view(np.uint32), kb.toHost()[:nb].view(np.uint32), va.toHost()[:na], vb.toHost()[:nb]
+        cnt = int(r.count.toHost()[0])
+        ok, ov, gi = ko.toHost().view(np.uint32)[:cnt], vo.toHost()[:cnt], r.index.toHost()[:cnt]
+        for b in (ka, kb, ko, va, vb, vo, r.index, r.count): b.release()
+        d.setParam("debug.setop_grid", 0)
+        wi, wk, wv, wc = setop_oracle.setop_oracle(sa, sb, tname, setop_oracle.OP_IDS[opname], 1 if desc else 0, sva, svb)
+        assert cnt == wc and np.array_equal(gi, wi) and np.array_equal(ok, wk) and np.array_equal(ov, wv), (it, kind, opname, n, na, tname, desc, dist)
     elif kind == "hist":   # a histogram of the keys: mode, type, bins and grid knob from a generator of this iteration's own
         hr = np.random.RandomState(args.seed + 7 * it)
         n = min(n, 1 << 24)
