@@ -224,6 +224,16 @@ public:
               const adl::Buffer<V>* valuesB, adl::Buffer<K>& keysOut, adl::Buffer<V>* valuesOut, adl::Buffer<u32>* indexOut, int na, int nb,
               bool descending = false);
 
+    // sorted search: posOut[i], i < n = where needles[i] would be inserted among the first m keys of sortedKeys -- sorted in the order
+    // of sortKeys(descending) -- to keep them sorted: the number of keys in front of the needle (right: in front of it or equal to it)
+    // in that order, always in [0, m].  thrust lower_bound / upper_bound, numpy.searchsorted.  K: int, float, long long, double, u32,
+    // u64; floats in totalOrder, equal means equal bits.  The inputs are left intact and may be the same Buffer; posOut may be
+    // neither.  A sequence that is not sorted gives unspecified positions in [0, m].  Enqueues and returns.  A TYPE_HOST device runs a
+    // plain binary search per needle
+    template <typename K>
+    void searchSorted(const adl::Device* device, const adl::Buffer<K>& sortedKeys, const adl::Buffer<K>& needles, adl::Buffer<u32>& posOut, int m,
+                      int n, bool descending = false, bool right = false);
+
 private:
     template <typename T> int uniqueTyped(const adl::Device* device, const adl::Buffer<T>& keys, adl::Buffer<T>& uniqueOut, adl::Buffer<u32>& countsOut,
                                           int n, bool descending);

@@ -693,6 +693,49 @@ int adlhip_set_op_typed(adlhip_device* dev, int key_type, int order, int op,
                         int value_bytes, void* d_keys_out_or_null, void* d_vals_out_or_null, uint32_t* d_index_out_or_null,
                         uint32_t* d_num_out, void* d_work, size_t work_bytes);
 
+/* ---- sorted search (no reference counterpart) ---- */
+
+/* The vectorised binary search: for every one of n needles its lower or upper bound in a sequence of m elements that is already
+ * sorted.  thrust's lower_bound / upper_bound on vectors of values, numpy.searchsorted, torch.searchsorted and torch.bucketize.
+ *
+ * Order.  d_sorted (m keys) is sorted in `order` as adlhip_merge_typed asks.  Precisely, with c(x) = the code
+ *   adlhip_key_encode(key_type, order) gives for x -- integers by value, floats by IEEE totalOrder on bits (-NaN < -inf < ... < -0 <
+ *   +0 < ... < +inf < +NaN: -0 is below +0 and NaNs sit at the two ends), descending the complement -- the codes of its elements are
+ *   non-decreasing as unsigned numbers.
+ * Result.
+ *     side ADLHIP_SEARCH_LEFT    d_pos_out[i] = the number of elements of d_sorted whose code is below c(d_needles[i])
+ *     side ADLHIP_SEARCH_RIGHT   d_pos_out[i] = the number of elements whose code is below or equal to it
+ *   always in [0, m]: where the needle would be inserted in front of (LEFT) or behind (RIGHT) its equals to keep the sequence sorted.
+ *   All six key types and both orders.
+ * Relation to the merge.  For sorted A and B, adlhip_merge_typed puts A[i] at i + LEFT_B(A[i]) and B[j] at j + RIGHT_A(B[j]), where
+ *   LEFT_B / RIGHT_A are this search in B / in A: ties take A.
+ *
+ * Contract.  m < 2^32 and n < 2^32.  The inputs are never written; d_sorted and d_needles may overlap or be the same array.
+ * d_pos_out overlaps no input.  d_needles and d_pos_out are 16-byte aligned.  d_sorted needs only the alignment of its element (4
+ * or 8 bytes), because it is gathered, never streamed: a view that starts at any element of a larger array is searched where it
+ * lies.  Every one of the n positions is written and nothing beyond them.  n == 0 succeeds and enqueues nothing.  m == 0 writes n
+ * zeros, and d_sorted is then not looked at (it may be NULL).  A NULL pointer, a misaligned pointer, an overlap of d_pos_out with
+ * an input, an unknown key_type, order or side, and m or n >= 2^32 fail before anything is enqueued, each with a message that
+ * names the argument.  There is no work buffer: the call keeps no state, nothing is remembered between calls.  The call enqueues
+ * and returns: nothing data-dependent reaches the host (the launch grid depends on n and m alone).  The kernel does not wait on
+ * another workgroup and uses no atomic to global memory.
+ *
+ * A sequence that is NOT sorted: the positions are unspecified, but each lies in [0, m], the call succeeds and terminates, every
+ * read stays inside [d_sorted, d_sorted + m) and the n needles, and every write inside the n positions (search_kernels.hpp proves
+ * it: every probe index is clamped to the table or the sequence, whatever the comparisons answer, and a position only ever moves
+ * to a count that is at most the length searched).
+ *
+ * One launch over tiles of ADLHIP_SEARCH_TILE needles, 8 consecutive needles per thread searched side by side.  Every workgroup
+ * first puts a table of at most C = 4096 codes in LDS ("debug.search_lds_keys" reports C): for m <= C the whole sequence, and the
+ * search ends there; for larger m the last element of every block of ceil(m / C) elements, and the search goes on inside the one
+ * block the table points to with a branch-free search on global memory whose probe index is clamped to [0, m). */
+#define ADLHIP_SEARCH_TILE 2048
+#define ADLHIP_SEARCH_LEFT 0
+#define ADLHIP_SEARCH_RIGHT 1
+int adlhip_search_sorted_typed(adlhip_device* dev, int key_type, int order, int side,
+                               const void* d_sorted, size_t m, const void* d_needles, size_t n,
+                               uint32_t* d_pos_out);
+
 /* ---- segments finished in LDS (no reference counterpart) ------------------------------------- */
 
 /* Sorts, stably and in place, every segment [d_seg_start[s], d_seg_start[s + 1]) of an array of u32 keys
@@ -871,6 +914,12 @@ int adlhip_generate_keys(adlhip_device* dev, int elem_kind, void* dptr, size_t n
  *                      change nothing); tests set it to make few workgroups take many tiles in turns.  The result does not depend on it
  *   "debug.setop_grid" workgroups the count and emit kernels of adlhip_set_op_typed are launched with at most (0 [default]: 8 per CU;
  *                      larger values change nothing); tests set it to make few workgroups take many tiles.  The result does not depend on it
+ *   "debug.search_grid" workgroups the kernel of adlhip_search_sorted_typed is launched with at most (0 [default]: 8 per CU, and never
+ *                      more than tiles of needles; larger values change nothing); tests set it to make few workgroups take many
+ *                      tiles.  The result does not depend on it
+ *   "debug.search_lds_keys" the capacity C of the table adlhip_search_sorted_typed keeps in LDS, in codes (2 .. 4096, default 4096; 0
+ *                      sets the default); tests lower it to reach the two-level path and long searches in global memory with a
+ *                      short sequence.  adlhip_get_param reports the capacity in force.  The result does not depend on it
  *   "debug.histogram_lds_bins" the largest num_bins for which adlhip_bincount_typed takes the LDS path (1 .. 8192, default 8192; 0
  *                      sets the default); tests lower it to reach the sorted path with few keys.  adlhip_get_param reports the limit
  *   "debug.persist_grid" workgroups both persistent passes of the large keys-only sort (cursor form) are launched with, rounded up to

@@ -1,7 +1,7 @@
 // adlhip_internal.hpp -- what the library's three host units share.  handle.hip defines the runtime under everything: the error text,
 // the handle (create, teardown, sync, buffers, map / unmap, events, profiling), the probes and the knob table.  adlhip.hip defines
 // the sorts, the scan and the partitions, and what a handle owns for them (sort_state_create / sort_state_destroy, the idle table).
-// primitives.hip defines what is built on top of the sorts (typed sort, top-k, unique, reduce by key, scans, compaction, histograms, merges, set operations).
+// primitives.hip defines what is built on top of the sorts (typed sort, top-k, unique, reduce by key, scans, compaction, histograms, merges, set operations, sorted search).
 // Not installed; nothing here is ABI.
 #pragma once
 #include "../../include/adlhip.h"
@@ -19,6 +19,9 @@ namespace adlhip_internal {
 // the largest table of the histogram's LDS path: the default and the ceiling of "debug.histogram_lds_bins".  primitives.hip asserts
 // that it is what the count kernel's LDS is sized for (adlhip::kHistLdsBins, histogram_kernels.hpp)
 constexpr int kHistogramLdsBinsMax = 8192;
+// the table of the sorted search in LDS: the default and the ceiling of "debug.search_lds_keys".  primitives.hip asserts that it is the
+// kernel's (adlhip::kSearchLdsKeys, search_kernels.hpp)
+constexpr int kSearchLdsKeysMax = 4096;
 struct ProfEntry {
     uint64_t launches = 0;
     double total_ms = 0.0;
@@ -70,6 +73,7 @@ struct adlhip_device {
     int histogram_grid = 0;   // "debug.histogram_grid": workgroups of the histogram's count kernel at most (0: hist_grid_cap)
     int merge_grid = 0;       // "debug.merge_grid": workgroups of the merge's tile kernel at most (0: kMergeWgsPerCu per CU)
     int setop_grid = 0;       // "debug.setop_grid": workgroups of the set operations' count and emit kernels at most (0: kSetopWgsPerCu per CU)
+    int search_grid = 0;      // "debug.search_grid": workgroups of the sorted search at most (0: kSearchWgsPerCu per CU)
     int persist_grid = 0;     // "debug.persist_grid": workgroups of the large sort's persistent passes, rounded up to a
                               // multiple of 8 (0: two per CU)
     // (with a rule of their own)
@@ -80,6 +84,7 @@ struct adlhip_device {
     int partition_lookback = 1;   // "partition.lookback": the MSB partition as one look-back pass where it pays (0: always three kernels)
     int profile = 0;          // "profile": an event pair around every launch
     int histogram_lds_bins = adlhip_internal::kHistogramLdsBinsMax;   // "debug.histogram_lds_bins": bincount takes the LDS path up to this many bins
+    int search_lds_keys = adlhip_internal::kSearchLdsKeysMax;   // "debug.search_lds_keys": codes of the sorted search's table in LDS at most
     int resident_wgs = 0;     // "debug.resident_wgs": workgroups of <= 80 KiB LDS / 512 threads that are certainly resident at once (2 per
                               // CU); the paths whose kernels hold a grid-wide barrier over 256 workgroups are taken only when this is >= 256
     int rank_mode = 1;        // "sort.rank": 1 = lane-ordered DS atomic ranking (needs lds_ordered), 0 = ballot match

@@ -192,6 +192,7 @@ struct Knob {
 constexpr int kNoMax = INT_MAX;
 int as_flag(adlhip_device*, int* v) { *v = *v ? 1 : 0; return ADLHIP_SUCCESS; }
 static_assert(kHistogramLdsBinsMax == 8192, "the refusal text of debug.histogram_lds_bins");
+static_assert(kSearchLdsKeysMax == 4096, "the refusal text of debug.search_lds_keys");
 const Knob kKnobs[] = {
     {"sort.algo", &adlhip_device::sort_algo, -1, 1, "sort.algo must be -1, 0 or 1", nullptr},
     {"sort.mid", &adlhip_device::mid_path, 0, 3,
@@ -217,6 +218,7 @@ const Knob kKnobs[] = {
     {"debug.histogram_grid", &adlhip_device::histogram_grid, 0, kNoMax, "debug.histogram_grid must be >= 0", nullptr},
     {"debug.merge_grid", &adlhip_device::merge_grid, 0, kNoMax, "debug.merge_grid must be >= 0", nullptr},
     {"debug.setop_grid", &adlhip_device::setop_grid, 0, kNoMax, "debug.setop_grid must be >= 0", nullptr},
+    {"debug.search_grid", &adlhip_device::search_grid, 0, kNoMax, "debug.search_grid must be >= 0", nullptr},
     {"debug.persist_grid", &adlhip_device::persist_grid, 0, 4096, "debug.persist_grid must be in [0, 4096]", nullptr},
     // ---- with a rule of their own
     {"sort.digit_bits", &adlhip_device::digit_bits, 0, 0, nullptr,
@@ -232,6 +234,11 @@ const Knob kKnobs[] = {
     {"debug.histogram_lds_bins", &adlhip_device::histogram_lds_bins, 0, kHistogramLdsBinsMax,
      "debug.histogram_lds_bins must be in [1, 8192], or 0 for the default",
      [](adlhip_device*, int* v) { if (!*v) *v = kHistogramLdsBinsMax; return ADLHIP_SUCCESS; }},
+    {"debug.search_lds_keys", &adlhip_device::search_lds_keys, 0, kSearchLdsKeysMax,
+     "debug.search_lds_keys must be in [2, 4096], or 0 for the default", [](adlhip_device*, int* v) {
+         if (*v == 1) return fail("debug.search_lds_keys must be in [2, 4096], or 0 for the default");
+         if (!*v) *v = kSearchLdsKeysMax;
+         return ADLHIP_SUCCESS; }},
     // (what the paths with a grid-wide barrier may count on; 0 = the device's own answer again.  Tests stand in for a small partition with it)
     {"debug.resident_wgs", &adlhip_device::resident_wgs, 0, kNoMax, "debug.resident_wgs must be >= 0",
      [](adlhip_device* d, int* v) { if (!*v) *v = d->resident_wgs_device; return ADLHIP_SUCCESS; }},

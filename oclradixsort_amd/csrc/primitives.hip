@@ -1,5 +1,5 @@
 // primitives.hip -- the host side of what is built on top of the sorts: typed keys and argsort, top-k, row-wise top-k, unique /
-// run-length encode, reduce by key, typed scans, stream compaction, histograms, merges, set operations.  No reference counterpart.  It reaches the sorts through adlhip_internal.hpp alone (sort_elements,
+// run-length encode, reduce by key, typed scans, stream compaction, histograms, merges, set operations, sorted search.  No reference counterpart.  It reaches the sorts through adlhip_internal.hpp alone (sort_elements,
 // sort_work_bytes, soa_wide_layout) and never sees their kernels.
 #include "adlhip_internal.hpp"
 
@@ -23,9 +23,10 @@
 #include "histogram_kernels.hpp"
 #include "merge_kernels.hpp"
 #include "setop_kernels.hpp"
+#include "search_kernels.hpp"
 
 // instantiated in kernels_select.hip / kernels_toprows.hip / kernels_unique.hip / kernels_reduce.hip / kernels_scan.hip /
-// kernels_compact.hip / kernels_histogram.hip / kernels_merge.hip / kernels_setop.hip; here they are only declared
+// kernels_compact.hip / kernels_histogram.hip / kernels_merge.hip / kernels_setop.hip / kernels_search.hip; here they are only declared
 #ifndef ADLHIP_SINGLE_TU
 #define X(...) extern template __global__ __VA_ARGS__;
 #include "select_kernels.inc"
@@ -37,6 +38,7 @@
 #include "histogram_kernels.inc"
 #include "merge_kernels.inc"
 #include "setop_kernels.inc"
+#include "search_kernels.inc"
 #undef X
 #endif
 
@@ -1040,6 +1042,48 @@ int setop_stage(adlhip_device* d, adlhip::RedCodec codec, uint32_t op, const K* 
     });
 }
 
+// ---- sorted search (search_kernels.hpp) ----------------------------------------------------------------------
+static_assert(ADLHIP_SEARCH_TILE == adlhip::kRedTile, "the header states the tile of the search");
+static_assert(ADLHIP_SEARCH_LEFT == adlhip::kSearchLeft && ADLHIP_SEARCH_RIGHT == adlhip::kSearchRight, "the header states the sides");
+static_assert(kSearchLdsKeysMax == (int)adlhip::kSearchLdsKeys, "\"debug.search_lds_keys\" may ask for no more codes than the kernel's table holds");
+// grid per CU at most ("debug.search_grid" lowers it): what the LDS of a full table of 4-byte codes and the registers admit; the
+// search is chains of dependent reads that only other waves hide.  Never more workgroups than tiles of needles: a workgroup does not
+// gather a table for less than one tile
+constexpr int kSearchWgsPerCu = 8;
+constexpr size_t kSearchMaxElems = 0xFFFFFFFFull;   // m and n: positions fit a dword
+
+uint32_t search_top_step(uint32_t len)   // the largest power of two <= len; 0 for 0
+{
+    if (len == 0) return 0u;
+    uint32_t top = 1u;
+    while ((uint64_t)top * 2 <= len) top *= 2;
+    return top;
+}
+
+// the bounds of n > 0 needles in m >= 0 sorted elements
+template <typename U>
+int search_stage(adlhip_device* d, adlhip::RedCodec codec, int side, const U* sorted, size_t m, const U* needles, size_t n, uint32_t* pos_out)
+{
+    const size_t cap_keys = (size_t)d->search_lds_keys;   // C, or what the knob lowered it to (>= 2)
+    adlhip::SearchArgs a;
+    a.m = (uint32_t)m;
+    a.stride = (uint32_t)std::max<size_t>(1, (m + cap_keys - 1) / cap_keys);
+    a.samples = (uint32_t)((m + a.stride - 1) / a.stride);   // <= cap_keys
+    a.top_s = search_top_step(a.samples);
+    a.top_g = search_top_step(a.stride);
+    const ChunkSplit cs = chunk_split(d, n, (size_t)adlhip::kRedTile, kSearchWgsPerCu, d->search_grid);
+    const size_t lds = align_up((size_t)a.samples * sizeof(U), 16);   // (at most 32 KiB)
+    static const char* const kName[2][2] = {{"search_left_k32", "search_left_k64"}, {"search_right_k32", "search_right_k64"}};
+    return launch(d, kName[side][sizeof(U) == 8], [&] {
+        if (side == ADLHIP_SEARCH_LEFT)
+            hipLaunchKernelGGL((adlhip::search_sorted_kernel<U, adlhip::kSearchLeft>), dim3(cs.wgs), dim3(adlhip::kSelNT), lds, d->stream, sorted, a,
+                               needles, (uint32_t)n, cs.tiles, cs.tiles_per_wg, codec, pos_out);
+        else
+            hipLaunchKernelGGL((adlhip::search_sorted_kernel<U, adlhip::kSearchRight>), dim3(cs.wgs), dim3(adlhip::kSelNT), lds, d->stream, sorted,
+                               a, needles, (uint32_t)n, cs.tiles, cs.tiles_per_wg, codec, pos_out);
+    });
+}
+
 }  // namespace
 
 extern "C" {
@@ -1543,6 +1587,26 @@ int adlhip_set_op_typed(adlhip_device* d, int key_type, int order, int op, const
     return ADLHIP_BY_WIDTH(t.bytes, K, ADLHIP_BY_WIDTH(value_bytes ? value_bytes : 4, V, setop_stage<K, V>(d, codec, (uint32_t)op,
                            (const K*)keys_a, (const V*)vals_a, na, (const K*)keys_b, (const V*)vals_b, nb, cap, (K*)keys_out, (V*)vals_out,
                            index_out, num_out, work)));
+}
+
+// ---- sorted search --------------------------------------------------------------------------------------
+int adlhip_search_sorted_typed(adlhip_device* d, int key_type, int order, int side, const void* sorted, size_t m, const void* needles, size_t n,
+                               uint32_t* pos_out)
+{
+    const char* what = "search sorted";
+    TypeInfo t;
+    if (bind(d) || key_type_info(key_type, order, &t)) return ADLHIP_FAILURE;
+    if (side != ADLHIP_SEARCH_LEFT && side != ADLHIP_SEARCH_RIGHT)
+        return fail("%s: side must be ADLHIP_SEARCH_LEFT (0) or ADLHIP_SEARCH_RIGHT (1), got %d", what, side);
+    if (m > kSearchMaxElems) return fail("%s: m = %zu exceeds the supported maximum %zu", what, m, (size_t)kSearchMaxElems);
+    if (n > kSearchMaxElems) return fail("%s: n = %zu exceeds the supported maximum %zu", what, n, (size_t)kSearchMaxElems);
+    if (n == 0) return ADLHIP_SUCCESS;
+    const size_t kb = (size_t)t.bytes;
+    if (merge_check_buffers(what, {{m ? sorted : nullptr, m * kb, "d_sorted", m != 0, kb}, {needles, n * kb, "d_needles", true, 16}},
+                            {{pos_out, n * 4, "d_pos_out", true, 16}}))
+        return ADLHIP_FAILURE;
+    const adlhip::RedCodec codec = {(uint32_t)t.kind, (uint32_t)order};
+    return ADLHIP_BY_WIDTH(t.bytes, U, search_stage<U>(d, codec, side, (const U*)sorted, m, (const U*)needles, n, pos_out));
 }
 
 }  // extern "C"

@@ -22,6 +22,7 @@
     p.binCount(device, keys, n, num_bins)                  # -> Buffer(uint32): the keys per value 0 .. num_bins - 1
     p.mergeKeys(device, a, b, out, na, nb)                 # the stable merge of two sorted key Buffers (mergePairs: with values)
     p.setOp(device, "intersection", a, b, out, na, nb)     # -> SetOpResult: also "union", "difference", "symmetric_difference"
+    p.searchSorted(device, sortedKeys, needles, posOut, m, n)   # every needle's lower (right=True: upper) bound in m sorted keys
 
 Like the reference object it owns lazily grown device scratch (m_u32WorkBuffer[0] = ping-pong data
 buffer, m_u32WorkBuffer[1] = histogram table; Pprims.h:44-45, Pprims.cpp:226-232, :332-337) and must be
@@ -827,6 +828,35 @@ class Pprims:
                 buf.release()
             raise
         return SetOpResult(out, valuesOut, idx, countOut)
+
+    # -- sorted search (no reference counterpart; include/adlhip.h adlhip_search_sorted_typed)
+    def searchSorted(self, device, sortedKeys, needles, posOut, m, n, descending=False, right=False):
+        """posOut[i], i < n = where needles[i] would be inserted among the first m keys of `sortedKeys` -- a Buffer of one of the six key
+        types, sorted in the order of sortKeys(descending) -- to keep them sorted: the number of keys that come before the needle
+        (right=True: before it or equal to it) in that order, always in [0, m].  numpy.searchsorted with side 'left' / 'right', in
+        the order of the typed sorts: floats by totalOrder (-0 before +0, NaNs by sign at the two ends), equal means equal bits.
+        `needles` is a Buffer of the same type, posOut a uint32 Buffer of n elements at least; the caller sizes them.  The inputs
+        are left intact and may be the same Buffer; posOut may be neither.  A sequence that is not sorted gives unspecified
+        positions in [0, m], never an access outside the Buffers.  Enqueues and returns."""
+        what = "searchSorted"
+        if device is None:
+            raise AdlHipError("%s needs a device" % what)
+        if sortedKeys is None or needles is None or posOut is None:
+            raise AdlHipError("%s: sortedKeys, needles and posOut are required (an empty sequence with m = 0)" % what)
+        kt = self._key_type(sortedKeys, what)
+        if np.dtype(needles.dtype) != np.dtype(sortedKeys.dtype):
+            raise AdlHipError("%s: sortedKeys is %s, needles %s" % (what, sortedKeys.dtype, needles.dtype))
+        m, n = int(m), int(n)
+        for name, buf, k in (("m", sortedKeys, m), ("n", needles, n)):
+            if k < 0 or buf.getSize() < k:
+                raise AdlHipError("%s: %s = %d outside [0, %d]" % (what, name, k, buf.getSize()))
+            if k >= 1 << 32:
+                raise AdlHipError("%s: %s = %d; fewer than 2^32 elements" % (what, name, k))
+        if not hasattr(posOut, "getSize") or np.dtype(posOut.dtype) != np.uint32 or posOut.getSize() < n:
+            raise AdlHipError("%s: posOut must be a uint32 buffer of %d elements" % (what, n))
+        check(_lib.load().adlhip_search_sorted_typed(device._h, kt, 1 if descending else 0, 1 if right else 0, sortedKeys.ptr(), m,
+                                                     needles.ptr(), n, posOut.ptr()), what)
+        return posOut
 
     def copy(self, device, dst, src, n):
         """Pprims::copy (Pprims.cpp:31-67, commented out in the reference): first n elements of src -> dst."""

@@ -18,6 +18,7 @@ back-end on torch's own stream.
     c = s.bincount(t); c = s.histogram(t, edges); c = s.histc(t, 100, 0.0, 1.0)  # torch.bincount / numpy.histogram(t, edges)[0] / the same on linspace edges
     m = s.merge(a, b); m, v, i = s.merge(a, b, values=(va, vb), return_indices=True)   # torch.sort(torch.cat((a, b)), stable=True) of sorted a, b
     i = s.intersect(a, b); u = s.union(a, b); d = s.difference(a, b); x = s.symmetric_difference(a, b)   # of sorted a, b: numpy.intersect1d / union1d / setdiff1d / setxor1d
+    pos = s.searchsorted(sorted_t, values, right=False); b = s.bucketize(values, boundaries)   # torch.searchsorted / torch.bucketize on a 1-D sorted tensor
     s.close()
 
 Always out of place and always stable.  The ONE difference from `torch.sort(t, stable=True)`: floats are ordered by
@@ -636,6 +637,54 @@ class TorchSorter:
         """numpy.setxor1d(a, b, assume_unique=True) of sorted 1-D tensors without duplicates; with duplicates thrust's
         set_symmetric_difference: |m - n| copies, the last of a's or of b's.  Everything else as intersect()."""
         return self._set_op("symmetric_difference", "symmetric_difference", a, b, descending, values, return_indices)
+
+    def searchsorted(self, sorted_sequence, values, right=False, side=None, out_int32=False, descending=False):
+        """What torch.searchsorted(sorted_sequence, values, right=right, side=side, out_int32=out_int32) returns for a 1-D
+        `sorted_sequence`: for every element of `values` -- a tensor of any shape and the same dtype, or a Python scalar -- the index
+        in front of which it would be inserted to keep the sequence sorted: in front of its equals (left, the default) or behind
+        them (right=True or side="right").  The result has the shape of `values` and is int64, or int32 with out_int32.
+        `sorted_sequence` is contiguous at any element offset (t[1:] is searched where it lies, a strided view is copied) and sorted
+        ascending, or descending with descending=True (which torch does not offer).  It differs from torch only on -0 against +0
+        and on NaN: the order is that of sort(), floats by totalOrder, so the sequence must be sorted with -0 before +0 and NaNs by
+        sign at the two ends, -0 is searched as a value below +0, and a NaN needle finds the NaNs of its own sign and payload.
+        A sequence that is not sorted gives unspecified indices in [0, len].  Not offered: `sorter=` and a batched N-D
+        `sorted_sequence`; for those the caller sorts first, or loops over the rows.  Nothing reaches the host."""
+        seq = self._merge_input(sorted_sequence, "searchsorted")
+        if side is not None:
+            if side not in ("left", "right"):
+                raise ValueError("TorchSorter.searchsorted: side must be 'left' or 'right', got %r" % (side,))
+            if side == "left" and right:
+                raise ValueError("TorchSorter.searchsorted: side is 'left' but right is True")
+            right = side == "right"
+        if not isinstance(values, torch.Tensor):
+            if isinstance(values, (bool, str)) or not isinstance(values, (int, float)):
+                raise TypeError("TorchSorter.searchsorted: values is a tensor or a Python number, got %s" % type(values).__name__)
+            values = torch.tensor(values, dtype=seq.dtype, device=seq.device)
+        if values.dtype != seq.dtype:
+            raise TypeError("TorchSorter.searchsorted: sorted_sequence is %s, values %s" % (seq.dtype, values.dtype))
+        if values.device != self.torch_device:
+            raise ValueError("TorchSorter: tensor is on %s, the sorter on %s" % (values.device, self.torch_device))
+        if torch.cuda.current_stream(self.torch_device).cuda_stream != self.raw_stream:
+            raise RuntimeError("TorchSorter: bound to the stream that was current at construction; another stream is current now")
+        m, n = seq.numel(), values.numel()
+        if m >= 1 << 32 or n >= 1 << 32:
+            raise ValueError("TorchSorter: fewer than 2^32 elements")
+        pos32 = torch.empty(n, dtype=torch.int32, device=seq.device)   # uint32 positions in an int32 tensor
+        if n:
+            needles = self._aligned(values.contiguous().view(-1))
+            kdt = _NP_DTYPE[seq.dtype]
+            self.pprims.searchSorted(self.device, self._wrap(seq, kdt), self._wrap(needles, kdt), self._wrap(pos32, np.uint32), m, n,
+                                     descending=bool(descending), right=bool(right))
+            self.device.checkFault()
+        out = pos32 if out_int32 else pos32.to(torch.int64) & 0xffffffff
+        return out.view(values.shape)
+
+    def bucketize(self, input, boundaries, right=False, out_int32=False):
+        """What torch.bucketize(input, boundaries, right=right, out_int32=out_int32) returns: searchsorted(boundaries, input) -- for
+        every element of `input` (any shape, or a Python scalar) the index of its bucket among the 1-D sorted `boundaries`: with
+        right=False boundaries[i - 1] < x <= boundaries[i], with right=True boundaries[i - 1] <= x < boundaries[i].  Everything else,
+        the difference from torch on -0 and NaN included, as searchsorted()."""
+        return self.searchsorted(boundaries, input, right=right, out_int32=out_int32)
 
     def sort(self, t, descending=False):
         """(values, indices) like torch.sort(t, descending=descending, stable=True); indices are int64."""

@@ -8,7 +8,8 @@
 // adlhip_scan_by_key, or a plain loop, left to right.  Pprims::compactFlagged / compactIf: adlhip_compact_flagged /
 // adlhip_compact_if_typed (they wait for the count), or a plain loop.  Pprims::histogramRange / binCount:
 // adlhip_histogram_range_typed / adlhip_bincount_typed, or a plain loop.  Pprims::mergeKeys / mergePairs: adlhip_merge_typed, or a
-// plain two-pointer loop in which a tie takes the first input.  Pprims::setOp: adlhip_set_op_typed (it waits for the count), or
+// plain two-pointer loop in which a tie takes the first input.  Pprims::searchSorted: adlhip_search_sorted_typed, or a binary search
+// per needle.  Pprims::setOp: adlhip_set_op_typed (it waits for the count), or
 // thrust's two-pointer loops.
 #include <Tahoe/ParallelPrimitives/Pprims.h>
 
@@ -912,6 +913,56 @@ TAHOE_SETOP_KEY(u32)
 TAHOE_SETOP_KEY(u64)
 #undef TAHOE_SETOP_KEY
 #undef TAHOE_SETOP
+
+// ---- sorted search: adlhip_search_sorted_typed, or a plain binary search per needle ----
+template <typename K>
+void Pprims::searchSorted(const adl::Device* device, const adl::Buffer<K>& sortedKeys, const adl::Buffer<K>& needles, adl::Buffer<u32>& posOut, int m,
+                          int n, bool descending, bool right)
+{
+    ADLASSERT(m >= 0 && n >= 0);
+    if (m < 0 || n <= 0) return;
+    ADLASSERT(device != 0);
+    ADLASSERT((adl::u64)m <= sortedKeys.getSize() && (adl::u64)n <= needles.getSize() && (adl::u64)n <= posOut.getSize());
+    if (!onDevice(device)) {
+        ADLASSERT(device->getType() == adl::TYPE_HOST);   // a HIP device never falls back to the CPU
+        if (device->getType() != adl::TYPE_HOST) return;
+        K* s = m ? sortedKeys.getHostPtr(m) : 0;
+        K* x = needles.getHostPtr(n);
+        u32* pos = posOut.getHostPtr(n);
+        adl::DeviceUtils::waitForCompletion(device);
+        for (int i = 0; i < n; ++i) {   // the first position whose element is not below (right: is above) the needle
+            int lo = 0, hi = m;
+            while (lo < hi) {
+                const int mid = lo + (hi - lo) / 2;
+                const bool before = right ? !(ordinal(x[i], descending) < ordinal(s[mid], descending))
+                                          : ordinal(s[mid], descending) < ordinal(x[i], descending);
+                if (before) lo = mid + 1;
+                else hi = mid;
+            }
+            pos[i] = (u32)lo;
+        }
+        if (s) sortedKeys.returnHostPtr(s);
+        needles.returnHostPtr(x);
+        posOut.returnHostPtr(pos);
+        adl::DeviceUtils::waitForCompletion(device);
+        return;
+    }
+    const int rc = adlhip_search_sorted_typed(device->hip(), KeyTraits<K>::TYPE, descending ? ADLHIP_ORDER_DESCENDING : ADLHIP_ORDER_ASCENDING,
+                                              right ? ADLHIP_SEARCH_RIGHT : ADLHIP_SEARCH_LEFT, m ? sortedKeys.m_ptr : 0, (size_t)m, needles.m_ptr,
+                                              (size_t)n, (uint32_t*)posOut.m_ptr);
+    if (rc != ADLHIP_SUCCESS) TH_LOG_ERROR("Pprims::searchSorted: %s\n", adlhip_last_error());
+    ADLASSERT(rc == ADLHIP_SUCCESS);
+}
+
+#define TAHOE_SEARCH(K) \
+    template void Pprims::searchSorted<K>(const adl::Device*, const adl::Buffer<K>&, const adl::Buffer<K>&, adl::Buffer<u32>&, int, int, bool, bool);
+TAHOE_SEARCH(int)
+TAHOE_SEARCH(float)
+TAHOE_SEARCH(long long)
+TAHOE_SEARCH(double)
+TAHOE_SEARCH(u32)
+TAHOE_SEARCH(u64)
+#undef TAHOE_SEARCH
 
 #define TAHOE_TYPED(T)                                                                                                              \
     void Pprims::sortKeys(const adl::Device* device, const adl::Buffer<T>& inout, int n, bool descending)                         \

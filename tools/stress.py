@@ -6,11 +6,13 @@ is followed -- while later sorts are already queued -- by the LDS-order self-tes
 behaviour "sort.rank" = 1 rests on, adlhip_selftest_lds_order), and one size class reaches past 64 Mi keys (the
 pointer-store write-out).  Half of the sorts take the automatic choice (mid-size sort, large sort with its look-back /
 cursor passes and the safety net inside its offsets kernel), with "sort.msd2" forced on for some and keys shifted down by a random number of bits.
-One kind in nine is a stream compaction between the sorts (a stable partition of the keys by a comparison, values and positions along),
+One kind in ten is a stream compaction between the sorts (a stable partition of the keys by a comparison, values and positions along),
 one a histogram (range or bincount, random key type, bins and grid knob, the LDS and the sorted path), one a merge (the keys cut in
 two, each part sorted by the library as int32 or float32 keys in either order, then merged with positions and 8-byte values along),
 one a set operation (the keys folded onto a random number of distinct values and cut in two, each part sorted by the library, then
-a random one of the four operations with positions and 8-byte values along, checked against tests/setop_oracle.py).
+a random one of the four operations with positions and 8-byte values along, checked against tests/setop_oracle.py),
+one a sorted search (the keys cut into a sequence, sorted by the library as int32 or float32 keys in either order, and needles -- random
+ones and elements of the sequence --, either side, random table capacity and grid knob, checked against numpy.searchsorted on the codes).
    python tools/stress.py [--seconds 60]"""
 import argparse, os, sys, time
 import numpy as np
@@ -39,7 +41,7 @@ def checks(a):
     return int(a64.sum(dtype=np.uint64)), int(np.bitwise_xor.reduce(a64)) if a.size else 0
 while time.time() < t_end and it < args.stop_after:
     it += 1
-    kind = rng.choice(["u32", "kv", "u64", "soa", "soaw", "compact", "hist", "merge", "setop"])
+    kind = rng.choice(["u32", "kv", "u64", "soa", "soaw", "compact", "hist", "merge", "setop", "search"])
     n = int(2 ** rng.uniform(10, 25.5)) + int(rng.randint(0, 1000))
     if it % 7 == 0: n = int(2 ** rng.uniform(21, 26.3))   # more of the large sort's range
     if kind == "u32" and it % 23 == 0: n = (1 << 26) + int(rng.randint(1, 1 << 22))     # past 256 MiB: pointer stores
@@ -58,7 +60,7 @@ while time.time() < t_end and it < args.stop_after:
             else: rng.randint(1, 4)
         continue
     if verbose: print("it %d %s n=%d algo=%d bits=%d tile=%d msd2=%d dist=%s shift=%d" % (it, kind, n, algo, bits, tile, msd2_mode, dist, shift), flush=True)
-    if kind in ("u32", "soa", "kv", "soaw", "compact", "hist", "merge", "setop"):
+    if kind in ("u32", "soa", "kv", "soaw", "compact", "hist", "merge", "setop", "search"):
         k = oracle.keys_u32(n, seed=it)
         if dist == "heavy": k = np.where(np.arange(n) % 10 != 0, (k >> np.uint32(8)) | np.uint32(0x37000000), k).astype(np.uint32)
         elif dist == "vals4096": k = (k >> np.uint32(20)) * np.uint32(0x00100801)
@@ -130,6 +132,26 @@ while time.time() < t_end and it < args.stop_after:
         order = np.argsort(~code if desc else code, kind="stable")
         assert np.array_equal(gi, order) and np.array_equal(ok, cat[order]) and np.array_equal(ov, np.concatenate([sva, svb])[order]), (it, kind, n, na, dt, desc, dist)
         assert np.array_equal(np.sort(ov), np.sort(v)), (it, kind, "the values are not a permutation")
+    elif kind == "search":   # the bounds of needles in a sorted part of the keys, against numpy.searchsorted on the codes
+        sr = np.random.RandomState(args.seed + 17 * it)
+        n = min(n, 1 << 24)
+        m = int(sr.choice([0, 1, 2, 4096, 4097, n // 2, int(sr.randint(0, n))])); m = min(m, n - 1); nn = n - m
+        dt, desc, right = [np.int32, np.float32][sr.randint(0, 2)], bool(sr.randint(0, 2)), bool(sr.randint(0, 2))
+        d.setParam("debug.search_grid", int(sr.choice([0, 0, 1, 7, 300])))
+        d.setParam("debug.search_lds_keys", int(sr.choice([0, 0, 2, 3, 100])))
+        ks = Buffer(d, max(m, 1), dt); kx = Buffer(d, nn, dt); po = Buffer(d, nn, np.uint32)
+        x = k[m:n].copy()
+        if m: x[::3] = k[:m][sr.randint(0, m, size=x[::3].size)]      # a third of the needles are in the sequence
+        if m: ks.write(k[:m].view(dt)); p.sortKeys(d, ks, m, descending=desc)
+        kx.write(x.view(dt))
+        p.searchSorted(d, ks, kx, po, m, nn, descending=desc, right=right)
+        ss, got = ks.toHost()[:m].view(np.uint32), po.toHost()
+        for b in (ks, kx, po): b.release()
+        d.setParam("debug.search_grid", 0); d.setParam("debug.search_lds_keys", 0)
+        def code(a):
+            c = a ^ np.uint32(0x80000000) if dt == np.int32 else a ^ np.where(a & np.uint32(0x80000000) != 0, np.uint32(0xffffffff), np.uint32(0x80000000))
+            return ~c if desc else c
+        assert np.array_equal(got, np.searchsorted(code(ss), code(x), side="right" if right else "left").astype(np.uint32)), (it, kind, m, nn, dt, desc, right, dist)
     elif kind == "setop":   # a set operation on two sorted parts of the keys, against the oracle of the tests
         sr = np.random.RandomState(args.seed + 13 * it)
         n = min(n, 1 << 22)
