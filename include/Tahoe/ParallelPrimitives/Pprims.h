@@ -8,6 +8,7 @@
 //   sortKeys / argsort  signed, float and descending keys            (new: adlhip_sort_keys_typed / adlhip_argsort_typed)
 //   topK      the first k entries of argsort, by selection           (new: adlhip_topk_typed)
 //   topKRows  topK of every row of a rows x cols matrix              (new: adlhip_topk_rows_typed)
+//   sortRows / argsortRows  every row of a rows x cols matrix sorted (new: adlhip_sort_rows_typed)
 //   unique    distinct keys in sorted order and their counts         (new: adlhip_unique_typed)
 //   reduceByKey  sum / min / max of the values of every distinct key  (new: adlhip_reduce_by_key_typed)
 // Same argument meaning; differences, all supersets: any n >= 0 (the reference needs n % 256 == 0 for
@@ -234,9 +235,23 @@ public:
     void searchSorted(const adl::Device* device, const adl::Buffer<K>& sortedKeys, const adl::Buffer<K>& needles, adl::Buffer<u32>& posOut, int m,
                       int n, bool descending = false, bool right = false);
 
+    // sort along rows: every row of a rows x cols matrix sorted on its own, row r at element r * rowStride (0: cols), in the order of
+    // sortKeys(descending) and stably: indexOut[r * cols + j] = column of the j-th element of row r, equal keys by ascending column in
+    // both orders; keysOut[r * cols + j] = that key.  torch.sort(dim=-1, stable=True), cub::DeviceSegmentedSort on equal segments.  K:
+    // int, float, long long, double, u32, u64.  keys is left intact; the outputs are dense rows x cols.  argsortRows writes the
+    // columns alone.  Enqueues and returns.  A TYPE_HOST device runs a stable sort per row on the ordinals
+    template <typename K>
+    void sortRows(const adl::Device* device, const adl::Buffer<K>& keys, adl::Buffer<K>& keysOut, adl::Buffer<u32>& indexOut, int rows, int cols,
+                  bool descending = false, int rowStride = 0);
+    template <typename K>
+    void argsortRows(const adl::Device* device, const adl::Buffer<K>& keys, adl::Buffer<u32>& indexOut, int rows, int cols, bool descending = false,
+                     int rowStride = 0);
+
 private:
     template <typename T> int uniqueTyped(const adl::Device* device, const adl::Buffer<T>& keys, adl::Buffer<T>& uniqueOut, adl::Buffer<u32>& countsOut,
                                           int n, bool descending);
+    template <typename T> void sortRowsTyped(const adl::Device* device, const adl::Buffer<T>& keys, adl::Buffer<T>* keysOut, adl::Buffer<u32>& indexOut,
+                                             int rows, int cols, bool descending, int rowStride);
     template <typename T> void topKRowsTyped(const adl::Device* device, const adl::Buffer<T>& keys, adl::Buffer<T>& keysOut, adl::Buffer<u32>& indexOut,
                                              int rows, int cols, int k, bool descending, int rowStride);
     template <typename T> void topKTyped(const adl::Device* device, const adl::Buffer<T>& keys, adl::Buffer<T>& keysOut, adl::Buffer<u32>& indexOut, int n,

@@ -317,6 +317,43 @@ int adlhip_topk_rows_typed(adlhip_device* dev, int key_type, int order, const vo
                            size_t row_stride, size_t k, void* d_keys_out_or_null, uint32_t* d_index_out_or_null,
                            void* d_work, size_t work_bytes);
 
+/* ---- sort and argsort along rows (no reference counterpart) ----------------------------------- */
+
+/* Work bytes of adlhip_sort_rows_typed for (key_type, rows, cols): the need of the path the knobs choose NOW ("sort.rows_algo").
+ * The row kernel uses no global scratch: 0.  The flat path, with N = rows * cols and kb = bytes per key, every part rounded up to 256
+ * bytes:  N kb (the rows packed densely; always counted, used when row_stride != cols) + 4 arrays of 4 N (positions, row ids and the
+ * partner arrays of their sort) + max(W_argsort(N), W_soa32(N, bits of rows - 1)); rows == 1 needs W_argsort(cols) alone.
+ * W_argsort = *work_bytes of adlhip_sort_typed_scratch_bytes (mode 2), W_soa32 = that of adlhip_radix_sort_soa_scratch_bytes (4, 4).
+ * rows * cols >= 2^32 and, under "sort.rows_algo" = 1, cols > 4096 are refused here as they are by the sort. */
+int adlhip_sort_rows_scratch_bytes(adlhip_device* dev, int key_type, size_t rows, size_t cols, size_t* work_bytes);
+
+/* Sort and argsort along the rows of a rows x cols matrix -- torch.sort(t, dim=-1, stable=True), cub::DeviceSegmentedSort on equal
+ * segments: for every row r < rows the output row is exactly what adlhip_argsort_typed(dev, key_type, order, ...) returns for that row
+ * alone (same key order, NaN and -0 included; stable: equal keys appear by ascending column, in both orders).
+ * Row r of the input starts at element r * row_stride (row_stride in elements, >= cols); the outputs are dense rows x cols, row-major:
+ * d_index_out[r * cols + j] = the COLUMN of the j-th element of row r, d_keys_out[r * cols + j] = its key, bit for bit.
+ * Only the base pointers (d_keys_in, the outputs, d_work) need 16-byte alignment: a row may start at any element, cols and row_stride
+ * may be odd.  d_keys_in is never written; the elements between cols and row_stride are never read either.  At least one output must
+ * be given and neither may overlap the input.  rows * cols < 2^32; rows == 0 or cols == 0 succeeds and enqueues nothing.  A NULL or
+ * misaligned base pointer, both outputs NULL, an output overlapping the input, row_stride < cols, an unknown key type or order,
+ * rows * cols >= 2^32, or work_bytes below adlhip_sort_rows_scratch_bytes fail before anything is enqueued.  Enqueues and returns;
+ * nothing data-dependent reaches the host and nothing is remembered between calls (the handle owns no device word of it).
+ * Two paths, chosen on the host from cols alone ("sort.rows_algo"), the same result bit for bit:
+ *   the row kernel (cols <= 4096): a workgroup of 256 threads holds a tile of 4096 composites {encoded key, column} in LDS.  With P the
+ *     power of two >= cols (at least 2) a tile takes G = 4096 / P rows side by side, each padded to P slots, and ONE bitonic network
+ *     sorts all of them at once: it runs the merge phases up to length P only -- log2(P) (log2(P) + 1) / 2 stages -- with the compare
+ *     direction taken from the index inside the row's block, so that every block comes out ascending.  Workgroups take tiles in turns.
+ *     row_stride == cols: the G rows of a tile are one span, read in 16-byte loads; otherwise row by row.  Every key is read once,
+ *     every output written once; no global scratch (d_work may be NULL when 0 bytes are reported), no atomics to global memory, no
+ *     fence, no workgroup depends on another.
+ *   the flat path (any cols): the rows are packed densely when row_stride != cols; adlhip_argsort_typed's sort of all N keys gives
+ *     positions p in key order; a kernel writes their rows p / cols; adlhip_radix_sort_soa32 sorts (row, p) stably on the bits of
+ *     rows - 1, which keeps every row's elements in key order and ties by ascending position; a last kernel writes the columns
+ *     p - row * cols and gathers the keys from the input.  One row is the argsort itself, written straight to the outputs. */
+int adlhip_sort_rows_typed(adlhip_device* dev, int key_type, int order, const void* d_keys_in, size_t rows, size_t cols,
+                           size_t row_stride, void* d_keys_out_or_null, uint32_t* d_index_out_or_null,
+                           void* d_work, size_t work_bytes);
+
 /* ---- unique keys, run lengths, inverse indices (no reference counterpart) --------------------- */
 
 /* Key equality in this block is equality of BITS, consistent with the totalOrder above (NaN and -0 order): -0 and +0 are two keys, NaNs
@@ -893,6 +930,12 @@ int adlhip_generate_keys(adlhip_device* dev, int elem_kind, void* dptr, size_t n
  *                      (tools/topk_rows_bench.py measures it).  The same result bit for bit either way
  *   "debug.topk_rows_grid" workgroups the row kernel is launched with at most (0 [default]: 4 per CU); tests set it to make few
  *                      workgroups take many rows in turns
+ *   "sort.rows_algo"   -1 [default] / 0 / 1: adlhip_sort_rows_typed runs its row kernel while cols <= 4096 and the flat path above that;
+ *                      0 always takes the flat path, 1 always the row kernel (cols > 4096 is then refused, by the scratch query
+ *                      too).  Whether 4096 is where the default ought to switch is what tools/sort_rows_bench.py measures.  The
+ *                      same result bit for bit either way
+ *   "debug.sort_rows_grid" workgroups the row kernel of adlhip_sort_rows_typed is launched with at most (0 [default]: 4 per CU);
+ *                      tests set it to make few workgroups take many tiles in turns.  The result does not depend on it
  *   "unique.algo"      -1 [default] / 1: adlhip_unique_typed takes its keys path (copy, typed keys sort, run stage) unless first_index or
  *                      inverse is asked, which need the index path (argsort, run stage with the permutation); 1 always takes the index
  *                      path (tests, measurements; the work buffer must then have the want_index size).  The same unique, counts and

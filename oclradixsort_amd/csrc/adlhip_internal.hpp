@@ -66,6 +66,9 @@ struct adlhip_device {
     int topk_rows_algo = -1;  // "topk.rows_algo": -1 the row kernel while k <= kRowMaxK and cols <= kTopkRowsMaxCols, the per-row
                               // loop above; 0 / 1 force the loop / the row kernel
     int topk_rows_grid = 0;   // "debug.topk_rows_grid": workgroups of the row kernel at most (0: kTopkRowsWgsPerCu per CU)
+    int sort_rows_algo = -1;  // "sort.rows_algo": -1 the row kernel while cols <= kRowCap, the flat path above; 0 / 1 force the flat
+                              // path / the row kernel
+    int sort_rows_grid = 0;   // "debug.sort_rows_grid": workgroups of the sort's row kernel at most (0: kSortRowsWgsPerCu per CU)
     int unique_grid = 0;      // "debug.unique_grid": workgroups of the run stage at most (0: kUniqueWgsPerCu per CU)
     int reduce_grid = 0;      // "debug.reduce_grid": workgroups of the reduce stage at most (0: kReduceWgsPerCu per CU)
     int scan_grid = 0;        // "debug.scan_grid": workgroups of the scan stage at most (0: kScanWgsPerCu per CU)

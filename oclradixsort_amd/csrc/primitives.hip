@@ -1,4 +1,4 @@
-// primitives.hip -- the host side of what is built on top of the sorts: typed keys and argsort, top-k, row-wise top-k, unique /
+// primitives.hip -- the host side of what is built on top of the sorts: typed keys and argsort, top-k, row-wise top-k, sort along rows, unique /
 // run-length encode, reduce by key, typed scans, stream compaction, histograms, merges, set operations, sorted search.  No reference counterpart.  It reaches the sorts through adlhip_internal.hpp alone (sort_elements,
 // sort_work_bytes, soa_wide_layout) and never sees their kernels.
 #include "adlhip_internal.hpp"
@@ -16,6 +16,7 @@
 #define ADLHIP_KERNEL
 #include "select_kernels.hpp"
 #include "toprows_kernels.hpp"
+#include "sortrows_kernels.hpp"
 #include "unique_kernels.hpp"
 #include "reduce_kernels.hpp"
 #include "scan_kernels.hpp"
@@ -25,12 +26,13 @@
 #include "setop_kernels.hpp"
 #include "search_kernels.hpp"
 
-// instantiated in kernels_select.hip / kernels_toprows.hip / kernels_unique.hip / kernels_reduce.hip / kernels_scan.hip /
+// instantiated in kernels_select.hip / kernels_toprows.hip / kernels_sortrows.hip / kernels_unique.hip / kernels_reduce.hip / kernels_scan.hip /
 // kernels_compact.hip / kernels_histogram.hip / kernels_merge.hip / kernels_setop.hip / kernels_search.hip; here they are only declared
 #ifndef ADLHIP_SINGLE_TU
 #define X(...) extern template __global__ __VA_ARGS__;
 #include "select_kernels.inc"
 #include "toprows_kernels.inc"
+#include "sortrows_kernels.inc"
 #include "unique_kernels.inc"
 #include "reduce_kernels.inc"
 #include "scan_kernels.inc"
@@ -447,6 +449,113 @@ int topk_rows_kernel_path(adlhip_device* d, int kind, int desc, const U* keys_in
                        (uint32_t)cols, row_stride, (uint32_t)k, keys_out, index_out, plan)
         ADLHIP_TYPED_DISPATCH(kind, desc, ADLHIP_ROWS);
 #undef ADLHIP_ROWS
+    });
+}
+
+// ---- sort along rows (sortrows_kernels.hpp) ---------------------------------------------------------------------
+// "sort.rows_algo" = -1: the row kernel while cols <= kRowCap, the flat path above.  Where the row kernel starts to lose to the flat
+// path has NOT been measured (tools/sort_rows_bench.py measures it); kRowCap is what the kernel can hold.
+constexpr int kSortRowsWgsPerCu = 4;   // default grid of the row kernel per CU (its LDS admits 5 workgroups of 4-byte keys, 3 of 8-byte keys)
+
+// does the row kernel serve (rows, cols) under the knobs?  Refuses "sort.rows_algo" = 1 with rows it cannot hold
+int sort_rows_by_kernel(const adlhip_device* d, size_t cols, bool* kernel)
+{
+    if (d->sort_rows_algo == 1 && cols > (size_t)adlhip::kRowCap)
+        return fail("sort of rows: the row kernel (\"sort.rows_algo\" = 1) serves cols <= %d, got %zu", adlhip::kRowCap, cols);
+    *kernel = d->sort_rows_algo < 0 ? cols <= (size_t)adlhip::kRowCap : d->sort_rows_algo == 1;
+    return ADLHIP_SUCCESS;
+}
+
+// rows * cols as n, refused from 2^32 on (and above what the flat sorts index, as they refuse it themselves)
+int sort_rows_elems(size_t rows, size_t cols, size_t* n)
+{
+    if (__builtin_mul_overflow(rows, cols, n) || *n > kMaxElems)
+        return fail("sort of rows: rows * cols = %zu * %zu exceeds the supported maximum %zu", rows, cols, (size_t)kMaxElems);
+    return ADLHIP_SUCCESS;
+}
+
+// Work of the flat path, n = rows * cols: [the rows packed densely: n keys (used when row_stride != cols)][p: n positions]
+// [rowkey: n row ids][the partner arrays of the (rowkey, p) sort: n u32 each][work of the argsort / of that sort, whichever is
+// larger], every part 256-byte aligned.  One row is the argsort alone: its work at offset 0.
+struct SortRowsLayout {
+    size_t off_dense, off_pos, off_rowkey, off_tkeys, off_tvals, off_swork, swork_bytes, total;
+    int row_bits;   // sort_bits of the (rowkey, p) sort: the bit length of rows - 1, a multiple of 4
+};
+SortRowsLayout sort_rows_layout(const adlhip_device* d, size_t key_bytes, size_t rows, size_t cols)
+{
+    SortRowsLayout L = {};
+    const size_t n = rows * cols;
+    L.swork_bytes = soa_wide_layout(d, n).total;
+    if (rows > 1) {
+        L.row_bits = 4;
+        while (L.row_bits < 32 && ((rows - 1) >> L.row_bits) != 0) L.row_bits += 4;
+        L.off_pos = align_up(n * key_bytes, 256);
+        L.off_rowkey = L.off_pos + align_up(n * 4, 256);
+        L.off_tkeys = L.off_rowkey + align_up(n * 4, 256);
+        L.off_tvals = L.off_tkeys + align_up(n * 4, 256);
+        L.off_swork = L.off_tvals + align_up(n * 4, 256);
+        L.swork_bytes = std::max(L.swork_bytes, sort_work_bytes(d, ADLHIP_ELEM_SOA32, n, L.row_bits, 1));
+    }
+    L.total = L.off_swork + L.swork_bytes;
+    return L;
+}
+
+template <typename U>
+int sort_rows_kernel_path(adlhip_device* d, int kind, int desc, const U* keys_in, size_t rows, size_t cols, size_t row_stride, U* keys_out,
+                          uint32_t* index_out)
+{
+    uint32_t shift = 1;   // P = 1 << shift: the power of two >= cols, at least 2
+    while (((size_t)1 << shift) < cols) ++shift;
+    const size_t per_tile = (size_t)adlhip::kRowCap >> shift, tiles = (rows + per_tile - 1) / per_tile;
+    size_t cap = (size_t)d->prop.multiProcessorCount * kSortRowsWgsPerCu;
+    if (d->sort_rows_grid > 0) cap = std::min(cap, (size_t)d->sort_rows_grid);
+    const uint32_t wgs = (uint32_t)std::min(tiles, cap);
+    const uint64_t inv_cols = (uint64_t(1) << 32) / cols + 1;   // div_by_cols
+    return launch(d, sizeof(U) == 4 ? "sort_rows_k32" : "sort_rows_k64", [&] {
+#define ADLHIP_SROWS(KIND_, DESC_)                                                                                                  \
+    hipLaunchKernelGGL((adlhip::sort_rows_kernel<U, KIND_, DESC_>), dim3(wgs), dim3(adlhip::kSelNT), 0, d->stream, keys_in, rows,  \
+                       (uint32_t)cols, row_stride, shift, inv_cols, keys_out, index_out)
+        ADLHIP_TYPED_DISPATCH(kind, desc, ADLHIP_SROWS);
+#undef ADLHIP_SROWS
+    });
+}
+
+template <typename U>
+int sort_rows_flat_path(adlhip_device* d, int kind, int desc, const U* keys_in, size_t rows, size_t cols, size_t row_stride, U* keys_out,
+                        uint32_t* index_out, void* work)
+{
+    const SortRowsLayout L = sort_rows_layout(d, sizeof(U), rows, cols);
+    const size_t n = rows * cols;
+    char* w = static_cast<char*>(work);
+    if (rows == 1) return typed_index_sort<U, uint32_t>(d, kind, desc, keys_in, keys_out, nullptr, nullptr, index_out, w + L.off_swork, n);
+    uint32_t* pos = reinterpret_cast<uint32_t*>(w + L.off_pos);
+    uint32_t* rowkey = reinterpret_cast<uint32_t*>(w + L.off_rowkey);
+    const uint32_t wgs = (uint32_t)std::min<size_t>((n + adlhip::kSelNT - 1) / adlhip::kSelNT, (size_t)d->prop.multiProcessorCount * 16);
+    const U* dense = keys_in;
+    int rc;
+    if (row_stride != cols) {
+        U* packed = reinterpret_cast<U*>(w + L.off_dense);
+        rc = launch(d, "rows_pack", [&] {
+            hipLaunchKernelGGL((adlhip::rows_pack_kernel<U>), dim3(wgs), dim3(adlhip::kSelNT), 0, d->stream, keys_in, n, (uint32_t)cols,
+                               row_stride, packed);
+        });
+        if (rc) return rc;
+        dense = packed;
+    }
+    rc = typed_index_sort<U, uint32_t>(d, kind, desc, dense, nullptr, nullptr, nullptr, pos, w + L.off_swork, n);
+    if (rc) return rc;
+    rc = launch(d, "rows_of_positions", [&] {
+        hipLaunchKernelGGL(adlhip::rows_of_positions_kernel, dim3(wgs), dim3(adlhip::kSelNT), 0, d->stream, (const uint32_t*)pos, n,
+                           (uint32_t)cols, rowkey);
+    });
+    if (rc) return rc;
+    // stable on the row id: every row's elements stay in key order, ties by ascending position
+    rc = adlhip_radix_sort_soa32(d, rowkey, pos, reinterpret_cast<uint32_t*>(w + L.off_tkeys), reinterpret_cast<uint32_t*>(w + L.off_tvals),
+                                 w + L.off_swork, L.swork_bytes, n, L.row_bits);
+    if (rc) return rc;
+    return launch(d, "rows_emit", [&] {
+        hipLaunchKernelGGL((adlhip::rows_emit_kernel<U>), dim3(wgs), dim3(adlhip::kSelNT), 0, d->stream, keys_in, (const uint32_t*)pos,
+                           (const uint32_t*)rowkey, n, (uint32_t)cols, row_stride, keys_out, index_out);
     });
 }
 
@@ -1230,6 +1339,47 @@ int adlhip_topk_rows_typed(adlhip_device* d, int key_type, int order, const void
     return ADLHIP_BY_WIDTH(
         t.bytes, U, kernel ? topk_rows_kernel_path<U>(d, t.kind, order, (const U*)keys_in, rows, cols, row_stride, k, (U*)keys_out, index_out)
                            : topk_rows_loop<U>(d, t.kind, order, (const U*)keys_in, rows, cols, row_stride, k, (U*)keys_out, index_out, work));
+}
+
+// ---- sort along rows ----------------------------------------------------------------------------------
+int adlhip_sort_rows_scratch_bytes(adlhip_device* d, int key_type, size_t rows, size_t cols, size_t* work_bytes)
+{
+    if (!d) return fail("null device handle");
+    TypeInfo t;
+    size_t n = 0;
+    bool kernel = false;
+    if (key_type_info(key_type, ADLHIP_ORDER_ASCENDING, &t) || sort_rows_elems(rows, cols, &n) || sort_rows_by_kernel(d, cols, &kernel))
+        return ADLHIP_FAILURE;
+    if (work_bytes) *work_bytes = kernel || n == 0 ? 0 : sort_rows_layout(d, (size_t)t.bytes, rows, cols).total;
+    return ADLHIP_SUCCESS;
+}
+
+int adlhip_sort_rows_typed(adlhip_device* d, int key_type, int order, const void* keys_in, size_t rows, size_t cols, size_t row_stride,
+                           void* keys_out, uint32_t* index_out, void* work, size_t work_bytes)
+{
+    TypeInfo t;
+    size_t n = 0, in_elems = 0;
+    if (bind(d) || key_type_info(key_type, order, &t) || sort_rows_elems(rows, cols, &n)) return ADLHIP_FAILURE;
+    if (row_stride < cols) return fail("sort of rows: row_stride = %zu is below cols = %zu", row_stride, cols);
+    if (n == 0) return ADLHIP_SUCCESS;
+    if (!keys_out && !index_out) return fail("sort of rows: at least one of d_keys_out and d_index_out must be given");
+    if (!keys_in) return fail("sort of rows: d_keys_in is NULL");
+    bool kernel = false;
+    if (sort_rows_by_kernel(d, cols, &kernel)) return ADLHIP_FAILURE;
+    const size_t need = kernel ? 0 : sort_rows_layout(d, (size_t)t.bytes, rows, cols).total;
+    if (need && !work) return fail("sort of rows: d_work is NULL");
+    const struct { const void* p; const char* name; } bases[] = {{keys_in, "d_keys_in"}, {keys_out, "d_keys_out"}, {index_out, "d_index_out"}, {work, "d_work"}};
+    for (const auto& b : bases)
+        if (reinterpret_cast<uintptr_t>(b.p) & 15u) return fail("sort of rows: %s must be 16-byte aligned", b.name);
+    if (__builtin_mul_overflow(rows - 1, row_stride, &in_elems) || __builtin_add_overflow(in_elems, cols, &in_elems) || in_elems > (SIZE_MAX >> 4))
+        return fail("sort of rows: rows = %zu with row_stride = %zu is beyond the address space", rows, row_stride);
+    const size_t in_bytes = in_elems * (size_t)t.bytes;
+    if (overlaps(keys_out, n * (size_t)t.bytes, keys_in, in_bytes)) return fail("sort of rows: d_keys_out must not overlap d_keys_in");
+    if (overlaps(index_out, n * 4, keys_in, in_bytes)) return fail("sort of rows: d_index_out must not overlap d_keys_in");
+    if (work_bytes < need) return fail("sort of rows: work_bytes = %zu is below %zu (adlhip_sort_rows_scratch_bytes)", work_bytes, need);
+    return ADLHIP_BY_WIDTH(
+        t.bytes, U, kernel ? sort_rows_kernel_path<U>(d, t.kind, order, (const U*)keys_in, rows, cols, row_stride, (U*)keys_out, index_out)
+                           : sort_rows_flat_path<U>(d, t.kind, order, (const U*)keys_in, rows, cols, row_stride, (U*)keys_out, index_out, work));
 }
 
 // ---- unique / run-length encode ---------------------------------------------------------------------

@@ -10,6 +10,7 @@
     p.argsort(device, keys, n, descending=False)           # -> Buffer(uint32): the stable sorting permutation
     p.topk(device, keys, n, k, descending=False)           # -> Buffer(uint32): its first k entries, by selection
     p.topkRows(device, keys, rows, cols, k)                # -> Buffer(uint32): rows x k columns, top-k of every row
+    p.sortRows(device, keys, rows, cols, keysOut=out)      # -> Buffer(uint32): rows x cols columns, the stable argsort of every row
     p.unique(device, keys, n, counts=True, inverse=True)   # -> UniqueResult: distinct keys in sorted order, counts, inverse, ...
     p.runLengthEncode(device, keys, n, counts=True)        # -> UniqueResult: the runs of keys that are already grouped
     p.reduceByKey(device, keys, values, n, op="sum")       # -> ReduceResult: distinct keys in sorted order, sum / min / max of their values
@@ -305,6 +306,42 @@ class Pprims:
             check(_lib.load().adlhip_topk_rows_typed(device._h, kt, 1 if descending else 0, keys.ptr(), rows, cols, stride, k,
                                                      keysOut.ptr() if keysOut is not None else None, out.ptr(), self.m_work.ptr(),
                                                      self.m_work.getSize()), "topkRows")
+        except AdlHipError:
+            if indexOut is None:
+                out.release()
+            raise
+        return out
+
+    def sortRows(self, device, keys, rows, cols, descending=False, keysOut=None, indexOut=None, rowStride=None):
+        """Sort and argsort along the rows of a rows x cols matrix (row r starts at element r * rowStride; default cols): returns a
+        Buffer(uint32) of rows * cols columns, row-major -- per row the row's own stable argsort, ties by ascending column in both
+        orders.  `keys` is left intact; keysOut (same dtype, rows * cols elements, not `keys`) receives the sorted rows.  indexOut: a
+        uint32 buffer of rows * cols elements to fill and return instead of a new one.  Key order as sortKeys."""
+        if device is None:
+            raise AdlHipError("sortRows needs a device")
+        kt = self._key_type(keys, "sortRows")
+        rows, cols = int(rows), int(cols)
+        stride = cols if rowStride is None else int(rowStride)
+        if rows < 0 or cols < 0:
+            raise AdlHipError("sortRows: rows = %d, cols = %d" % (rows, cols))
+        if rows * cols >= 1 << 32:
+            raise AdlHipError("sortRows: rows * cols = %d, fewer than 2^32 elements" % (rows * cols))
+        if stride < cols:
+            raise AdlHipError("sortRows: rowStride = %d is below cols = %d" % (stride, cols))
+        if rows and cols and keys.getSize() < (rows - 1) * stride + cols:
+            raise AdlHipError("sortRows: keys must hold (rows - 1) * rowStride + cols = %d elements" % ((rows - 1) * stride + cols))
+        if keysOut is not None and (np.dtype(keysOut.dtype) != np.dtype(keys.dtype) or keysOut.getSize() < rows * cols):
+            raise AdlHipError("sortRows: keysOut must hold rows * cols elements of %s" % keys.dtype)
+        if indexOut is not None and (np.dtype(indexOut.dtype) != np.uint32 or indexOut.getSize() < rows * cols):
+            raise AdlHipError("sortRows: indexOut must hold rows * cols uint32 elements")
+        wb = ctypes.c_size_t()
+        check(_lib.load().adlhip_sort_rows_scratch_bytes(device._h, kt, rows, cols, ctypes.byref(wb)), "adlhip_sort_rows_scratch_bytes")
+        self._scratch(device, 0, wb.value)
+        out = indexOut if indexOut is not None else Buffer(device, rows * cols, np.uint32)
+        try:
+            check(_lib.load().adlhip_sort_rows_typed(device._h, kt, 1 if descending else 0, keys.ptr(), rows, cols, stride,
+                                                     keysOut.ptr() if keysOut is not None else None, out.ptr(), self.m_work.ptr(),
+                                                     self.m_work.getSize()), "sortRows")
         except AdlHipError:
             if indexOut is None:
                 out.release()

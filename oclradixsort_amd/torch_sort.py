@@ -6,6 +6,7 @@ back-end on torch's own stream.
     indices = s.argsort(t, descending=True)
     values, indices = s.topk(t, 10)         # the 10 largest, largest first; ties to the lower index
     values, indices = s.topk_rows(m, 10)    # m: 2-D or more; the same along the last dimension of every row
+    values, indices = s.sort_rows(m)        # torch.sort(m, dim=-1, stable=True) for m of 2 dimensions or more; argsort_rows: the indices
     u, inverse, counts = s.unique(t, return_inverse=True, return_counts=True)   # torch.unique(t) on any number of dimensions
     u, counts = s.unique_consecutive(t, return_counts=True)                      # torch.unique_consecutive(t), 1-D
     u, sums = s.reduce_by_key(keys, values, op="sum")                            # per distinct key: sum / min / max of its values
@@ -167,6 +168,44 @@ class TorchSorter:
                              keysOut=self._wrap(values, npdt), indexOut=self._wrap(idx32, np.uint32))
         self.device.checkFault()
         return values, idx32.to(torch.int64) & 0xffffffff
+
+    def _run_rows(self, what, t, descending, want_values):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError("TorchSorter: expected a torch.Tensor, got %s" % type(t).__name__)
+        if t.dtype not in _NP_DTYPE:
+            raise TypeError("TorchSorter: dtype %s unsupported (int32, int64, float32, float64)" % t.dtype)
+        if t.dim() < 2:
+            raise ValueError("TorchSorter.%s: 2-D tensors and above, got %d dimensions (sort / argsort serve 1-D)" % (what, t.dim()))
+        if t.device != self.torch_device:
+            raise ValueError("TorchSorter: tensor is on %s, the sorter on %s" % (t.device, self.torch_device))
+        if t.numel() >= 1 << 32:
+            raise ValueError("TorchSorter: fewer than 2^32 elements")
+        if torch.cuda.current_stream(self.torch_device).cuda_stream != self.raw_stream:
+            raise RuntimeError("TorchSorter: bound to the stream that was current at construction; another stream is current now")
+        cols = t.shape[-1]
+        rows = t.numel() // cols if cols else 0
+        values = torch.empty(t.shape, dtype=t.dtype, device=t.device) if want_values else None
+        if rows == 0 or cols == 0:
+            return values, torch.empty(t.shape, dtype=torch.int64, device=t.device)
+        src = self._aligned(t)         # (the base pointer only: rows may start anywhere)
+        npdt = _NP_DTYPE[t.dtype]
+        idx32 = torch.empty(t.shape, dtype=torch.int32, device=t.device)   # uint32 columns in an int32 tensor
+        self.pprims.sortRows(self.device, self._wrap(src, npdt), rows, cols, descending=descending,
+                             keysOut=self._wrap(values, npdt) if want_values else None, indexOut=self._wrap(idx32, np.uint32))
+        self.device.checkFault()
+        return values, idx32.to(torch.int64) & 0xffffffff
+
+    def sort_rows(self, t, descending=False):
+        """(values, indices) like torch.sort(t, dim=-1, descending=descending, stable=True) for t.dim() >= 2: every row of the last
+        dimension sorted, the leading dimensions flattened to rows; both results have t's shape, indices are int64.  A contiguous input
+        is read where it lies.  It differs from torch on NaN and -0 only: floats are ordered by totalOrder, so NaNs with the sign bit
+        set sort first (torch puts every NaN last) and -0 sorts before +0 (torch holds them equal).  A 1-D tensor is sort()'s."""
+        return self._run_rows("sort_rows", t, bool(descending), True)
+
+    def argsort_rows(self, t, descending=False):
+        """indices like torch.argsort(t, dim=-1, descending=descending, stable=True) for t.dim() >= 2, int64, of t's shape; NaN and -0
+        as in sort_rows (totalOrder).  A 1-D tensor is argsort()'s."""
+        return self._run_rows("argsort_rows", t, bool(descending), False)[1]
 
     def _flat_input(self, t, what, one_dim):
         """the checks of topk (dtype, device, size, stream) for `what`; returns t flattened, contiguous and 16-byte aligned (a copy only

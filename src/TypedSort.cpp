@@ -2,7 +2,8 @@
 // u32 bit patterns, ascending: Tahoe/ParallelPrimitives/Pprims.h:38-41).  A TYPE_CL (HIP) device runs adlhip_sort_keys_typed /
 // adlhip_argsort_typed; a TYPE_HOST device sorts on the CPU with std::stable_sort on the same total order, as the reference's
 // host branches do for u32 keys (Pprims.cpp:202-212, :306-316).  Pprims::topK: adlhip_topk_typed, or a partial sort on (ordinal,
-// position) on the host.  Pprims::topKRows: adlhip_topk_rows_typed, or the same partial sort per row.  Pprims::unique:
+// position) on the host.  Pprims::topKRows: adlhip_topk_rows_typed, or the same partial sort per row.  Pprims::sortRows /
+// argsortRows: adlhip_sort_rows_typed, or the host argsort per row.  Pprims::unique:
 // adlhip_unique_typed (it waits for the count), or the runs of the host argsort.  Pprims::reduceByKey: adlhip_reduce_by_key_typed (it
 // waits for the count), or a loop over the runs of the host argsort.  Pprims::scanTyped / scanByKey: adlhip_scan_typed /
 // adlhip_scan_by_key, or a plain loop, left to right.  Pprims::compactFlagged / compactIf: adlhip_compact_flagged /
@@ -225,6 +226,74 @@ void Pprims::topKRowsTyped(const adl::Device* device, const adl::Buffer<T>& keys
     if (rc != ADLHIP_SUCCESS) TH_LOG_ERROR("Pprims::topKRows: %s\n", adlhip_last_error());
     ADLASSERT(rc == ADLHIP_SUCCESS);
 }
+
+template <typename T>
+void Pprims::sortRowsTyped(const adl::Device* device, const adl::Buffer<T>& keys, adl::Buffer<T>* keysOut, adl::Buffer<u32>& indexOut, int rows,
+                           int cols, bool descending, int rowStride)
+{
+    const int stride = rowStride ? rowStride : cols;
+    ADLASSERT(rows >= 0 && cols >= 0 && stride >= cols);
+    if (rows <= 0 || cols <= 0 || stride < cols) return;
+    ADLASSERT(device != 0);
+    const adl::u64 inElems = (adl::u64)(rows - 1) * (adl::u64)stride + (adl::u64)cols, outElems = (adl::u64)rows * (adl::u64)cols;
+    ADLASSERT(inElems <= keys.getSize() && (!keysOut || outElems <= keysOut->getSize()) && outElems <= indexOut.getSize());
+    if (!onDevice(device)) {
+        ADLASSERT(device->getType() == adl::TYPE_HOST);   // a HIP device never falls back to the CPU
+        if (device->getType() != adl::TYPE_HOST) return;
+        T* host = keys.getHostPtr(inElems);
+        T* kout = keysOut ? keysOut->getHostPtr(outElems) : 0;
+        u32* out = indexOut.getHostPtr(outElems);
+        adl::DeviceUtils::waitForCompletion(device);
+        std::vector<Ranked<typename KeyTraits<T>::Bits> > order;
+        for (int r = 0; r < rows; ++r) {
+            const T* row = host + (size_t)r * (size_t)stride;
+            hostArgsort(row, cols, descending, order);
+            for (int j = 0; j < cols; ++j) {
+                out[(size_t)r * cols + j] = order[j].idx;
+                if (kout) kout[(size_t)r * cols + j] = row[order[j].idx];
+            }
+        }
+        keys.returnHostPtr(host);
+        if (keysOut) keysOut->returnHostPtr(kout);
+        indexOut.returnHostPtr(out);
+        adl::DeviceUtils::waitForCompletion(device);
+        return;
+    }
+    size_t wb = 0;
+    const int rcq = adlhip_sort_rows_scratch_bytes(device->hip(), KeyTraits<T>::TYPE, (size_t)rows, (size_t)cols, &wb);
+    ADLASSERT(rcq == ADLHIP_SUCCESS);
+    reserve(device, 0, wb);
+    const int rc = adlhip_sort_rows_typed(device->hip(), KeyTraits<T>::TYPE, descending ? ADLHIP_ORDER_DESCENDING : ADLHIP_ORDER_ASCENDING,
+                                          keys.m_ptr, (size_t)rows, (size_t)cols, (size_t)stride, keysOut ? keysOut->m_ptr : 0,
+                                          (uint32_t*)indexOut.m_ptr, m_work->m_ptr, (size_t)m_work->getSize());
+    if (rc != ADLHIP_SUCCESS) TH_LOG_ERROR("Pprims::sortRows: %s\n", adlhip_last_error());
+    ADLASSERT(rc == ADLHIP_SUCCESS);
+}
+
+template <typename K>
+void Pprims::sortRows(const adl::Device* device, const adl::Buffer<K>& keys, adl::Buffer<K>& keysOut, adl::Buffer<u32>& indexOut, int rows, int cols,
+                      bool descending, int rowStride)
+{
+    sortRowsTyped<K>(device, keys, &keysOut, indexOut, rows, cols, descending, rowStride);
+}
+
+template <typename K>
+void Pprims::argsortRows(const adl::Device* device, const adl::Buffer<K>& keys, adl::Buffer<u32>& indexOut, int rows, int cols, bool descending,
+                         int rowStride)
+{
+    sortRowsTyped<K>(device, keys, 0, indexOut, rows, cols, descending, rowStride);
+}
+
+#define TAHOE_SORT_ROWS(K)                                                                                                                       \
+    template void Pprims::sortRows<K>(const adl::Device*, const adl::Buffer<K>&, adl::Buffer<K>&, adl::Buffer<u32>&, int, int, bool, int); \
+    template void Pprims::argsortRows<K>(const adl::Device*, const adl::Buffer<K>&, adl::Buffer<u32>&, int, int, bool, int);
+TAHOE_SORT_ROWS(int)
+TAHOE_SORT_ROWS(float)
+TAHOE_SORT_ROWS(long long)
+TAHOE_SORT_ROWS(double)
+TAHOE_SORT_ROWS(u32)
+TAHOE_SORT_ROWS(u64)
+#undef TAHOE_SORT_ROWS
 
 template <typename T>
 int Pprims::uniqueTyped(const adl::Device* device, const adl::Buffer<T>& keys, adl::Buffer<T>& uniqueOut, adl::Buffer<u32>& countsOut, int n,
