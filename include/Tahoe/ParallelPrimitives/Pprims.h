@@ -9,6 +9,7 @@
 //   topK      the first k entries of argsort, by selection           (new: adlhip_topk_typed)
 //   topKRows  topK of every row of a rows x cols matrix              (new: adlhip_topk_rows_typed)
 //   sortRows / argsortRows  every row of a rows x cols matrix sorted (new: adlhip_sort_rows_typed)
+//   sortSegments / argsortSegments  every segment [offsets[s], offsets[s + 1]) sorted (new: adlhip_sort_segments_typed)
 //   unique    distinct keys in sorted order and their counts         (new: adlhip_unique_typed)
 //   reduceByKey  sum / min / max of the values of every distinct key  (new: adlhip_reduce_by_key_typed)
 // Same argument meaning; differences, all supersets: any n >= 0 (the reference needs n % 256 == 0 for
@@ -247,7 +248,25 @@ public:
     void argsortRows(const adl::Device* device, const adl::Buffer<K>& keys, adl::Buffer<u32>& indexOut, int rows, int cols, bool descending = false,
                      int rowStride = 0);
 
+    // sort within segments: segment s < numSegments is elements [offsets[s], offsets[s + 1]) of the n keys (offsets: numSegments + 1
+    // ascending entries, the first 0, the last n; empty segments may stand anywhere), sorted on its own in the order of
+    // sortKeys(descending) and stably: indexOut[offsets[s] + j] = position inside the segment of its j-th element (plus offsets[s] with
+    // globalIndex), equal keys by ascending position in both orders; keysOut[offsets[s] + j] = that key.  cub::DeviceSegmentedSort.
+    // maxSegment: an upper bound on the longest segment, 0 = unknown (adlhip_sort_segments_typed chooses its path from it; a segment
+    // longer than a bound of 4096 or less comes back in input order).  K: int, float, long long, double, u32, u64.  keys is left
+    // intact.  argsortSegments writes the indices alone.  Enqueues and returns.  A TYPE_HOST device runs a stable sort per segment on
+    // the ordinals, whatever maxSegment says
+    template <typename K>
+    void sortSegments(const adl::Device* device, const adl::Buffer<K>& keys, const adl::Buffer<u32>& offsets, adl::Buffer<K>& keysOut,
+                      adl::Buffer<u32>& indexOut, int n, int numSegments, int maxSegment = 0, bool descending = false, bool globalIndex = false);
+    template <typename K>
+    void argsortSegments(const adl::Device* device, const adl::Buffer<K>& keys, const adl::Buffer<u32>& offsets, adl::Buffer<u32>& indexOut, int n,
+                         int numSegments, int maxSegment = 0, bool descending = false, bool globalIndex = false);
+
 private:
+    template <typename T> void sortSegmentsTyped(const adl::Device* device, const adl::Buffer<T>& keys, const adl::Buffer<u32>& offsets,
+                                                 adl::Buffer<T>* keysOut, adl::Buffer<u32>& indexOut, int n, int numSegments, int maxSegment,
+                                                 bool descending, bool globalIndex);
     template <typename T> int uniqueTyped(const adl::Device* device, const adl::Buffer<T>& keys, adl::Buffer<T>& uniqueOut, adl::Buffer<u32>& countsOut,
                                           int n, bool descending);
     template <typename T> void sortRowsTyped(const adl::Device* device, const adl::Buffer<T>& keys, adl::Buffer<T>* keysOut, adl::Buffer<u32>& indexOut,

@@ -354,6 +354,59 @@ int adlhip_sort_rows_typed(adlhip_device* dev, int key_type, int order, const vo
                            size_t row_stride, void* d_keys_out_or_null, uint32_t* d_index_out_or_null,
                            void* d_work, size_t work_bytes);
 
+/* ---- sort and argsort within variable-length segments (no reference counterpart) -------------- */
+
+#define ADLHIP_SEGMENT_INDEX_LOCAL  0   /* position inside the segment (what sort_rows calls the column) */
+#define ADLHIP_SEGMENT_INDEX_GLOBAL 1   /* position in d_keys_in */
+
+/* Work bytes of adlhip_sort_segments_typed for (n, num_segments = S, max_segment): the need of the path the knobs choose NOW
+ * ("sort.segments_algo"); key_type is checked and does not change the size.  Every part rounded up to 256 bytes:
+ *   the segment kernel  4 arrays of 4 S (class numbers, segment ids and the partner arrays of their sort) + 256 (the class counts) +
+ *                       W_soa32(S, 4)
+ *   the flat path       4 arrays of 4 n (positions, segment ids and the partner arrays of their sort) + max(W_argsort(n),
+ *                       W_soa32(n, bits of S - 1 rounded up to a multiple of 4)); S == 1 needs W_argsort(n) alone.
+ * W_argsort = *work_bytes of adlhip_sort_typed_scratch_bytes (mode 2), W_soa32 = that of adlhip_radix_sort_soa_scratch_bytes (4, 4).
+ * n == 0 or S == 0: 0.  n or S beyond what the flat sorts index (n >= 2^32 among them) and, under "sort.segments_algo" = 1,
+ * max_segment == 0 or > 4096 are refused here as they are by the sort. */
+int adlhip_sort_segments_scratch_bytes(adlhip_device* dev, int key_type, size_t n, size_t num_segments, size_t max_segment,
+                                       size_t* work_bytes);
+
+/* Sort and argsort within segments -- cub::DeviceSegmentedSort, the column indices of every CSR row, the members of every group, the
+ * tokens of every sequence of a ragged batch: for every segment s < S = num_segments, with elements [off[s], off[s + 1]) of d_keys_in,
+ * the same positions of the outputs hold exactly what adlhip_argsort_typed(dev, key_type, order, ...) returns for that segment alone
+ * (keys bit for bit, totalOrder on NaN and -0; stable: equal keys appear by ascending position, in both orders).  d_index_out holds
+ * the position inside the segment (ADLHIP_SEGMENT_INDEX_LOCAL) or that plus off[s] (ADLHIP_SEGMENT_INDEX_GLOBAL).
+ * d_offsets: S + 1 ascending u32 element offsets in device memory, off[0] = 0, off[S] = n -- what adlhip_run_length_encode and
+ * adlhip_unique_typed hand out.  Empty segments may stand anywhere, so S may exceed n.  n < 2^32 and S within what the flat sorts
+ * index.  d_keys_in is never written.  At least one of the two outputs must be given; neither may overlap the input or d_offsets.
+ * Only the base pointers (d_keys_in, d_offsets, the outputs, d_work) need 16-byte alignment, the count word 4-byte alignment.
+ * n == 0 or S == 0 succeeds and enqueues nothing but, when the count word is given, one 4-byte clear of it.  A NULL or misaligned
+ * pointer, an overlap, an unknown key type, order or index_base, n >= 2^32, or work_bytes below adlhip_sort_segments_scratch_bytes
+ * fail before anything is enqueued.  Enqueues and returns; nothing data-dependent reaches the host, the launch grids depend on n, S
+ * and max_segment alone, nothing is remembered between calls, all state lives in d_work (the handle owns no device word of it).
+ * Offsets that break the requirements (not ascending, off[S] != n, ...) give an unspecified result but never an access outside the
+ * arrays: every offset is clamped to [previous, n] wherever it is used and every segment id to [0, S - 1].
+ * max_segment: the caller's upper bound on the longest segment, 0 = unknown.  The host picks the path from it alone
+ * ("sort.segments_algo"), the same result bit for bit:
+ *   the segment kernel (0 < max_segment <= 4096): a plan -- one thread per segment writes (class, id), class k = 1 .. 12 for the
+ *     smallest power of two P = 2^k >= len (at least 2), 0 for an empty segment, 13 for len > 4096; adlhip_radix_sort_soa32 sorts
+ *     the pairs stably on 4 bits; one workgroup finds the class counts in the sorted classes -- and then ONE launch of the row
+ *     kernel's tile and network: a tile of class k holds 4096 / P listed segments side by side, each padded to P slots, and the
+ *     bitonic network that stops at length P sorts all of them; workgroups take the tiles of all classes in turns.  Skewed lengths
+ *     do not pad every segment to the longest.  Every key is read once, every output written once; no atomics to global memory, no
+ *     fence, no workgroup depends on another.
+ *     A segment longer than 4096 -- the bound was wrong -- is a defined result, not a fault: it is passed through in input order
+ *     (keys copied, identity indices, local or global) and counted in *d_num_oversized_out.
+ *   the flat path (any lengths): adlhip_argsort_typed's sort of all n keys gives positions p in key order; the segment of p is its
+ *     upper bound in off[1 .. S] (the kernel of adlhip_search_sorted_typed, which steps over runs of empty segments);
+ *     adlhip_radix_sort_soa32 sorts (segment, p) stably on the bits of S - 1; a last kernel writes p - off[segment] or p and gathers
+ *     the keys.  S == 1 is the argsort itself, written straight to the outputs.
+ * d_num_oversized_out, when given, is always written: the number of segments passed through, 0 on the flat path.  The handle's fault
+ * word is not involved. */
+int adlhip_sort_segments_typed(adlhip_device* dev, int key_type, int order, const void* d_keys_in, size_t n, const uint32_t* d_offsets,
+                               size_t num_segments, size_t max_segment, int index_base, void* d_keys_out_or_null,
+                               uint32_t* d_index_out_or_null, uint32_t* d_num_oversized_out_or_null, void* d_work, size_t work_bytes);
+
 /* ---- unique keys, run lengths, inverse indices (no reference counterpart) --------------------- */
 
 /* Key equality in this block is equality of BITS, consistent with the totalOrder above (NaN and -0 order): -0 and +0 are two keys, NaNs
@@ -936,6 +989,13 @@ int adlhip_generate_keys(adlhip_device* dev, int elem_kind, void* dptr, size_t n
  *                      same result bit for bit either way
  *   "debug.sort_rows_grid" workgroups the row kernel of adlhip_sort_rows_typed is launched with at most (0 [default]: 4 per CU);
  *                      tests set it to make few workgroups take many tiles in turns.  The result does not depend on it
+ *   "sort.segments_algo" -1 [default] / 0 / 1: adlhip_sort_segments_typed runs its segment kernel while 0 < max_segment <= 4096 and the
+ *                      flat path otherwise; 0 always takes the flat path, 1 always the segment kernel (max_segment == 0 or > 4096 is
+ *                      then refused, by the scratch query too).  tools/sort_segments_bench.py measures both per shape.  The same
+ *                      result bit for bit either way
+ *   "debug.sort_segments_grid" workgroups the segment kernel is launched with at most (0 [default]: 3 per CU for 4-byte keys, 2 for
+ *                      8-byte keys, what its LDS admits); tests set it to make few workgroups walk tiles across class boundaries.
+ *                      The result does not depend on it
  *   "unique.algo"      -1 [default] / 1: adlhip_unique_typed takes its keys path (copy, typed keys sort, run stage) unless first_index or
  *                      inverse is asked, which need the index path (argsort, run stage with the permutation); 1 always takes the index
  *                      path (tests, measurements; the work buffer must then have the want_index size).  The same unique, counts and

@@ -76,6 +76,8 @@ SIGNATURES = {
     "adlhip_topk_rows_typed": (_I, [_VP, _I, _I, _VP, _SZ, _SZ, _SZ, _SZ, _VP, _VP, _VP, _SZ]),
     "adlhip_sort_rows_scratch_bytes": (_I, [_VP, _I, _SZ, _SZ, c_size_p]),
     "adlhip_sort_rows_typed": (_I, [_VP, _I, _I, _VP, _SZ, _SZ, _SZ, _VP, _VP, _VP, _SZ]),
+    "adlhip_sort_segments_scratch_bytes": (_I, [_VP, _I, _SZ, _SZ, _SZ, c_size_p]),
+    "adlhip_sort_segments_typed": (_I, [_VP, _I, _I, _VP, _SZ, _VP, _SZ, _SZ, _I, _VP, _VP, _VP, _VP, _SZ]),
     "adlhip_run_length_encode_scratch_bytes": (_I, [_VP, _I, _SZ, c_size_p]),
     "adlhip_run_length_encode": (_I, [_VP, _I, _VP, _SZ, _VP, _VP, _VP, _VP, _VP, _SZ]),
     "adlhip_unique_scratch_bytes": (_I, [_VP, _I, _SZ, _I, c_size_p]),

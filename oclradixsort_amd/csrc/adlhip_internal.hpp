@@ -69,6 +69,9 @@ struct adlhip_device {
     int sort_rows_algo = -1;  // "sort.rows_algo": -1 the row kernel while cols <= kRowCap, the flat path above; 0 / 1 force the flat
                               // path / the row kernel
     int sort_rows_grid = 0;   // "debug.sort_rows_grid": workgroups of the sort's row kernel at most (0: kSortRowsWgsPerCu per CU)
+    int sort_segments_algo = -1;  // "sort.segments_algo": -1 the segment kernel while 0 < max_segment <= kRowCap, the flat path
+                                  // otherwise; 0 / 1 force the flat path / the segment kernel
+    int sort_segments_grid = 0;   // "debug.sort_segments_grid": workgroups of the segment kernel at most (0: what its LDS admits per CU)
     int unique_grid = 0;      // "debug.unique_grid": workgroups of the run stage at most (0: kUniqueWgsPerCu per CU)
     int reduce_grid = 0;      // "debug.reduce_grid": workgroups of the reduce stage at most (0: kReduceWgsPerCu per CU)
     int scan_grid = 0;        // "debug.scan_grid": workgroups of the scan stage at most (0: kScanWgsPerCu per CU)

@@ -214,6 +214,9 @@ const Knob kKnobs[] = {
     {"sort.rows_algo", &adlhip_device::sort_rows_algo, -1, 1,
      "sort.rows_algo must be -1 (by cols), 0 (always the flat path) or 1 (always the row kernel)", nullptr},
     {"debug.sort_rows_grid", &adlhip_device::sort_rows_grid, 0, kNoMax, "debug.sort_rows_grid must be >= 0", nullptr},
+    {"sort.segments_algo", &adlhip_device::sort_segments_algo, -1, 1,
+     "sort.segments_algo must be -1 (by max_segment), 0 (always the flat path) or 1 (always the segment kernel)", nullptr},
+    {"debug.sort_segments_grid", &adlhip_device::sort_segments_grid, 0, kNoMax, "debug.sort_segments_grid must be >= 0", nullptr},
     {"debug.unique_grid", &adlhip_device::unique_grid, 0, kNoMax, "debug.unique_grid must be >= 0", nullptr},
     {"debug.reduce_grid", &adlhip_device::reduce_grid, 0, kNoMax, "debug.reduce_grid must be >= 0", nullptr},
     {"debug.scan_grid", &adlhip_device::scan_grid, 0, kNoMax, "debug.scan_grid must be >= 0", nullptr},

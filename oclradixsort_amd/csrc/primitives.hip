@@ -1,4 +1,4 @@
-// primitives.hip -- the host side of what is built on top of the sorts: typed keys and argsort, top-k, row-wise top-k, sort along rows, unique /
+// primitives.hip -- the host side of what is built on top of the sorts: typed keys and argsort, top-k, row-wise top-k, sort along rows and within segments, unique /
 // run-length encode, reduce by key, typed scans, stream compaction, histograms, merges, set operations, sorted search.  No reference counterpart.  It reaches the sorts through adlhip_internal.hpp alone (sort_elements,
 // sort_work_bytes, soa_wide_layout) and never sees their kernels.
 #include "adlhip_internal.hpp"
@@ -17,6 +17,7 @@
 #include "select_kernels.hpp"
 #include "toprows_kernels.hpp"
 #include "sortrows_kernels.hpp"
+#include "segments_kernels.hpp"
 #include "unique_kernels.hpp"
 #include "reduce_kernels.hpp"
 #include "scan_kernels.hpp"
@@ -26,13 +27,14 @@
 #include "setop_kernels.hpp"
 #include "search_kernels.hpp"
 
-// instantiated in kernels_select.hip / kernels_toprows.hip / kernels_sortrows.hip / kernels_unique.hip / kernels_reduce.hip / kernels_scan.hip /
+// instantiated in kernels_select.hip / kernels_toprows.hip / kernels_sortrows.hip / kernels_segments.hip / kernels_unique.hip / kernels_reduce.hip / kernels_scan.hip /
 // kernels_compact.hip / kernels_histogram.hip / kernels_merge.hip / kernels_setop.hip / kernels_search.hip; here they are only declared
 #ifndef ADLHIP_SINGLE_TU
 #define X(...) extern template __global__ __VA_ARGS__;
 #include "select_kernels.inc"
 #include "toprows_kernels.inc"
 #include "sortrows_kernels.inc"
+#include "segments_kernels.inc"
 #include "unique_kernels.inc"
 #include "reduce_kernels.inc"
 #include "scan_kernels.inc"
@@ -1193,6 +1195,132 @@ int search_stage(adlhip_device* d, adlhip::RedCodec codec, int side, const U* so
     });
 }
 
+// ---- sort within segments (segments_kernels.hpp) ---------------------------------------------------------------
+static_assert(ADLHIP_SEGMENT_INDEX_LOCAL == adlhip::kSegIndexLocal && ADLHIP_SEGMENT_INDEX_GLOBAL == adlhip::kSegIndexGlobal,
+              "the header states the index bases");
+// default grid of the segment kernel per CU: what its LDS admits.  The tile (32 KiB for 4-byte keys, 48 KiB for 8-byte keys) and the
+// starts and lengths of up to 2048 listed segments (12 KiB) make 44.1 and 60.1 KiB of the CU's 160: 3 and 2 workgroups.  Reasoned from
+// the LDS alone, not measured against fewer
+constexpr int kSortSegmentsWgsPerCu32 = 3, kSortSegmentsWgsPerCu64 = 2;
+
+// does the segment kernel serve max_segment under the knobs?  Refuses "sort.segments_algo" = 1 with a bound it cannot hold
+int sort_segments_by_kernel(const adlhip_device* d, size_t max_segment, bool* kernel)
+{
+    const bool fits = max_segment > 0 && max_segment <= (size_t)adlhip::kRowCap;
+    if (d->sort_segments_algo == 1 && !fits)
+        return fail("sort of segments: the segment kernel (\"sort.segments_algo\" = 1) serves 0 < max_segment <= %d, got %zu", adlhip::kRowCap,
+                    max_segment);
+    *kernel = d->sort_segments_algo < 0 ? fits : d->sort_segments_algo == 1;
+    return ADLHIP_SUCCESS;
+}
+
+int sort_segments_sizes(size_t n, size_t num_segments)
+{
+    if (n > kMaxElems) return fail("sort of segments: n = %zu exceeds the supported maximum %zu", n, (size_t)kMaxElems);
+    if (num_segments > kMaxElems)
+        return fail("sort of segments: num_segments = %zu exceeds the supported maximum %zu", num_segments, (size_t)kMaxElems);
+    return ADLHIP_SUCCESS;
+}
+
+// Work of either path, S = num_segments, every part 256-byte aligned.
+//   the segment kernel  [cls: S class numbers][ids: S segment ids][the partner arrays of the (cls, ids) sort: S u32 each][counts: the 14
+//                       class counts][work of that sort on 4 bits]
+//   the flat path       [pos: n positions][seg: n segment ids][the partner arrays of the (seg, pos) sort: n u32 each][work of the
+//                       argsort / of that sort, whichever is larger].  One segment is the argsort alone: its work at offset 0.
+struct SortSegmentsLayout {
+    size_t off_a, off_b, off_ta, off_tb, off_counts, off_swork, swork_bytes, total;
+    int seg_bits;   // flat path: sort_bits of the (seg, pos) sort, the bit length of S - 1 rounded up to a multiple of 4
+};
+SortSegmentsLayout sort_segments_layout(const adlhip_device* d, bool kernel, size_t n, size_t num_segments)
+{
+    SortSegmentsLayout L = {};
+    if (kernel) {
+        const size_t part = align_up(num_segments * 4, 256);
+        L.off_b = part;
+        L.off_ta = 2 * part;
+        L.off_tb = 3 * part;
+        L.off_counts = 4 * part;
+        L.off_swork = L.off_counts + 256;
+        L.swork_bytes = sort_work_bytes(d, ADLHIP_ELEM_SOA32, num_segments, 4, 1);
+    } else {
+        L.swork_bytes = soa_wide_layout(d, n).total;
+        if (num_segments > 1) {
+            L.seg_bits = 4;
+            while (L.seg_bits < 32 && ((num_segments - 1) >> L.seg_bits) != 0) L.seg_bits += 4;
+            const size_t part = align_up(n * 4, 256);
+            L.off_b = part;
+            L.off_ta = 2 * part;
+            L.off_tb = 3 * part;
+            L.off_swork = 4 * part;
+            L.swork_bytes = std::max(L.swork_bytes, sort_work_bytes(d, ADLHIP_ELEM_SOA32, n, L.seg_bits, 1));
+        }
+    }
+    L.total = L.off_swork + L.swork_bytes;
+    return L;
+}
+
+template <typename U>
+int sort_segments_kernel_path(adlhip_device* d, int kind, int desc, const U* keys_in, size_t n, const uint32_t* offsets, size_t S,
+                              int index_base, U* keys_out, uint32_t* index_out, uint32_t* oversized, void* work)
+{
+    const SortSegmentsLayout L = sort_segments_layout(d, true, n, S);
+    char* w = static_cast<char*>(work);
+    uint32_t* cls = reinterpret_cast<uint32_t*>(w + L.off_a);
+    uint32_t* ids = reinterpret_cast<uint32_t*>(w + L.off_b);
+    uint32_t* counts = reinterpret_cast<uint32_t*>(w + L.off_counts);
+    const uint32_t pwgs = (uint32_t)std::min<size_t>((S + adlhip::kSelNT - 1) / adlhip::kSelNT, (size_t)d->prop.multiProcessorCount * 16);
+    int rc = launch(d, "segments_classify", [&] {
+        hipLaunchKernelGGL(adlhip::segments_classify_kernel, dim3(pwgs), dim3(adlhip::kSelNT), 0, d->stream, offsets, (uint32_t)S, (uint32_t)n,
+                           cls, ids);
+    });
+    if (rc) return rc;
+    // stable on the class: the ids of every class stay ascending
+    rc = adlhip_radix_sort_soa32(d, cls, ids, reinterpret_cast<uint32_t*>(w + L.off_ta), reinterpret_cast<uint32_t*>(w + L.off_tb),
+                                 w + L.off_swork, L.swork_bytes, S, 4);
+    if (rc) return rc;
+    rc = launch(d, "segments_counts", [&] {
+        hipLaunchKernelGGL(adlhip::segments_counts_kernel, dim3(1), dim3(64), 0, d->stream, (const uint32_t*)cls, (uint32_t)S, counts, oversized);
+    });
+    if (rc) return rc;
+    size_t cap = (size_t)d->prop.multiProcessorCount * (sizeof(U) == 4 ? kSortSegmentsWgsPerCu32 : kSortSegmentsWgsPerCu64);
+    if (d->sort_segments_grid > 0) cap = std::min(cap, (size_t)d->sort_segments_grid);
+    const uint32_t wgs = (uint32_t)std::min(S, cap);
+    return launch(d, sizeof(U) == 4 ? "segments_sort_k32" : "segments_sort_k64", [&] {
+#define ADLHIP_SSEG(KIND_, DESC_)                                                                                                       \
+    hipLaunchKernelGGL((adlhip::segments_sort_kernel<U, KIND_, DESC_>), dim3(wgs), dim3(adlhip::kSelNT), 0, d->stream, keys_in, (uint32_t)n, \
+                       offsets, (uint32_t)S, (const uint32_t*)ids, (const uint32_t*)counts, (uint32_t)index_base, keys_out, index_out)
+        ADLHIP_TYPED_DISPATCH(kind, desc, ADLHIP_SSEG);
+#undef ADLHIP_SSEG
+    });
+}
+
+template <typename U>
+int sort_segments_flat_path(adlhip_device* d, int kind, int desc, const U* keys_in, size_t n, const uint32_t* offsets, size_t S,
+                            int index_base, U* keys_out, uint32_t* index_out, uint32_t* oversized, void* work)
+{
+    const SortSegmentsLayout L = sort_segments_layout(d, false, n, S);
+    char* w = static_cast<char*>(work);
+    if (oversized) HIPCHK(hipMemsetAsync(oversized, 0, 4, d->stream));   // nothing is oversized here
+    if (S == 1) return typed_index_sort<U, uint32_t>(d, kind, desc, keys_in, keys_out, nullptr, nullptr, index_out, w + L.off_swork, n);
+    uint32_t* pos = reinterpret_cast<uint32_t*>(w + L.off_a);
+    uint32_t* seg = reinterpret_cast<uint32_t*>(w + L.off_b);
+    int rc = typed_index_sort<U, uint32_t>(d, kind, desc, keys_in, nullptr, nullptr, nullptr, pos, w + L.off_swork, n);
+    if (rc) return rc;
+    // the segment of p: the number of offsets off[1 .. S] that are <= p, which skips runs of empty segments (p < n = off[S], so S - 1 at
+    // most for offsets that keep the contract; the emit kernel clamps what others give)
+    rc = search_stage<uint32_t>(d, adlhip::RedCodec{(uint32_t)adlhip::kKeyUnsigned, 0u}, ADLHIP_SEARCH_RIGHT, offsets + 1, S, pos, n, seg);
+    if (rc) return rc;
+    // stable on the segment: every segment's elements stay in key order, ties by ascending position
+    rc = adlhip_radix_sort_soa32(d, seg, pos, reinterpret_cast<uint32_t*>(w + L.off_ta), reinterpret_cast<uint32_t*>(w + L.off_tb),
+                                 w + L.off_swork, L.swork_bytes, n, L.seg_bits);
+    if (rc) return rc;
+    const uint32_t wgs = (uint32_t)std::min<size_t>((n + adlhip::kSelNT - 1) / adlhip::kSelNT, (size_t)d->prop.multiProcessorCount * 16);
+    return launch(d, "segments_emit", [&] {
+        hipLaunchKernelGGL((adlhip::segments_emit_kernel<U>), dim3(wgs), dim3(adlhip::kSelNT), 0, d->stream, keys_in, (const uint32_t*)pos,
+                           (const uint32_t*)seg, (uint32_t)n, offsets, (uint32_t)S, (uint32_t)index_base, keys_out, index_out);
+    });
+}
+
 }  // namespace
 
 extern "C" {
@@ -1380,6 +1508,57 @@ int adlhip_sort_rows_typed(adlhip_device* d, int key_type, int order, const void
     return ADLHIP_BY_WIDTH(
         t.bytes, U, kernel ? sort_rows_kernel_path<U>(d, t.kind, order, (const U*)keys_in, rows, cols, row_stride, (U*)keys_out, index_out)
                            : sort_rows_flat_path<U>(d, t.kind, order, (const U*)keys_in, rows, cols, row_stride, (U*)keys_out, index_out, work));
+}
+
+// ---- sort within segments --------------------------------------------------------------------------------
+int adlhip_sort_segments_scratch_bytes(adlhip_device* d, int key_type, size_t n, size_t num_segments, size_t max_segment, size_t* work_bytes)
+{
+    if (!d) return fail("null device handle");
+    TypeInfo t;
+    bool kernel = false;
+    if (key_type_info(key_type, ADLHIP_ORDER_ASCENDING, &t) || sort_segments_sizes(n, num_segments) ||
+        sort_segments_by_kernel(d, max_segment, &kernel))
+        return ADLHIP_FAILURE;
+    if (work_bytes) *work_bytes = n == 0 || num_segments == 0 ? 0 : sort_segments_layout(d, kernel, n, num_segments).total;
+    return ADLHIP_SUCCESS;
+}
+
+int adlhip_sort_segments_typed(adlhip_device* d, int key_type, int order, const void* keys_in, size_t n, const uint32_t* offsets,
+                               size_t num_segments, size_t max_segment, int index_base, void* keys_out, uint32_t* index_out,
+                               uint32_t* num_oversized, void* work, size_t work_bytes)
+{
+    TypeInfo t;
+    if (bind(d) || key_type_info(key_type, order, &t) || sort_segments_sizes(n, num_segments)) return ADLHIP_FAILURE;
+    if (index_base != ADLHIP_SEGMENT_INDEX_LOCAL && index_base != ADLHIP_SEGMENT_INDEX_GLOBAL)
+        return fail("sort of segments: index_base must be ADLHIP_SEGMENT_INDEX_LOCAL (0) or ADLHIP_SEGMENT_INDEX_GLOBAL (1), got %d", index_base);
+    if (reinterpret_cast<uintptr_t>(num_oversized) & 3u) return fail("sort of segments: d_num_oversized_out must be 4-byte aligned");
+    bool kernel = false;
+    if (sort_segments_by_kernel(d, max_segment, &kernel)) return ADLHIP_FAILURE;
+    if (n == 0 || num_segments == 0) {
+        if (num_oversized) HIPCHK(hipMemsetAsync(num_oversized, 0, 4, d->stream));
+        return ADLHIP_SUCCESS;
+    }
+    if (!keys_out && !index_out) return fail("sort of segments: at least one of d_keys_out and d_index_out must be given");
+    if (!keys_in) return fail("sort of segments: d_keys_in is NULL");
+    if (!offsets) return fail("sort of segments: d_offsets is NULL");
+    if (!work) return fail("sort of segments: d_work is NULL");
+    const struct { const void* p; const char* name; } bases[] = {
+        {keys_in, "d_keys_in"}, {offsets, "d_offsets"}, {keys_out, "d_keys_out"}, {index_out, "d_index_out"}, {work, "d_work"}};
+    for (const auto& b : bases)
+        if (reinterpret_cast<uintptr_t>(b.p) & 15u) return fail("sort of segments: %s must be 16-byte aligned", b.name);
+    const size_t kb = (size_t)t.bytes;
+    const struct { const void* p; size_t bytes; const char* name; } ins[] = {{keys_in, n * kb, "d_keys_in"}, {offsets, (num_segments + 1) * 4, "d_offsets"}},
+        outs[] = {{keys_out, n * kb, "d_keys_out"}, {index_out, n * 4, "d_index_out"}, {num_oversized, 4, "d_num_oversized_out"}};
+    for (const auto& in : ins)
+        for (const auto& o : outs)
+            if (overlaps(o.p, o.bytes, in.p, in.bytes)) return fail("sort of segments: %s must not overlap %s", o.name, in.name);
+    const size_t need = sort_segments_layout(d, kernel, n, num_segments).total;
+    if (work_bytes < need) return fail("sort of segments: work_bytes = %zu is below %zu (adlhip_sort_segments_scratch_bytes)", work_bytes, need);
+    return ADLHIP_BY_WIDTH(t.bytes, U,
+                           kernel ? sort_segments_kernel_path<U>(d, t.kind, order, (const U*)keys_in, n, offsets, num_segments, index_base,
+                                                                 (U*)keys_out, index_out, num_oversized, work)
+                                  : sort_segments_flat_path<U>(d, t.kind, order, (const U*)keys_in, n, offsets, num_segments, index_base,
+                                                               (U*)keys_out, index_out, num_oversized, work));
 }
 
 // ---- unique / run-length encode ---------------------------------------------------------------------

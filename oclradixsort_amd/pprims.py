@@ -11,6 +11,7 @@
     p.topk(device, keys, n, k, descending=False)           # -> Buffer(uint32): its first k entries, by selection
     p.topkRows(device, keys, rows, cols, k)                # -> Buffer(uint32): rows x k columns, top-k of every row
     p.sortRows(device, keys, rows, cols, keysOut=out)      # -> Buffer(uint32): rows x cols columns, the stable argsort of every row
+    p.sortSegments(device, keys, offsets, S, maxSegment=m) # -> Buffer(uint32): the stable argsort of every segment [offsets[s], offsets[s+1])
     p.unique(device, keys, n, counts=True, inverse=True)   # -> UniqueResult: distinct keys in sorted order, counts, inverse, ...
     p.runLengthEncode(device, keys, n, counts=True)        # -> UniqueResult: the runs of keys that are already grouped
     p.reduceByKey(device, keys, values, n, op="sum")       # -> ReduceResult: distinct keys in sorted order, sum / min / max of their values
@@ -342,6 +343,48 @@ class Pprims:
             check(_lib.load().adlhip_sort_rows_typed(device._h, kt, 1 if descending else 0, keys.ptr(), rows, cols, stride,
                                                      keysOut.ptr() if keysOut is not None else None, out.ptr(), self.m_work.ptr(),
                                                      self.m_work.getSize()), "sortRows")
+        except AdlHipError:
+            if indexOut is None:
+                out.release()
+            raise
+        return out
+
+    def sortSegments(self, device, keys, offsets, numSegments, maxSegment=0, descending=False, keysOut=None, indexOut=None,
+                     globalIndex=False, oversizedOut=None):
+        """Sort and argsort within segments: segment s is elements [offsets[s], offsets[s + 1]) of `keys`, n = keys.getSize().
+        Returns a Buffer(uint32) of n indices -- per segment the segment's own stable argsort, ties by ascending position in both
+        orders; the position inside the segment, or in `keys` with globalIndex.  offsets: a uint32 buffer of numSegments + 1 ascending
+        offsets, the first 0, the last n; empty segments may stand anywhere.  maxSegment: an upper bound on the longest segment (0:
+        unknown); up to 4096 the segment kernel runs, otherwise the flat path.  A segment longer than a bound of 4096 or less comes
+        back in input order and is counted in oversizedOut (a uint32 buffer of one element, always written when given).  `keys` is
+        left intact; keysOut (same dtype, n elements, not `keys`) receives the sorted segments.  indexOut: a uint32 buffer of n
+        elements to fill and return instead of a new one.  Key order as sortKeys."""
+        if device is None:
+            raise AdlHipError("sortSegments needs a device")
+        kt = self._key_type(keys, "sortSegments")
+        n, S, bound = int(keys.getSize()), int(numSegments), int(maxSegment)
+        if S < 0 or bound < 0:
+            raise AdlHipError("sortSegments: numSegments = %d, maxSegment = %d" % (S, bound))
+        if n >= 1 << 32:
+            raise AdlHipError("sortSegments: n = %d, fewer than 2^32 elements" % n)
+        if np.dtype(offsets.dtype) != np.uint32 or offsets.getSize() < S + 1:
+            raise AdlHipError("sortSegments: offsets must hold numSegments + 1 = %d uint32 elements" % (S + 1))
+        if keysOut is not None and (np.dtype(keysOut.dtype) != np.dtype(keys.dtype) or keysOut.getSize() < n):
+            raise AdlHipError("sortSegments: keysOut must hold n = %d elements of %s" % (n, keys.dtype))
+        if indexOut is not None and (np.dtype(indexOut.dtype) != np.uint32 or indexOut.getSize() < n):
+            raise AdlHipError("sortSegments: indexOut must hold n = %d uint32 elements" % n)
+        if oversizedOut is not None and (np.dtype(oversizedOut.dtype) != np.uint32 or oversizedOut.getSize() < 1):
+            raise AdlHipError("sortSegments: oversizedOut must hold one uint32 element")
+        wb = ctypes.c_size_t()
+        check(_lib.load().adlhip_sort_segments_scratch_bytes(device._h, kt, n, S, bound, ctypes.byref(wb)),
+              "adlhip_sort_segments_scratch_bytes")
+        self._scratch(device, 0, wb.value)
+        out = indexOut if indexOut is not None else Buffer(device, n, np.uint32)
+        try:
+            check(_lib.load().adlhip_sort_segments_typed(device._h, kt, 1 if descending else 0, keys.ptr(), n, offsets.ptr(), S, bound,
+                                                         1 if globalIndex else 0, keysOut.ptr() if keysOut is not None else None,
+                                                         out.ptr(), oversizedOut.ptr() if oversizedOut is not None else None,
+                                                         self.m_work.ptr(), self.m_work.getSize()), "sortSegments")
         except AdlHipError:
             if indexOut is None:
                 out.release()

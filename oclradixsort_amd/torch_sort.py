@@ -207,6 +207,75 @@ class TorchSorter:
         as in sort_rows (totalOrder).  A 1-D tensor is argsort()'s."""
         return self._run_rows("argsort_rows", t, bool(descending), False)[1]
 
+    def _run_segments(self, what, t, offsets, descending, max_segment, global_indices, want_values):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError("TorchSorter: expected a torch.Tensor, got %s" % type(t).__name__)
+        if t.dtype not in _NP_DTYPE:
+            raise TypeError("TorchSorter: dtype %s unsupported (int32, int64, float32, float64)" % t.dtype)
+        if t.dim() != 1:
+            raise ValueError("TorchSorter.%s: 1-D tensors only, got %d dimensions (sort_rows serves equal rows)" % (what, t.dim()))
+        if not isinstance(offsets, torch.Tensor):
+            raise TypeError("TorchSorter.%s: offsets must be a torch.Tensor, got %s" % (what, type(offsets).__name__))
+        if offsets.dtype not in (torch.int32, torch.int64):
+            raise TypeError("TorchSorter.%s: offsets must be int32 or int64, got %s" % (what, offsets.dtype))
+        if offsets.dim() != 1 or offsets.numel() < 1:
+            raise ValueError("TorchSorter.%s: offsets must be 1-D with num_segments + 1 entries" % what)
+        n, S = t.numel(), offsets.numel() - 1
+        if S == 0 and n != 0:   # (seen from the shapes alone: off[0] = 0 = off[S] cannot be t.numel())
+            raise ValueError("TorchSorter.%s: offsets has one entry (no segment) for t.numel() = %d elements" % (what, n))
+        if not offsets.is_cuda:   # a host tensor is checked where it lies: nothing is waited for
+            if int(offsets[0]) != 0 or int(offsets[-1]) != n:
+                raise ValueError("TorchSorter.%s: offsets must start at 0 and end at t.numel() = %d" % (what, n))
+        self._check(t)   # (the device and the size)
+        if torch.cuda.current_stream(self.torch_device).cuda_stream != self.raw_stream:
+            raise RuntimeError("TorchSorter: bound to the stream that was current at construction; another stream is current now")
+        if not offsets.is_cuda:
+            if max_segment is None:
+                max_segment = int((offsets[1:] - offsets[:-1]).max()) if S else 0
+        elif max_segment is None:   # the one host read: first and last offset and the longest segment together
+            lens = offsets[1:] - offsets[:-1]
+            first, last, longest = torch.stack([offsets[0], offsets[-1], lens.max() if S else offsets[0]]).tolist()
+            if first != 0 or last != n:
+                raise ValueError("TorchSorter.%s: offsets must start at 0 and end at t.numel() = %d" % (what, n))
+            max_segment = longest if S else 0
+        max_segment = int(max_segment)
+        if max_segment < 0:
+            raise ValueError("TorchSorter.%s: max_segment = %d" % (what, max_segment))
+        values = torch.empty(n, dtype=t.dtype, device=t.device) if want_values else None
+        if n == 0 or S == 0:
+            return values, torch.empty(n, dtype=torch.int64, device=t.device)
+        # uint32 offsets in an int32 tensor: the low dwords of the int64 values, taken as bits (offsets from 2^31 on do not go through
+        # a narrowing conversion); a new tensor
+        off32 = offsets.to(device=t.device, dtype=torch.int64).contiguous().view(torch.int32)[::2].contiguous()
+        if off32.data_ptr() % 16:
+            off32 = off32.clone()
+        src = self._aligned(t)
+        npdt = _NP_DTYPE[t.dtype]
+        idx32 = torch.empty(n, dtype=torch.int32, device=t.device)   # uint32 positions in an int32 tensor
+        self.pprims.sortSegments(self.device, self._wrap(src, npdt), self._wrap(off32, np.uint32), S, maxSegment=max_segment,
+                                 descending=descending, keysOut=self._wrap(values, npdt) if want_values else None,
+                                 indexOut=self._wrap(idx32, np.uint32), globalIndex=bool(global_indices))
+        self.device.checkFault()
+        return values, idx32.to(torch.int64) & 0xffffffff
+
+    def sort_segments(self, t, offsets, descending=False, max_segment=None, global_indices=False):
+        """(values, indices): every segment t[offsets[s]:offsets[s + 1]] of the 1-D tensor t sorted on its own, in place of the segment
+        -- per segment what torch.sort(segment, descending=descending, stable=True) returns; indices are int64 positions inside the
+        segment, or in t with global_indices.  offsets: an int32 or int64 tensor of num_segments + 1 ascending entries, on the host or
+        the device, the first 0 and the last t.numel(); empty segments may stand anywhere (a single entry, no segment, is accepted for
+        an empty t only).  It differs from torch on NaN and -0 only:
+        floats are ordered by totalOrder (sort_rows).  max_segment is an upper bound on the longest segment; up to 4096 one kernel
+        sorts all segments, beyond that (or with 0, "unknown") two flat sorts do.  max_segment=None computes the longest segment,
+        which for offsets on the device costs ONE host read (first and last offset are checked by the same read): the call waits for
+        the stream.  With max_segment given and offsets on the device nothing reaches the host, and the ends of offsets are not
+        checked (offsets that break the rules give an unspecified result, never an access outside the tensors).  A segment longer
+        than a bound of 4096 or less comes back in input order."""
+        return self._run_segments("sort_segments", t, offsets, bool(descending), max_segment, global_indices, True)
+
+    def argsort_segments(self, t, offsets, descending=False, max_segment=None, global_indices=False):
+        """indices of sort_segments alone, int64; NaN and -0 as there (totalOrder), the same host read for max_segment=None."""
+        return self._run_segments("argsort_segments", t, offsets, bool(descending), max_segment, global_indices, False)[1]
+
     def _flat_input(self, t, what, one_dim):
         """the checks of topk (dtype, device, size, stream) for `what`; returns t flattened, contiguous and 16-byte aligned (a copy only
         for a strided or oddly placed input; the input is never written)"""

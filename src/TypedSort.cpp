@@ -3,7 +3,8 @@
 // adlhip_argsort_typed; a TYPE_HOST device sorts on the CPU with std::stable_sort on the same total order, as the reference's
 // host branches do for u32 keys (Pprims.cpp:202-212, :306-316).  Pprims::topK: adlhip_topk_typed, or a partial sort on (ordinal,
 // position) on the host.  Pprims::topKRows: adlhip_topk_rows_typed, or the same partial sort per row.  Pprims::sortRows /
-// argsortRows: adlhip_sort_rows_typed, or the host argsort per row.  Pprims::unique:
+// argsortRows: adlhip_sort_rows_typed, or the host argsort per row.  Pprims::sortSegments / argsortSegments:
+// adlhip_sort_segments_typed, or the host argsort per segment.  Pprims::unique:
 // adlhip_unique_typed (it waits for the count), or the runs of the host argsort.  Pprims::reduceByKey: adlhip_reduce_by_key_typed (it
 // waits for the count), or a loop over the runs of the host argsort.  Pprims::scanTyped / scanByKey: adlhip_scan_typed /
 // adlhip_scan_by_key, or a plain loop, left to right.  Pprims::compactFlagged / compactIf: adlhip_compact_flagged /
@@ -294,6 +295,79 @@ TAHOE_SORT_ROWS(double)
 TAHOE_SORT_ROWS(u32)
 TAHOE_SORT_ROWS(u64)
 #undef TAHOE_SORT_ROWS
+
+template <typename T>
+void Pprims::sortSegmentsTyped(const adl::Device* device, const adl::Buffer<T>& keys, const adl::Buffer<u32>& offsets, adl::Buffer<T>* keysOut,
+                               adl::Buffer<u32>& indexOut, int n, int numSegments, int maxSegment, bool descending, bool globalIndex)
+{
+    ADLASSERT(n >= 0 && numSegments >= 0 && maxSegment >= 0);
+    if (n <= 0 || numSegments <= 0 || maxSegment < 0) return;
+    ADLASSERT(device != 0);
+    ADLASSERT((adl::u64)n <= keys.getSize() && (adl::u64)numSegments + 1 <= offsets.getSize() && (!keysOut || (adl::u64)n <= keysOut->getSize()) &&
+              (adl::u64)n <= indexOut.getSize());
+    if (!onDevice(device)) {
+        ADLASSERT(device->getType() == adl::TYPE_HOST);   // a HIP device never falls back to the CPU
+        if (device->getType() != adl::TYPE_HOST) return;
+        T* host = keys.getHostPtr(n);
+        u32* off = offsets.getHostPtr(numSegments + 1);
+        T* kout = keysOut ? keysOut->getHostPtr(n) : 0;
+        u32* out = indexOut.getHostPtr(n);
+        adl::DeviceUtils::waitForCompletion(device);
+        std::vector<Ranked<typename KeyTraits<T>::Bits> > order;
+        for (int s = 0; s < numSegments; ++s) {   // every offset clamped to [previous, n], as the device clamps it
+            const u32 lo = off[s] < (u32)n ? off[s] : (u32)n;
+            const u32 hi = off[s + 1] < lo ? lo : (off[s + 1] < (u32)n ? off[s + 1] : (u32)n);
+            hostArgsort(host + lo, (int)(hi - lo), descending, order);
+            for (u32 j = 0; j < hi - lo; ++j) {
+                out[lo + j] = order[j].idx + (globalIndex ? lo : 0u);
+                if (kout) kout[lo + j] = host[lo + order[j].idx];
+            }
+        }
+        keys.returnHostPtr(host);
+        offsets.returnHostPtr(off);
+        if (keysOut) keysOut->returnHostPtr(kout);
+        indexOut.returnHostPtr(out);
+        adl::DeviceUtils::waitForCompletion(device);
+        return;
+    }
+    size_t wb = 0;
+    const int rcq = adlhip_sort_segments_scratch_bytes(device->hip(), KeyTraits<T>::TYPE, (size_t)n, (size_t)numSegments, (size_t)maxSegment, &wb);
+    ADLASSERT(rcq == ADLHIP_SUCCESS);
+    reserve(device, 0, wb);
+    const int rc = adlhip_sort_segments_typed(device->hip(), KeyTraits<T>::TYPE, descending ? ADLHIP_ORDER_DESCENDING : ADLHIP_ORDER_ASCENDING,
+                                              keys.m_ptr, (size_t)n, (const uint32_t*)offsets.m_ptr, (size_t)numSegments, (size_t)maxSegment,
+                                              globalIndex ? ADLHIP_SEGMENT_INDEX_GLOBAL : ADLHIP_SEGMENT_INDEX_LOCAL, keysOut ? keysOut->m_ptr : 0,
+                                              (uint32_t*)indexOut.m_ptr, 0, m_work->m_ptr, (size_t)m_work->getSize());
+    if (rc != ADLHIP_SUCCESS) TH_LOG_ERROR("Pprims::sortSegments: %s\n", adlhip_last_error());
+    ADLASSERT(rc == ADLHIP_SUCCESS);
+}
+
+template <typename K>
+void Pprims::sortSegments(const adl::Device* device, const adl::Buffer<K>& keys, const adl::Buffer<u32>& offsets, adl::Buffer<K>& keysOut,
+                          adl::Buffer<u32>& indexOut, int n, int numSegments, int maxSegment, bool descending, bool globalIndex)
+{
+    sortSegmentsTyped<K>(device, keys, offsets, &keysOut, indexOut, n, numSegments, maxSegment, descending, globalIndex);
+}
+
+template <typename K>
+void Pprims::argsortSegments(const adl::Device* device, const adl::Buffer<K>& keys, const adl::Buffer<u32>& offsets, adl::Buffer<u32>& indexOut,
+                             int n, int numSegments, int maxSegment, bool descending, bool globalIndex)
+{
+    sortSegmentsTyped<K>(device, keys, offsets, 0, indexOut, n, numSegments, maxSegment, descending, globalIndex);
+}
+
+#define TAHOE_SORT_SEGMENTS(K)                                                                                                                \
+    template void Pprims::sortSegments<K>(const adl::Device*, const adl::Buffer<K>&, const adl::Buffer<u32>&, adl::Buffer<K>&, adl::Buffer<u32>&, \
+                                          int, int, int, bool, bool);                                                                       \
+    template void Pprims::argsortSegments<K>(const adl::Device*, const adl::Buffer<K>&, const adl::Buffer<u32>&, adl::Buffer<u32>&, int, int, int, \
+                                             bool, bool);
+TAHOE_SORT_SEGMENTS(int)
+TAHOE_SORT_SEGMENTS(float)
+TAHOE_SORT_SEGMENTS(long long)
+TAHOE_SORT_SEGMENTS(double)
+TAHOE_SORT_SEGMENTS(u32)
+TAHOE_SORT_SEGMENTS(u64)
+#undef TAHOE_SORT_SEGMENTS
 
 template <typename T>
 int Pprims::uniqueTyped(const adl::Device* device, const adl::Buffer<T>& keys, adl::Buffer<T>& uniqueOut, adl::Buffer<u32>& countsOut, int n,

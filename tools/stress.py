@@ -12,7 +12,10 @@ two, each part sorted by the library as int32 or float32 keys in either order, t
 one a set operation (the keys folded onto a random number of distinct values and cut in two, each part sorted by the library, then
 a random one of the four operations with positions and 8-byte values along, checked against tests/setop_oracle.py),
 one a sorted search (the keys cut into a sequence, sorted by the library as int32 or float32 keys in either order, and needles -- random
-ones and elements of the sequence --, either side, random table capacity and grid knob, checked against numpy.searchsorted on the codes).
+ones and elements of the sequence --, either side, random table capacity and grid knob, checked against numpy.searchsorted on the codes),
+one a sort within segments (the keys as int32 or float32 in either order, cut into segments of uniform or heavy-tailed lengths with runs
+of empty ones, on the segment kernel or the flat path with a random grid knob and index base, checked against one numpy lexsort on
+(segment, code)).
    python tools/stress.py [--seconds 60]"""
 import argparse, os, sys, time
 import numpy as np
@@ -41,7 +44,7 @@ def checks(a):
     return int(a64.sum(dtype=np.uint64)), int(np.bitwise_xor.reduce(a64)) if a.size else 0
 while time.time() < t_end and it < args.stop_after:
     it += 1
-    kind = rng.choice(["u32", "kv", "u64", "soa", "soaw", "compact", "hist", "merge", "setop", "search"])
+    kind = rng.choice(["u32", "kv", "u64", "soa", "soaw", "compact", "hist", "merge", "setop", "search", "segments"])
     n = int(2 ** rng.uniform(10, 25.5)) + int(rng.randint(0, 1000))
     if it % 7 == 0: n = int(2 ** rng.uniform(21, 26.3))   # more of the large sort's range
     if kind == "u32" and it % 23 == 0: n = (1 << 26) + int(rng.randint(1, 1 << 22))     # past 256 MiB: pointer stores
@@ -60,7 +63,7 @@ while time.time() < t_end and it < args.stop_after:
             else: rng.randint(1, 4)
         continue
     if verbose: print("it %d %s n=%d algo=%d bits=%d tile=%d msd2=%d dist=%s shift=%d" % (it, kind, n, algo, bits, tile, msd2_mode, dist, shift), flush=True)
-    if kind in ("u32", "soa", "kv", "soaw", "compact", "hist", "merge", "setop", "search"):
+    if kind in ("u32", "soa", "kv", "soaw", "compact", "hist", "merge", "setop", "search", "segments"):
         k = oracle.keys_u32(n, seed=it)
         if dist == "heavy": k = np.where(np.arange(n) % 10 != 0, (k >> np.uint32(8)) | np.uint32(0x37000000), k).astype(np.uint32)
         elif dist == "vals4096": k = (k >> np.uint32(20)) * np.uint32(0x00100801)
@@ -152,6 +155,27 @@ while time.time() < t_end and it < args.stop_after:
             c = a ^ np.uint32(0x80000000) if dt == np.int32 else a ^ np.where(a & np.uint32(0x80000000) != 0, np.uint32(0xffffffff), np.uint32(0x80000000))
             return ~c if desc else c
         assert np.array_equal(got, np.searchsorted(code(ss), code(x), side="right" if right else "left").astype(np.uint32)), (it, kind, m, nn, dt, desc, right, dist)
+    elif kind == "segments":   # every segment sorted on its own, against the stable lexsort on (segment, code)
+        sr = np.random.RandomState(args.seed + 19 * it)
+        n = min(n, 1 << 22); k = k[:n]
+        top = int(sr.choice([1, 2, 33, 4096, 4097, 100000]))
+        lens = np.minimum(np.floor(sr.uniform(1e-9, 1, size=n) ** -0.8), top) if sr.randint(0, 2) else sr.randint(0, top + 1, size=n)
+        lens = lens.astype(np.int64); lens[sr.randint(0, n, size=n // 8)] = 0      # runs of empty segments
+        S = min(int(np.searchsorted(np.cumsum(lens), n)) + 1, n); lens = lens[:S]; lens[-1] -= int(lens.sum()) - n
+        offs = np.concatenate([[0], np.cumsum(lens)]).astype(np.uint32)
+        dt, desc, glob = [np.int32, np.float32][sr.randint(0, 2)], bool(sr.randint(0, 2)), bool(sr.randint(0, 2))
+        bound = int(lens.max()); bound = int(sr.choice([bound, 0])) if bound <= 4096 else bound
+        d.setParam("debug.sort_segments_grid", int(sr.choice([0, 0, 1, 7, 300])))
+        kb = Buffer(d, n, dt); ko = Buffer(d, n, dt); ob = Buffer(d, S + 1, np.uint32); cnt = Buffer(d, 1, np.uint32)
+        kb.write(k.view(dt)); ob.write(offs)
+        out = p.sortSegments(d, kb, ob, S, maxSegment=bound, descending=desc, keysOut=ko, globalIndex=glob, oversizedOut=cnt)
+        gi, gk, over = out.toHost().astype(np.int64), ko.toHost().view(np.uint32), int(cnt.toHost()[0])
+        for b in (kb, ko, ob, cnt, out): b.release()
+        d.setParam("debug.sort_segments_grid", 0)
+        code = k ^ np.uint32(0x80000000) if dt == np.int32 else k ^ np.where(k & np.uint32(0x80000000) != 0, np.uint32(0xffffffff), np.uint32(0x80000000))
+        seg = np.repeat(np.arange(S), lens)
+        order = np.lexsort((~code if desc else code, seg))   # stable: ties by position
+        assert over == 0 and np.array_equal(gk, k[order]) and np.array_equal(gi, order if glob else order - offs[:-1].astype(np.int64)[seg]), (it, kind, n, S, top, dt, desc, glob, bound, dist)
     elif kind == "setop":   # a set operation on two sorted parts of the keys, against the oracle of the tests
         sr = np.random.RandomState(args.seed + 13 * it)
         n = min(n, 1 << 22)
