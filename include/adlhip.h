@@ -140,7 +140,9 @@ int adlhip_unmap(adlhip_device* dev, void* dptr, void* hptr, size_t bytes);
  *                 once for its largest batch; changing "sort.tile", "sort.digit_bits" or "sort.algo" later can
  *                 raise the requirement (the sort entry points re-check and fail loudly).
  * Data, tmp and work buffers of the sorts and partitions need 16-byte alignment and no more; a pointer that is not
- * 16-byte aligned is refused before anything is enqueued.  The work buffer's contents on entry are arbitrary. */
+ * 16-byte aligned is refused before anything is enqueued.  The work buffer's contents on entry are arbitrary.
+ * n beyond 0xFFF00000 -- the kernels index elements with 32 bits and keep 2^20 of head-room below 2^32 -- is refused by the scratch
+ * queries as it is by the sorts. */
 int adlhip_radix_sort_scratch_bytes(adlhip_device* dev, int elem_kind, size_t n,
                                     size_t* tmp_bytes, size_t* work_bytes);
 
@@ -690,12 +692,13 @@ int adlhip_bincount_typed(adlhip_device* dev, int key_type, const void* d_keys_i
  *     d_index_out[j]  its position in A || B: i for A[i], na + i for B[i]
  *   At least one output is given; each holds na + nb elements and every one of them is written.
  *
- * Contract.  na + nb < 2^32; either count may be 0 (the array of an empty input is not looked at).  The inputs are never written; A
+ * Contract.  na + nb <= 0xFFF00000, the limit of the sorts; either count may be 0 (the array of an empty input is not looked at).
+ * The inputs are never written; A
  * and B may overlap or be the same array.  No output may overlap an input, another output or d_work.  The outputs and d_work are
  * 16-byte aligned.  The INPUTS need only the alignment of their element (4 or 8 bytes; values: value_bytes): a tile's share of A
  * and of B starts at an arbitrary element anyway, so a view that starts at any element of a larger array is merged where it lies.
  * na + nb == 0 succeeds and enqueues nothing.  A NULL required pointer, a misaligned pointer, an overlap, an unknown key_type, order
- * or value_bytes, value arrays that do not agree with value_bytes, no output at all, na + nb >= 2^32 and a work buffer one byte
+ * or value_bytes, value arrays that do not agree with value_bytes, no output at all, na + nb beyond the limit and a work buffer one byte
  * short (the message names the needed size and adlhip_merge_scratch_bytes) fail before anything is enqueued, each with a message
  * that names the argument.  The call enqueues and returns: nothing data-dependent reaches the host (launch grids depend on na + nb
  * alone), nothing is remembered between calls, all state lives in d_work -- whose contents on entry are arbitrary -- and the handle
@@ -748,12 +751,12 @@ int adlhip_merge_typed(adlhip_device* dev, int key_type, int order,
  *   At least one output besides the count word is given.  Each given output holds cap elements: cap = na for intersection and
  *   difference, na + nb for union and symmetric difference.  Elements at S and beyond are never written.
  *
- * Contract.  That of adlhip_merge_typed: na + nb < 2^32; either count may be 0 (the array of an empty input is not looked at).  The
+ * Contract.  That of adlhip_merge_typed: na + nb <= 0xFFF00000; either count may be 0 (the array of an empty input is not looked at).  The
  * inputs are never written, need only the alignment of their element and may overlap or be the same array.  No output, nor the count
  * word, nor d_work may overlap an input or one another.  The outputs and d_work are 16-byte aligned, the count word 4-byte aligned.
  * na + nb == 0 succeeds and enqueues only a clear of the count word (d_work may then be NULL).  A NULL required pointer, a misaligned
  * pointer, an overlap, an unknown key_type, order, op or value_bytes, value arrays that do not agree with value_bytes, no output at
- * all, na + nb >= 2^32 and a work buffer one byte short (the message names the needed size and adlhip_set_op_scratch_bytes) fail
+ * all, na + nb beyond the limit and a work buffer one byte short (the message names the needed size and adlhip_set_op_scratch_bytes) fail
  * before anything is enqueued, each with a message that names the argument.  The call enqueues and returns: nothing data-dependent
  * reaches the host (launch grids depend on na + nb alone), nothing is remembered between calls, all state lives in d_work -- whose
  * contents on entry are arbitrary.  No kernel waits on another workgroup or uses an atomic to global memory.
@@ -844,7 +847,8 @@ int adlhip_segment_sort(adlhip_device* dev, int elem_kind, void* d_data, const u
  * -- Pprims.h:35, Pprims.cpp:122-179.  Exclusive prefix sum, 32-bit wrap-around.  dst may equal src.
  * h_sum_or_null: when non-NULL the grand total is copied there (stream-ordered; valid after
  * adlhip_sync(), like the reference's non-blocking read at Pprims.cpp:164-167).  No n < 1,048,576
- * limit (the reference silently returns for numBlocks >= 4096, Pprims.cpp:134-138). */
+ * limit (the reference silently returns for numBlocks >= 4096, Pprims.cpp:134-138); n <= 0xFFF00000, the limit of the sorts,
+ * beyond which both functions fail. */
 int adlhip_scan_scratch_bytes(adlhip_device* dev, size_t n, size_t* work_bytes);
 int adlhip_exclusive_scan_u32(adlhip_device* dev, uint32_t* d_dst, const uint32_t* d_src,
                               void* d_work, size_t work_bytes, size_t n, uint32_t* h_sum_or_null);

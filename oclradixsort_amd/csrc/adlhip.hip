@@ -1796,7 +1796,7 @@ int soa_wide_sort(adlhip_device* d, K* keys, V* vals, K* tmp_keys, V* tmp_vals, 
     uint64_t* pb = reinterpret_cast<uint64_t*>(w + L.off_pairs_b);
     void* kv = w + L.off_kv;
     const uint32_t nn = (uint32_t)n;
-    const uint32_t wgs = (uint32_t)std::min<size_t>((n + adlhip::kSoaNT - 1) / adlhip::kSoaNT, (size_t)d->prop.multiProcessorCount * 16);
+    const uint32_t wgs = (uint32_t)stride32_wgs(d->prop, n);
     int rc = launch(d, sizeof(K) == 4 ? "soa_pack_index_k32" : "soa_pack_index_k64", [&] {
         hipLaunchKernelGGL(adlhip::soa_pack_index_kernel<K>, dim3(wgs), dim3(adlhip::kSoaNT), 0, d->stream, (const K*)keys, pa, nn);
     });
@@ -1988,6 +1988,7 @@ int adlhip_radix_sort_scratch_bytes_for(adlhip_device* d, int elem_kind, size_t 
     const int max_bits = elem_kind == ADLHIP_ELEM_U64 ? 64 : 32;
     if (sort_bits < 4 || sort_bits > max_bits || (sort_bits & 3)) return fail("sort_bits must be a multiple of 4 in [4,%d], got %d", max_bits, sort_bits);
     if (level < 0 || level > 2) return fail("level must be 0 (minimum), 1 (full speed) or 2 (lean), got %d", level);
+    if (n > kMaxElems) return fail("n = %zu exceeds the supported maximum %zu", n, (size_t)kMaxElems);   // as the sorts themselves refuse it
     const size_t esz = (elem_kind == ADLHIP_ELEM_U32 || elem_kind == ADLHIP_ELEM_SOA32) ? 4 : 8;   // SoA: per array
     if (tmp_bytes) *tmp_bytes = align_up(n * esz, 256);
     if (work_bytes) *work_bytes = sort_work_bytes(d, elem_kind, n, sort_bits, level);
@@ -2039,6 +2040,7 @@ int adlhip_radix_sort_soa_scratch_bytes(adlhip_device* d, int key_bytes, int val
     if (!d) return fail("null device handle");
     if (soa_check_widths(key_bytes, value_bytes)) return ADLHIP_FAILURE;
     if (sort_bits < 4 || sort_bits > 8 * key_bytes || (sort_bits & 3)) return fail("sort_bits must be a multiple of 4 in [4,%d], got %d", 8 * key_bytes, sort_bits);
+    if (n > kMaxElems) return fail("n = %zu exceeds the supported maximum %zu", n, (size_t)kMaxElems);   // as the sorts themselves refuse it
     if (tmp_keys_bytes) *tmp_keys_bytes = align_up(n * (size_t)key_bytes, 256);
     if (tmp_vals_bytes) *tmp_vals_bytes = align_up(n * (size_t)value_bytes, 256);
     if (work_bytes) {
@@ -2098,6 +2100,9 @@ int adlhip_segment_sort(adlhip_device* d, int elem_kind, void* data, const uint3
 int adlhip_scan_scratch_bytes(adlhip_device* d, size_t n, size_t* work_bytes)
 {
     if (!d) return fail("null device handle");
+    // the sorts' limit.  (The kernels index with size_t, but one workgroup per tile passes HIP's 2^32 work-items per grid
+    // dimension at 2^36 elements, and nothing beyond kMaxElems has ever run.)
+    if (n > kMaxElems) return fail("scan: n = %zu exceeds the supported maximum %zu", n, (size_t)kMaxElems);
     const size_t blocks = (n + adlhip::kScanTile - 1) / adlhip::kScanTile;
     if (work_bytes) *work_bytes = align_up((blocks + 2) * 4, 256);
     return ADLHIP_SUCCESS;
@@ -2108,7 +2113,7 @@ int adlhip_exclusive_scan_u32(adlhip_device* d, uint32_t* dst, const uint32_t* s
 {
     if (bind(d)) return ADLHIP_FAILURE;
     size_t need = 0;
-    adlhip_scan_scratch_bytes(d, n, &need);
+    if (adlhip_scan_scratch_bytes(d, n, &need)) return ADLHIP_FAILURE;   // n beyond the limit
     if (work_bytes < need || !work) return fail("scan work buffer too small: %zu < %zu", work_bytes, need);
     uint32_t* partial = reinterpret_cast<uint32_t*>(work);
     if (n == 0) {
@@ -2117,7 +2122,6 @@ int adlhip_exclusive_scan_u32(adlhip_device* d, uint32_t* dst, const uint32_t* s
     }
     if (!dst || !src) return fail("null buffer passed to scan");
     const size_t blocks = (n + adlhip::kScanTile - 1) / adlhip::kScanTile;
-    if (blocks > 0x7fffffffull) return fail("scan: n too large");
     uint32_t* d_total = partial + blocks;   // grand total lives behind the block sums
     int rc;
     if (blocks <= 8) {

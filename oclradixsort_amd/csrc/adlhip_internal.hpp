@@ -8,6 +8,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdio>
 #include <map>
 #include <string>
@@ -172,6 +173,15 @@ int sort_elements(adlhip_device* d, int elem_kind, void* data, void* tmp, void* 
 int launch_scan_single(adlhip_device* d, const char* name, const uint32_t* src, uint32_t* dst, size_t n, uint32_t* d_total);
 
 constexpr size_t kMaxElems = 0xFFF00000ull;   // 32-bit element indices inside the kernels
+// Grid of the kernels that walk up to kMaxElems elements as `for (uint32_t i = ...; i < n; i += stride)` with stride = grid x 256 threads
+// (typed_kernels.hpp, soa_wide_kernels.hpp, select_gather_kernel): the last i below n is followed by i + stride < n + stride, which must
+// not pass 2^32, or the index wraps and the loop never ends.  So stride <= 2^32 - kMaxElems = 2^20: at most 4096 workgroups, which is
+// what 16 workgroups per CU come to on 256 CUs; a device with more CUs is held to the same grid.
+constexpr size_t kStride32MaxWgs = ((size_t(1) << 32) - kMaxElems) / 256;
+inline size_t stride32_wgs(const hipDeviceProp_t& prop, size_t n)
+{
+    return std::min(std::min((n + 255) / 256, (size_t)prop.multiProcessorCount * 16), kStride32MaxWgs);
+}
 inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
 #define HIPCHK(expr)                                                                           \

@@ -203,7 +203,7 @@ int typed_index_sort(adlhip_device* d, int kind, int desc, const U* keys_in, U* 
     uint64_t* pb = reinterpret_cast<uint64_t*>(w + L.off_pairs_b);
     void* kv = w + L.off_kv;
     const uint32_t nn = (uint32_t)n;
-    const uint32_t wgs = (uint32_t)std::min<size_t>((n + adlhip::kSoaNT - 1) / adlhip::kSoaNT, (size_t)d->prop.multiProcessorCount * 16);
+    const uint32_t wgs = (uint32_t)stride32_wgs(d->prop, n);
     int rc = launch(d, sizeof(U) == 4 ? "typed_pack_index_k32" : "typed_pack_index_k64", [&] {
 #define ADLHIP_PACK(KIND_, DESC_) \
     hipLaunchKernelGGL((adlhip::typed_pack_index_kernel<U, KIND_, DESC_>), dim3(wgs), dim3(adlhip::kSoaNT), 0, d->stream, keys_in, pa, nn)
@@ -400,7 +400,7 @@ int topk_by_select(adlhip_device* d, int kind, int desc, const U* keys_in, U* ke
     void* fwork = w + L.off_fwork;
     rc = sort_elements(d, ADLHIP_ELEM_U32, result, ptmp, fwork, L.fwork_bytes, k, 32);
     if (rc) return rc;
-    const uint32_t gwgs = (uint32_t)std::min<size_t>((k + adlhip::kSelNT - 1) / adlhip::kSelNT, (size_t)d->prop.multiProcessorCount * 16);
+    const uint32_t gwgs = (uint32_t)stride32_wgs(d->prop, k);
     rc = launch(d, "select_gather", [&] {
         hipLaunchKernelGGL((adlhip::select_gather_kernel<U>), dim3(gwgs), dim3(adlhip::kSelNT), 0, d->stream, keys_in, (const uint32_t*)result,
                            gkeys, kk);
@@ -1025,7 +1025,7 @@ static_assert(ADLHIP_MERGE_TILE == adlhip::kRedTile, "the header states the tile
 // grid of the tile kernel per CU at most ("debug.merge_grid" lowers it): its LDS (12 or 20 KiB) admits that many workgroups, and the
 // searches and the serial merge are chains of dependent LDS reads that only other waves hide
 constexpr int kMergeWgsPerCu = 8;
-constexpr size_t kMergeMaxElems = 0xFFFFFFFFull;   // na + nb: positions in A || B fit a dword
+constexpr size_t kMergeMaxElems = kMaxElems;   // na + nb: the limit of the sorts (positions in A || B fit a dword)
 
 // na + nb, refused when it does not fit
 int merge_total(const char* what, size_t na, size_t nb, size_t* n)
@@ -1351,7 +1351,7 @@ int adlhip_sort_typed_scratch_bytes(adlhip_device* d, int key_type, int mode, in
 {
     if (!d) return fail("null device handle");
     TypeInfo t;
-    if (key_type_info(key_type, ADLHIP_ORDER_ASCENDING, &t)) return ADLHIP_FAILURE;
+    if (key_type_info(key_type, ADLHIP_ORDER_ASCENDING, &t) || typed_check_n(n)) return ADLHIP_FAILURE;   // (n: as the sorts refuse it)
     if (mode < 0 || mode > 2) return fail("mode must be 0 (keys only), 1 (pairs) or 2 (argsort), got %d", mode);
     if (mode == 1 && soa_check_widths(t.bytes, value_bytes)) return ADLHIP_FAILURE;
     const bool partner_keys = mode == 0 || (mode == 1 && t.bytes == 8);   // (4-byte keys of pairs come out of the sorted pairs themselves)

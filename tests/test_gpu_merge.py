@@ -315,14 +315,14 @@ def test_work_buffer_contents_do_not_matter(dev):
 
 
 def test_scratch_bytes_follow_the_formula(dev):
-    for na, nb in ((0, 0), (1, 0), (T, 0), (T, 1), (1000, 5 * T), (63 * T, 0), (63 * T, 1), (1 << 31, (1 << 31) - 1)):
+    for na, nb in ((0, 0), (1, 0), (T, 0), (T, 1), (1000, 5 * T), (63 * T, 0), (63 * T, 1), (1 << 31, 0xFFF00000 - (1 << 31))):   # (the last: na + nb at the limit)
         tiles = (na + nb + T - 1) // T
         want = (4 * (tiles + 1) + 255) // 256 * 256
         for kt, vb in ((0, 0), (5, 8), (2, 4)):
             assert scratch_bytes(dev, kt, vb, na, nb) == want, (na, nb)
     sz = ctypes.c_size_t()
     lib = _lib.load()
-    for args in ((0, 0, 1 << 31, 1 << 31), (0, 0, 1 << 32, 0), (0, 0, 0, 1 << 40), (6, 0, 5, 5), (-1, 0, 5, 5), (0, 2, 5, 5), (0, 16, 5, 5)):
+    for args in ((0, 0, 1 << 31, 0xFFF00001 - (1 << 31)), (0, 0, 0xFFF00001, 0), (0, 0, 1 << 31, 1 << 31), (0, 0, 1 << 32, 0), (0, 0, 0, 1 << 40), (6, 0, 5, 5), (-1, 0, 5, 5), (0, 2, 5, 5), (0, 16, 5, 5)):
         assert lib.adlhip_merge_scratch_bytes(dev._h, *args, ctypes.byref(sz)) == 1, args
         assert lib_err()
 
