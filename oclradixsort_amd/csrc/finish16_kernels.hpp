@@ -21,7 +21,23 @@
 // SQ_LDS_IDX_ACTIVE is 186 K cycles per CU, 62 % of them bank conflicts of the returning atomics, the gathers and the 16-bit scatter
 // -- and what was tried on top changed nothing: 8 waves per SIMD instead of 5 (bounded batches of ranks and gathers, digits
 // recomputed: 63 VGPRs), a prologue of one round trip, a tile index of four instructions instead of eight (profiles/finish16_ab.txt,
-// finish16_pmc.txt).  Registers: <10,4> 73, <12,4> 86, <20,4> 125 VGPRs, no scratch.
+// finish16_pmc.txt).
+//
+// So the LDS cycles themselves had to go.  Where more than 8 bits are left to sort -- where the LSD code runs two passes -- ONE pass
+// (finish16_bins) places the keys by the top kFinish16BinBits = 9 bits of what is left, 512 bins, not stably (equal keys of a
+// key-only sort are indistinguishable), into a blocked layout: lane l owns 2 RR consecutive positions at an odd dword stride
+// (finish16_block_byte), so that every lane reads its own block back without a bank conflict.  A bin of uniform keys holds 2-3 keys,
+// the largest of a segment 7-8 (12 at most in simulation), and what shares a bin is ordered in registers: M rounds of odd-even
+// transposition on whole 16-bit keys, M = the segment's largest bin, v_min_u32 / v_max_u32 between neighbouring registers and one
+// DPP wave shift per direction for the pair that straddles two lanes.  The sorted block goes back to the tile and is read out in
+// rows of 64 for the same stores as before.  A segment whose keys all share one bin, or whose largest bin exceeds
+// kFinish16MaxRounds = 24, takes the LSD passes below on the keys it still holds; it has paid the ranking (one atomic per key) by
+// then.  64 Mi keys: 0.096 -> 0.076-0.077 ms per launch, SQ_LDS_IDX_ACTIVE 186 K -> 124 K cycles per CU, SQ_INSTS_VALU 37.3 M ->
+// 27.9 M (CHANGELOG.md, "the 16-bit finish places once and orders its bins in registers"; profiles/finish16_bins_ab.txt,
+// finish16_bins_pmc.txt).  At 403 MB in 0.077 ms the kernel now moves 5.3 TB/s: neither the LDS array (about two thirds busy) nor the
+// VALU is the limit any more.
+// LDS per wave: 256 (R2 | 1) bytes of tile + 2 KiB of counters = <10,4> 4864, <12,4> 5376, <20,4> 7424 bytes; the VGPRs, not the LDS,
+// bound the resident waves.  Registers: <10,4> 73, <12,4> 86, <20,4> 125 VGPRs (6, 5 and 4 waves per SIMD), no scratch, no FLAT load.
 // What the wave's LDS accesses may assume of each other is written down once, at finish16_lds_order().
 //
 // Reference behaviour: Tahoe/ClKernels/RadixSort32Kernels.cl:401-489 (sort4Bits1: the stable local sort of a block).
@@ -33,10 +49,15 @@
 
 namespace adlhip {
 
+constexpr int kFinish16BinBits = 9;      // B: the one LDS pass of the fast path places the keys by their top B bits
+constexpr int kFinish16MaxRounds = 24;   // a segment whose largest bin holds more keys takes the two LSD passes instead
+
 template <int R2>
 struct Finish16Cfg {
     static constexpr int CAP = 128 * R2;                     // keys a wave's tile holds
-    static constexpr size_t PER_WAVE = 2 * CAP + 256 * 4;    // tile + 256 counters
+    static constexpr int BINS = 1 << kFinish16BinBits;
+    static constexpr size_t TILE = 256 * (R2 | 1);           // bytes: 64 lanes x an odd number of dwords (finish16_block_byte)
+    static constexpr size_t PER_WAVE = TILE + 4 * BINS;      // tile + counters
 };
 
 __device__ __forceinline__ uint32_t finish16_index(uint32_t p) { return (p & ~127u) | ((p & 63u) << 1) | ((p >> 6) & 1u); }
@@ -47,6 +68,161 @@ __device__ __forceinline__ uint32_t finish16_index(uint32_t p) { return (p & ~12
 // back as uint32_t (strict aliasing lets the loads move above the stores), and the bin starts are written as one u32x4 per lane and
 // gathered by other lanes.  This point is that promise: no LDS access moves across it.  It emits no instruction.
 __device__ __forceinline__ void finish16_lds_order() { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); }
+
+// The blocked layout of the fast path: lane l owns the J = 2 RR consecutive positions [l J, (l + 1) J), RR dwords at a lane stride of
+// RR | 1 dwords.  An odd stride puts the 32 lanes of a ds_read_b32 / ds_write_b32 group on 32 different banks; 64 consecutive
+// positions (the scatter's pads, the striped read-out) touch at most 32 + 64 / J consecutive dwords.  Returns the byte offset.
+template <int RR>
+__device__ __forceinline__ uint32_t finish16_block_byte(uint32_t p)
+{
+    constexpr uint32_t J = 2 * RR;
+    if constexpr ((RR & 1) != 0) {
+        return 2u * p;
+    } else if constexpr ((J & (J - 1)) == 0) {
+        return 2u * p + 4u * (p / J);
+    } else {   // p / J for p < 64 J <= 2560 as a 24-bit multiply and a shift: exact while p (MAGIC J - 65536) < 65536
+        constexpr uint32_t MAGIC = (65536u + J - 1u) / J;
+        static_assert(64u * J * (MAGIC * J - 65536u) < 65536u, "the reciprocal is not exact over the tile");
+        return 2u * p + 4u * (__umul24(p, MAGIC) >> 16);
+    }
+}
+
+// the largest value of the wave, in every lane; all 64 lanes must be active (the DPP steps of wave_incl_scan_u32 with max for +)
+__device__ __forceinline__ uint32_t finish16_wave_max(uint32_t v)
+{
+    v = max(v, dpp_mov0<0x111, 0xf, 0xf>(v));
+    v = max(v, dpp_mov0<0x112, 0xf, 0xf>(v));
+    v = max(v, dpp_mov0<0x114, 0xf, 0xf>(v));
+    v = max(v, dpp_mov0<0x118, 0xf, 0xf>(v));
+    v = max(v, dpp_mov0<0x142, 0xa, 0xf>(v));
+    v = max(v, dpp_mov0<0x143, 0xc, 0xf>(v));
+    return (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
+}
+
+// The fast path (low_bits > 8, where the LSD code below runs two passes): ONE LDS pass places the keys by their top
+// min(B, low_bits) bits -- not stably: equal keys are indistinguishable -- into the blocked layout, every lane reads its J keys
+// back and M rounds of odd-even transposition in registers order what shares a bin (M = the largest bin of the segment: keys of
+// different bins are in order already, so every bin is a run of its own and a run of length L is sorted after L rounds, whichever
+// parity it starts on).  Positions [m, 64 J) are padded with 0xffff, which no compare-exchange moves below a key.  Returns false
+// with kp[] and the tile's meaning untouched when the LSD code has to run: every key in one bin, or M > kFinish16MaxRounds.
+template <int RR>
+__device__ __forceinline__ bool finish16_bins(const uint32_t (&kp)[RR], uint32_t* __restrict__ out, uint32_t m, int lane,
+                                              uint16_t* __restrict__ buf16, uint32_t* __restrict__ cnt, uint32_t low_bits, uint32_t hi,
+                                              bool a_lo, bool a_hi, bool b_lo, bool b_hi)
+{
+    constexpr int L = RR - 1, J = 2 * RR, S = RR | 1;
+    constexpr int NB = 1 << kFinish16BinBits, PL = NB / 64;   // counters, counters per lane
+    static_assert(PL % 4 == 0, "a lane scans its counters as u32x4");
+    const uint32_t bb = low_bits < (uint32_t)kFinish16BinBits ? low_bits : (uint32_t)kFinish16BinBits;
+    const uint32_t sh = low_bits - bb;   // <= 16 - B: the digit of either half lies inside its half
+    auto dlo = [&](uint32_t x) -> uint32_t { return (x >> sh) & (uint32_t)(NB - 1); };
+    auto dhi = [&](uint32_t x) -> uint32_t { return (x >> (16u + sh)) & (uint32_t)(NB - 1); };
+    {   // every key in one bin: all 64 lanes of every atomic would queue on ONE counter, and the LSD code knows what to skip
+        const uint32_t d0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)dlo(kp[0]));
+        bool same = true;
+#pragma unroll
+        for (int j = 0; j < RR; ++j) {
+            if (j < L || a_lo) same &= dlo(kp[j]) == d0;
+            if (j < L || a_hi) same &= dhi(kp[j]) == d0;
+        }
+        if (__all(same)) return false;
+    }
+    const u32x4 z = {0u, 0u, 0u, 0u};
+#pragma unroll
+    for (int q = 0; q < PL / 4; ++q) *reinterpret_cast<u32x4*>(cnt + PL * lane + 4 * q) = z;
+    uint32_t rk[RR];   // the two ranks of a register's keys, in whatever order the atomics of a bin were served
+#pragma unroll
+    for (int j = 0; j < RR; ++j) {
+        uint32_t r0 = 0u, r1 = 0u;
+        if (j < L || a_lo) r0 = __hip_atomic_fetch_add(&cnt[dlo(kp[j])], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+        if (j < L || a_hi) r1 = __hip_atomic_fetch_add(&cnt[dhi(kp[j])], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+        rk[j] = r0 | (r1 << 16);
+    }
+    const bool tail = low_bits > bb;   // otherwise the bin is the whole key
+    uint32_t rounds;
+    {   // counts -> bin starts, and the largest count
+        u32x4 c[PL / 4];
+        uint32_t sum = 0u, big = 0u;
+#pragma unroll
+        for (int q = 0; q < PL / 4; ++q) {
+            c[q] = *reinterpret_cast<const u32x4*>(cnt + PL * lane + 4 * q);
+            sum += c[q].x + c[q].y + c[q].z + c[q].w;
+            big = max(max(big, max(c[q].x, c[q].y)), max(c[q].z, c[q].w));
+        }
+        rounds = finish16_wave_max(big);
+        if (tail && rounds > (uint32_t)kFinish16MaxRounds) return false;
+        uint32_t run = wave_incl_scan_u32(sum) - sum;
+#pragma unroll
+        for (int q = 0; q < PL / 4; ++q) {
+            u32x4 o;
+            o.x = run;
+            o.y = o.x + c[q].x;
+            o.z = o.y + c[q].y;
+            o.w = o.z + c[q].z;
+            run = o.w + c[q].w;
+            *reinterpret_cast<u32x4*>(cnt + PL * lane + 4 * q) = o;
+        }
+    }
+    unsigned char* tile = reinterpret_cast<unsigned char*>(buf16);
+    const bool sort = tail && rounds > 1u;   // wave-uniform
+    if (sort) {   // the pads: positions [m, 64 J) are at most 128, since m > 128 (RR - 1)
+        const uint32_t p0 = m + (uint32_t)lane, p1 = p0 + 64u;
+        if (p0 < (uint32_t)(64 * J)) *reinterpret_cast<uint16_t*>(tile + finish16_block_byte<RR>(p0)) = (uint16_t)0xffffu;
+        if (p1 < (uint32_t)(64 * J)) *reinterpret_cast<uint16_t*>(tile + finish16_block_byte<RR>(p1)) = (uint16_t)0xffffu;
+    }
+    finish16_lds_order();   // the bin starts are written before any lane gathers one
+#pragma unroll
+    for (int j = 0; j < RR; ++j) {   // slot = bin start (a plain LDS read) + rank
+        uint32_t p0 = 0u, p1 = 0u;
+        if (j < L || a_lo) p0 = cnt[dlo(kp[j])] + (rk[j] & 0xffffu);
+        if (j < L || a_hi) p1 = cnt[dhi(kp[j])] + (rk[j] >> 16);
+        if (j < L || a_lo) *reinterpret_cast<uint16_t*>(tile + finish16_block_byte<RR>(p0)) = (uint16_t)kp[j];
+        if (j < L || a_hi) *reinterpret_cast<uint16_t*>(tile + finish16_block_byte<RR>(p1)) = (uint16_t)(kp[j] >> 16);
+    }
+    finish16_lds_order();   // the 16-bit stores of the tile are issued before any lane reads what others placed
+    if (sort) {
+        uint32_t* own = reinterpret_cast<uint32_t*>(tile) + S * lane;
+        uint32_t k[J];
+#pragma unroll
+        for (int j = 0; j < RR; ++j) {
+            const uint32_t w = own[j];
+            k[2 * j] = w & 0xffffu;
+            k[2 * j + 1] = w >> 16;
+        }
+        for (uint32_t r = 0u; r < rounds; r += 2u) {
+#pragma unroll
+            for (int j = 0; j < RR; ++j) {   // pairs (0,1), (2,3), ... inside the lane
+                const uint32_t a = k[2 * j], b = k[2 * j + 1];
+                k[2 * j] = min(a, b);
+                k[2 * j + 1] = max(a, b);
+            }
+            // pairs (1,2), (3,4), ... and the lane's last key against the next lane's first (wave_shl:1 / wave_shr:1: lane l
+            // receives from lane l + 1 / l - 1; the edge lanes keep `old`, which their key beats)
+            const uint32_t up = (uint32_t)__builtin_amdgcn_update_dpp((int)0xffffffffu, (int)k[0], 0x130, 0xf, 0xf, false);
+            const uint32_t dn = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)k[J - 1], 0x138, 0xf, 0xf, false);
+#pragma unroll
+            for (int j = 0; j < RR - 1; ++j) {
+                const uint32_t a = k[2 * j + 1], b = k[2 * j + 2];
+                k[2 * j + 1] = min(a, b);
+                k[2 * j + 2] = max(a, b);
+            }
+            k[J - 1] = min(k[J - 1], up);
+            k[0] = max(k[0], dn);
+        }
+#pragma unroll
+        for (int j = 0; j < RR; ++j) own[j] = k[2 * j] | (k[2 * j + 1] << 16);
+        finish16_lds_order();   // the sorted block is written before the striped read-out
+    }
+#pragma unroll
+    for (int i = 0; i < J; ++i) {   // row i = positions 64 i + lane: one dword per lane to consecutive addresses
+        if (i < 2 * L || (i == 2 * L ? b_lo : b_hi)) {
+            const uint32_t p = (uint32_t)(64 * i + lane);
+            const uint32_t v = *reinterpret_cast<const uint16_t*>(tile + finish16_block_byte<RR>(p));
+            __builtin_nontemporal_store(hi | v, out + p);
+        }
+    }
+    return true;
+}
 
 // RR row pairs; the first RR - 1 are full (m > 128 (RR - 1)), only the last is tested per lane
 template <int RR>
@@ -61,6 +237,7 @@ __device__ __forceinline__ void finish16_rows(const uint32_t* __restrict__ src32
 #pragma unroll
     for (int j = 0; j < RR; ++j)
         if (j < L || a_lo) kp[j] = __builtin_nontemporal_load(src32 + j * 64 + lane);
+    if (low_bits > 8u && finish16_bins<RR>(kp, out, m, lane, buf16, cnt, low_bits, hi, a_lo, a_hi, b_lo, b_hi)) return;
     bool placed = false;   // wave-uniform: the keys sit in position order (a pass has run)
     const int npass = ((int)low_bits + 7) / 8;
     int sb = 0;
@@ -165,7 +342,7 @@ __global__ __launch_bounds__(64 * WAVES) void wave_finish16_kernel(const uint16_
     const int w = (int)threadIdx.x >> 6;
     unsigned char* mine = smem + (size_t)w * C::PER_WAVE;
     uint16_t* __restrict__ buf16 = reinterpret_cast<uint16_t*>(mine);
-    uint32_t* __restrict__ cnt = reinterpret_cast<uint32_t*>(mine + 2 * C::CAP);
+    uint32_t* __restrict__ cnt = reinterpret_cast<uint32_t*>(mine + C::TILE);
     const uint32_t seg = (uint32_t)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * (uint32_t)WAVES + (uint32_t)w));
     if (seg >= num_segments) return;
     const uint32_t low_bits = (uint32_t)__builtin_amdgcn_readfirstlane((int)dyn[0]);
