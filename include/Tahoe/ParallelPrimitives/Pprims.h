@@ -236,6 +236,26 @@ public:
     void searchSorted(const adl::Device* device, const adl::Buffer<K>& sortedKeys, const adl::Buffer<K>& needles, adl::Buffer<u32>& posOut, int m,
                       int n, bool descending = false, bool right = false);
 
+    // join of sorted sequences: kind = ADLHIP_JOIN_INNER / LEFT / SEMI / ANTI of the first na keys of keysA with the first nb keys of
+    // keysB, each sorted in the order of sortKeys(descending), as pairs of positions: A[i] with m equal keys in B, the first at lo,
+    // gives the rows (i, lo) .. (i, lo + m - 1) (INNER), the same or (i, ADLHIP_JOIN_NONE) where m is 0 (LEFT), (i, lo) once where
+    // m > 0 (SEMI), (i, ADLHIP_JOIN_NONE) where m is 0 (ANTI), ordered by i, then by the position in B.  Keys are equal when their
+    // bits are.  Returns the exact number T of rows (it waits for it), whatever cap is; rows below min(T, cap) are written to indexA
+    // and indexB (cap elements each; either may be 0), nothing beyond.  cap = 0 without outputs only counts.  K: int, float, long
+    // long, double, u32, u64.  The inputs are left intact and may be the same Buffer.  A TYPE_HOST device runs a two-pointer loop
+    template <typename K>
+    unsigned long long joinSorted(const adl::Device* device, int kind, const adl::Buffer<K>& keysA, const adl::Buffer<K>& keysB,
+                                  adl::Buffer<u32>* indexA, adl::Buffer<u32>* indexB, int na, int nb, int cap, bool descending = false);
+
+    // expansion of runs (run-length decode, the inverse of runLengthEncode): counts[i] rows for every run i < numRuns, in the order of
+    // the runs; row o of run i, whose rows start at start[i] = counts[0] + .. + counts[i - 1], gets runOut[o] = i, rankOut[o] =
+    // o - start[i] and valuesOut[o] = values[i].  Returns T, the sum of the counts (it waits for it), whatever cap is; rows below
+    // min(T, cap) are written to whichever outputs are given (cap elements each), nothing beyond.  cap = 0 without outputs only
+    // counts.  V: int, float, long long, double, u32, u64.  A TYPE_HOST device runs a loop over the runs
+    template <typename V>
+    unsigned long long expandRuns(const adl::Device* device, const adl::Buffer<u32>& counts, const adl::Buffer<V>* values, adl::Buffer<u32>* runOut,
+                                  adl::Buffer<u32>* rankOut, adl::Buffer<V>* valuesOut, int numRuns, int cap);
+
     // sort along rows: every row of a rows x cols matrix sorted on its own, row r at element r * rowStride (0: cols), in the order of
     // sortKeys(descending) and stably: indexOut[r * cols + j] = column of the j-th element of row r, equal keys by ascending column in
     // both orders; keysOut[r * cols + j] = that key.  torch.sort(dim=-1, stable=True), cub::DeviceSegmentedSort on equal segments.  K:

@@ -829,6 +829,98 @@ int adlhip_search_sorted_typed(adlhip_device* dev, int key_type, int order, int 
                                const void* d_sorted, size_t m, const void* d_needles, size_t n,
                                uint32_t* d_pos_out);
 
+/* ---- expansion of runs and join of sorted sequences (no reference counterpart) ---- */
+
+/* adlhip_expand_runs: run-length decode, the inverse of adlhip_run_length_encode; torch.repeat_interleave; thrust's "expand".
+ *
+ * Result.  With start = the exclusive scan of the num_runs counts and T = their sum as a 64-bit number:
+ *     *d_num_out      T.  It stays on the device and is never clamped, so the caller learns the capacity it needs
+ *   and for every row o < min(T, cap), in whichever of the outputs is given:
+ *     d_run_out[o]    the run i with start[i] <= o < start[i] + d_counts_in[i]
+ *     d_rank_out[o]   o - start[i]
+ *     d_vals_out[o]   d_vals_in[i] (value_bytes 4 or 8; value_bytes 0: both value pointers are NULL)
+ *   Nothing is written at or beyond min(T, cap).  cap == 0 with no output is the counting call: only T is produced.
+ *
+ * Contract.  num_runs + cap <= 0xFFF00000.  The inputs are never written and need only the alignment of their element.  The outputs,
+ * the count word and d_work overlap no input and not one another; the outputs and d_work are 16-byte aligned, the count word 8-byte
+ * aligned.  num_runs == 0 enqueues only the clear of the count word (d_work may then be NULL).  A NULL required pointer, a
+ * misaligned pointer, an overlap, an unknown value_bytes, value arrays that do not agree with value_bytes, outputs given with
+ * cap == 0, cap > 0 with no output, sizes beyond the limit and a work buffer one byte short (the message names the needed size and
+ * adlhip_expand_scratch_bytes) fail before anything is enqueued, each with a message that names the argument.  The call enqueues and
+ * returns: nothing data-dependent reaches the host (launch grids depend on num_runs and cap alone), all state lives in d_work --
+ * whose contents on entry are arbitrary.  No kernel waits on another workgroup or uses an atomic to global memory.
+ *
+ * Work bytes:
+ *   adlhip_expand_scratch_bytes = (8 x 8 x CUs rounded up to 256) + (4 x num_runs rounded up to 256) + (4 x (tiles + 1) rounded up to 256),
+ *   tiles = ceil((num_runs + cap) / ADLHIP_JOIN_TILE): the rows per workgroup, the start of every run (saturated at cap), and the
+ *   number of runs in front of every tile boundary.
+ *
+ * Five launches (two for the counting call): the sums of the workgroups' chunks of counts; their scan, whose total is T; the starts;
+ * and a merge path of the starts with the row numbers, cut into tiles of ADLHIP_JOIN_TILE runs plus rows -- a partition and a row
+ * kernel that holds a tile's starts in LDS and stores its rows densely.  A tile is bounded whatever the counts: ten thousand zero
+ * counts in a row and one count of a million cost what their number of items costs. */
+#define ADLHIP_JOIN_TILE 2048
+int adlhip_expand_scratch_bytes(adlhip_device* dev, size_t num_runs, size_t cap, size_t* work_bytes);
+int adlhip_expand_runs(adlhip_device* dev, const uint32_t* d_counts_in, size_t num_runs,
+                       int value_bytes, const void* d_vals_in_or_null, size_t cap,
+                       uint32_t* d_run_out_or_null, uint32_t* d_rank_out_or_null, void* d_vals_out_or_null,
+                       uint64_t* d_num_out, void* d_work, size_t work_bytes);
+
+/* adlhip_join_sorted_typed: the join of two sequences that are already sorted, as pairs of positions: all m x n pairs of a key that
+ * occurs m times in A and n times in B, where ADLHIP_SETOP_INTERSECTION keeps min(m, n) elements.
+ *
+ * Order.  A (d_keys_a, na keys) and B (d_keys_b, nb keys) are each sorted in `order` as adlhip_set_op_typed asks: the codes
+ *   adlhip_key_encode(key_type, order) gives for their elements are non-decreasing.  Keys are equal when their bits are: -0 is not
+ *   +0, NaNs are equal by payload.  All six key types and both orders.
+ * Result.  For A[i] let lo_i be the number of codes of B below its code and m_i the number equal to it.  A[i] contributes
+ *     kind                rows                   content
+ *     ADLHIP_JOIN_INNER   m_i                    (i, lo_i + r), r = 0 .. m_i - 1
+ *     ADLHIP_JOIN_LEFT    max(m_i, 1)            as INNER; where m_i == 0, the one row (i, ADLHIP_JOIN_NONE)
+ *     ADLHIP_JOIN_SEMI    min(m_i, 1)            (i, lo_i)
+ *     ADLHIP_JOIN_ANTI    m_i == 0 ? 1 : 0       (i, ADLHIP_JOIN_NONE)
+ *   and the rows are ordered by i, then by the position in B: the result is fixed bit for bit.
+ *     *d_num_out            T, the exact 64-bit number of rows.  It can reach na x nb; it stays on the device and is never clamped
+ *     d_index_a_out[o]      the position in A of row o, o < min(T, cap)
+ *     d_index_b_out[o]      its position in B, or ADLHIP_JOIN_NONE
+ *   Rows below min(T, cap) are written to whichever of the two index outputs is given; nothing is written at or beyond that.
+ *   cap == 0 with both outputs NULL is the counting call: it skips the expansion launches.
+ *
+ * Contract.  na + nb <= 0xFFF00000 and na + cap <= 0xFFF00000.  The inputs are never written, need only the alignment of their element
+ * -- a view that starts at any element of a larger array is joined where it lies -- and may overlap or be the same array.  The
+ * outputs, the count word and d_work overlap no input and not one another; the outputs and d_work are 16-byte aligned, the count
+ * word 8-byte aligned.  na == 0 enqueues only the clear of the count word (d_work may then be NULL).  nb == 0 is legal (d_keys_b is
+ * then not looked at): INNER and SEMI give 0 rows, LEFT and ANTI na rows.  A NULL required pointer, a misaligned pointer, an
+ * overlap, an unknown key_type, order or kind, outputs given with cap == 0, cap > 0 with no output, sizes beyond the limits and a
+ * work buffer one byte short (the message names the needed size and adlhip_join_scratch_bytes) fail before anything is enqueued, each
+ * with a message that names the argument.  The call enqueues and returns: nothing data-dependent reaches the host (launch grids
+ * depend on na, nb and cap alone), nothing is remembered between calls, all state lives in d_work -- whose contents on entry are
+ * arbitrary.  No kernel waits on another workgroup or uses an atomic to global memory.
+ *
+ * Inputs that are NOT sorted: the rows and the count are unspecified, but the call succeeds and terminates, every read stays inside
+ * [A, A + na) and [B, B + nb), every written index_a is below na, every written index_b is below nb or is ADLHIP_JOIN_NONE, and no
+ * write lands at cap or beyond (join_kernels.hpp proves it: m_i is clamped to hi > lo ? hi - lo : 0, and the rows are expanded from
+ * the library's own scan of the counts).
+ *
+ * Work bytes:
+ *   adlhip_join_scratch_bytes = (8 x 8 x CUs rounded up to 256) + 2 x (4 x na rounded up to 256) + (4 x (tiles + 1) rounded up to 256),
+ *   tiles = ceil((na + cap) / ADLHIP_JOIN_TILE): the rows per workgroup, lo_i and the start of the rows of every element of A (saturated at
+ *   cap), and the number of elements of A in front of every tile boundary.  key_type and nb are checked and do not change the value.
+ *
+ * Five launches (two for the counting call).  The bounds: over tiles of ADLHIP_JOIN_TILE elements of A, every thread searches its 8
+ * elements in B for both sides as adlhip_search_sorted_typed does, from one table of at most 16 KiB of codes in LDS (4096 4-byte or
+ * 2048 8-byte codes, fewer where "debug.search_lds_keys" says so), and writes lo_i and the rows of A[i]; then the scan, the starts,
+ * the partition and the row kernel of adlhip_expand_runs, which adds lo_i to the rank. */
+#define ADLHIP_JOIN_INNER 0
+#define ADLHIP_JOIN_LEFT  1
+#define ADLHIP_JOIN_SEMI  2
+#define ADLHIP_JOIN_ANTI  3
+#define ADLHIP_JOIN_NONE  0xFFFFFFFFu
+int adlhip_join_scratch_bytes(adlhip_device* dev, int key_type, size_t na, size_t nb, size_t cap, size_t* work_bytes);
+int adlhip_join_sorted_typed(adlhip_device* dev, int key_type, int order, int kind,
+                             const void* d_keys_a, size_t na, const void* d_keys_b, size_t nb, size_t cap,
+                             uint32_t* d_index_a_out_or_null, uint32_t* d_index_b_out_or_null,
+                             uint64_t* d_num_out, void* d_work, size_t work_bytes);
+
 /* ---- segments finished in LDS (no reference counterpart) ------------------------------------- */
 
 /* Sorts, stably and in place, every segment [d_seg_start[s], d_seg_start[s + 1]) of an array of u32 keys
@@ -1024,6 +1116,9 @@ int adlhip_generate_keys(adlhip_device* dev, int elem_kind, void* dptr, size_t n
  *   "debug.search_grid" workgroups the kernel of adlhip_search_sorted_typed is launched with at most (0 [default]: 8 per CU, and never
  *                      more than tiles of needles; larger values change nothing); tests set it to make few workgroups take many
  *                      tiles.  The result does not depend on it
+ *   "debug.join_grid"  workgroups the bounds, sum, starts and row kernels of adlhip_join_sorted_typed and adlhip_expand_runs are launched
+ *                      with at most (0 [default]: 8 per CU; larger values change nothing); tests set it to make few workgroups take
+ *                      many tiles.  The result does not depend on it
  *   "debug.search_lds_keys" the capacity C of the table adlhip_search_sorted_typed keeps in LDS, in codes (2 .. 4096, default 4096; 0
  *                      sets the default); tests lower it to reach the two-level path and long searches in global memory with a
  *                      short sequence.  adlhip_get_param reports the capacity in force.  The result does not depend on it

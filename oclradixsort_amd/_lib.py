@@ -101,6 +101,10 @@ SIGNATURES = {
     "adlhip_set_op_scratch_bytes": (_I, [_VP, _I, _I, _SZ, _SZ, c_size_p]),
     "adlhip_set_op_typed": (_I, [_VP, _I, _I, _I, _VP, _VP, _SZ, _VP, _VP, _SZ, _I, _VP, _VP, _VP, _VP, _VP, _SZ]),
     "adlhip_search_sorted_typed": (_I, [_VP, _I, _I, _I, _VP, _SZ, _VP, _SZ, _VP]),
+    "adlhip_expand_scratch_bytes": (_I, [_VP, _SZ, _SZ, c_size_p]),
+    "adlhip_expand_runs": (_I, [_VP, _VP, _SZ, _I, _VP, _SZ, _VP, _VP, _VP, _VP, _VP, _SZ]),
+    "adlhip_join_scratch_bytes": (_I, [_VP, _I, _SZ, _SZ, _SZ, c_size_p]),
+    "adlhip_join_sorted_typed": (_I, [_VP, _I, _I, _I, _VP, _SZ, _VP, _SZ, _SZ, _VP, _VP, _VP, _VP, _SZ]),
     "adlhip_segment_sort": (_I, [_VP, _I, _VP, _VP, _SZ, _SZ, _I]),
     "adlhip_scan_scratch_bytes": (_I, [_VP, _SZ, c_size_p]),
     "adlhip_exclusive_scan_u32": (_I, [_VP, _VP, _VP, _VP, _SZ, _SZ, _VP]),

@@ -1,7 +1,7 @@
 // adlhip_internal.hpp -- what the library's three host units share.  handle.hip defines the runtime under everything: the error text,
 // the handle (create, teardown, sync, buffers, map / unmap, events, profiling), the probes and the knob table.  adlhip.hip defines
 // the sorts, the scan and the partitions, and what a handle owns for them (sort_state_create / sort_state_destroy, the idle table).
-// primitives.hip defines what is built on top of the sorts (typed sort, top-k, unique, reduce by key, scans, compaction, histograms, merges, set operations, sorted search).
+// primitives.hip defines what is built on top of the sorts (typed sort, top-k, unique, reduce by key, scans, compaction, histograms, merges, set operations, sorted search, joins).
 // Not installed; nothing here is ABI.
 #pragma once
 #include "../../include/adlhip.h"
@@ -81,6 +81,7 @@ struct adlhip_device {
     int merge_grid = 0;       // "debug.merge_grid": workgroups of the merge's tile kernel at most (0: kMergeWgsPerCu per CU)
     int setop_grid = 0;       // "debug.setop_grid": workgroups of the set operations' count and emit kernels at most (0: kSetopWgsPerCu per CU)
     int search_grid = 0;      // "debug.search_grid": workgroups of the sorted search at most (0: kSearchWgsPerCu per CU)
+    int join_grid = 0;        // "debug.join_grid": workgroups of the join's and the expansion's bounds, sum, starts and row kernels at most (0: kJoinWgsPerCu per CU)
     int persist_grid = 0;     // "debug.persist_grid": workgroups of the large sort's persistent passes, rounded up to a
                               // multiple of 8 (0: two per CU)
     // (with a rule of their own)

@@ -225,6 +225,7 @@ const Knob kKnobs[] = {
     {"debug.merge_grid", &adlhip_device::merge_grid, 0, kNoMax, "debug.merge_grid must be >= 0", nullptr},
     {"debug.setop_grid", &adlhip_device::setop_grid, 0, kNoMax, "debug.setop_grid must be >= 0", nullptr},
     {"debug.search_grid", &adlhip_device::search_grid, 0, kNoMax, "debug.search_grid must be >= 0", nullptr},
+    {"debug.join_grid", &adlhip_device::join_grid, 0, kNoMax, "debug.join_grid must be >= 0", nullptr},
     {"debug.persist_grid", &adlhip_device::persist_grid, 0, 4096, "debug.persist_grid must be in [0, 4096]", nullptr},
     // ---- with a rule of their own
     {"sort.digit_bits", &adlhip_device::digit_bits, 0, 0, nullptr,

@@ -1,5 +1,5 @@
 // primitives.hip -- the host side of what is built on top of the sorts: typed keys and argsort, top-k, row-wise top-k, sort along rows and within segments, unique /
-// run-length encode, reduce by key, typed scans, stream compaction, histograms, merges, set operations, sorted search.  No reference counterpart.  It reaches the sorts through adlhip_internal.hpp alone (sort_elements,
+// run-length encode, reduce by key, typed scans, stream compaction, histograms, merges, set operations, sorted search, joins.  No reference counterpart.  It reaches the sorts through adlhip_internal.hpp alone (sort_elements,
 // sort_work_bytes, soa_wide_layout) and never sees their kernels.
 #include "adlhip_internal.hpp"
 
@@ -26,9 +26,10 @@
 #include "merge_kernels.hpp"
 #include "setop_kernels.hpp"
 #include "search_kernels.hpp"
+#include "join_kernels.hpp"
 
 // instantiated in kernels_select.hip / kernels_toprows.hip / kernels_sortrows.hip / kernels_segments.hip / kernels_unique.hip / kernels_reduce.hip / kernels_scan.hip /
-// kernels_compact.hip / kernels_histogram.hip / kernels_merge.hip / kernels_setop.hip / kernels_search.hip; here they are only declared
+// kernels_compact.hip / kernels_histogram.hip / kernels_merge.hip / kernels_setop.hip / kernels_search.hip / kernels_join.hip; here they are only declared
 #ifndef ADLHIP_SINGLE_TU
 #define X(...) extern template __global__ __VA_ARGS__;
 #include "select_kernels.inc"
@@ -43,6 +44,7 @@
 #include "merge_kernels.inc"
 #include "setop_kernels.inc"
 #include "search_kernels.inc"
+#include "join_kernels.inc"
 #undef X
 #endif
 
@@ -1195,6 +1197,114 @@ int search_stage(adlhip_device* d, adlhip::RedCodec codec, int side, const U* so
     });
 }
 
+// ---- expansion of runs and join of sorted sequences (join_kernels.hpp) ---------------------------------------
+static_assert(ADLHIP_JOIN_TILE == adlhip::kRedTile, "the header states the tile of the join and the expansion");
+static_assert(ADLHIP_JOIN_INNER == adlhip::kJoinInner && ADLHIP_JOIN_LEFT == adlhip::kJoinLeft && ADLHIP_JOIN_SEMI == adlhip::kJoinSemi &&
+              ADLHIP_JOIN_ANTI == adlhip::kJoinAnti && ADLHIP_JOIN_NONE == adlhip::kJoinNone, "the kernels' kinds are the public ones");
+// grid of the bounds, sum, starts and row kernels per CU at most ("debug.join_grid" lowers it): what their LDS (16.1, 0, 8.1 and
+// 12 KiB) admits of the 8 waves a SIMD holds, as the merge's
+constexpr int kJoinWgsPerCu = 8;
+// Work of the expansion: [row totals: one u64 per workgroup of the largest grid], rounded up to 256 bytes; [start: one u32 per
+// element], rounded up to 256 bytes; [split: one u32 per boundary of the tiles of num_runs + cap items], rounded up to 256 bytes.  The
+// join puts [base: one u32 per element of A], rounded up to 256 bytes, between the first two
+size_t join_chunk_bytes(const adlhip_device* d)
+{
+    return align_up((size_t)d->prop.multiProcessorCount * kJoinWgsPerCu * 8, 256);
+}
+size_t expand_work_bytes(const adlhip_device* d, size_t n, size_t cap)
+{
+    return join_chunk_bytes(d) + align_up(4 * n, 256) + merge_work_bytes(n + cap);
+}
+size_t join_work_bytes(const adlhip_device* d, size_t na, size_t cap)
+{
+    return align_up(4 * na, 256) + expand_work_bytes(d, na, cap);
+}
+int expand_check_sizes(const char* what, const char* n_name, size_t n, size_t cap)
+{
+    if (n > kMaxElems || cap > kMaxElems - n)
+        return fail("%s: %s + cap = %zu + %zu exceeds the supported maximum %zu", what, n_name, n, cap, (size_t)kMaxElems);
+    return ADLHIP_SUCCESS;
+}
+
+// What follows the chunk totals of n > 0 elements: their scan, whose total goes to num_out, and -- with cap > 0 -- the starts (counts
+// may be start), the partition and the rows.  cs: the chunks the totals were taken over
+template <typename V>
+int expand_rows_stage(adlhip_device* d, const uint32_t* counts, size_t n, size_t cap, const ChunkSplit& cs, uint64_t* chunk, uint32_t* start,
+                      uint32_t* split, const uint32_t* base_in, const V* vals_in, uint32_t* run_out, uint32_t* rank_out, V* vals_out,
+                      uint64_t* num_out)
+{
+    int rc = launch(d, "expand_scan", [&] {
+        hipLaunchKernelGGL(adlhip::expand_scan_kernel, dim3(1), dim3(adlhip::kSelNT), 0, d->stream, chunk, cs.wgs, num_out);
+    });
+    if (rc || cap == 0) return rc;
+    const uint32_t un = (uint32_t)n, ucap = (uint32_t)cap;
+    rc = launch(d, "expand_starts", [&] {
+        hipLaunchKernelGGL(adlhip::expand_starts_kernel, dim3(cs.wgs), dim3(adlhip::kSelNT), 0, d->stream, counts, un, ucap, cs.tiles,
+                           cs.tiles_per_wg, (const uint64_t*)chunk, start);
+    });
+    if (rc) return rc;
+    const ChunkSplit rs = chunk_split(d, n + cap, (size_t)adlhip::kRedTile, kJoinWgsPerCu, d->join_grid);
+    const uint32_t pwgs = (rs.tiles + 1 + (uint32_t)adlhip::kSelNT - 1) / (uint32_t)adlhip::kSelNT;
+    rc = launch(d, "expand_partition", [&] {
+        hipLaunchKernelGGL(adlhip::expand_partition_kernel, dim3(pwgs), dim3(adlhip::kSelNT), 0, d->stream, (const uint32_t*)start, un,
+                           (const uint64_t*)num_out, ucap, rs.tiles, split);
+    });
+    if (rc) return rc;
+    constexpr bool has_vals = !std::is_same<V, adlhip::MergeNone>::value;
+    return launch(d, has_vals ? (sizeof(V) == 4 ? "expand_rows_v32" : "expand_rows_v64") : "expand_rows_v0", [&] {
+        hipLaunchKernelGGL((adlhip::expand_rows_kernel<V>), dim3(rs.wgs), dim3(adlhip::kSelNT), 0, d->stream, (const uint32_t*)start, un,
+                           (const uint64_t*)num_out, ucap, (const uint32_t*)split, rs.tiles, rs.tiles_per_wg, base_in, vals_in, run_out,
+                           rank_out, vals_out);
+    });
+}
+
+// the expansion of n > 0 counts
+template <typename V>
+int expand_stage(adlhip_device* d, const uint32_t* counts, size_t n, size_t cap, const V* vals_in, uint32_t* run_out, uint32_t* rank_out,
+                 V* vals_out, uint64_t* num_out, void* work)
+{
+    char* w = static_cast<char*>(work);
+    uint64_t* chunk = reinterpret_cast<uint64_t*>(w);
+    uint32_t* start = reinterpret_cast<uint32_t*>(w + join_chunk_bytes(d));
+    uint32_t* split = reinterpret_cast<uint32_t*>(w + join_chunk_bytes(d) + align_up(4 * n, 256));
+    const ChunkSplit cs = chunk_split(d, n, (size_t)adlhip::kRedTile, kJoinWgsPerCu, d->join_grid);
+    const int rc = launch(d, "expand_sum", [&] {
+        hipLaunchKernelGGL(adlhip::expand_sum_kernel, dim3(cs.wgs), dim3(adlhip::kSelNT), 0, d->stream, counts, (uint32_t)n, cs.tiles,
+                           cs.tiles_per_wg, chunk);
+    });
+    if (rc) return rc;
+    return expand_rows_stage<V>(d, counts, n, cap, cs, chunk, start, split, nullptr, vals_in, run_out, rank_out, vals_out, num_out);
+}
+
+// the join of na > 0 elements of A with nb >= 0 of B
+template <typename K>
+int join_stage(adlhip_device* d, adlhip::RedCodec codec, uint32_t kind, const K* a, size_t na, const K* b, size_t nb, size_t cap,
+               uint32_t* index_a, uint32_t* index_b, uint64_t* num_out, void* work)
+{
+    char* w = static_cast<char*>(work);
+    uint64_t* chunk = reinterpret_cast<uint64_t*>(w);
+    uint32_t* base = reinterpret_cast<uint32_t*>(w + join_chunk_bytes(d));
+    uint32_t* start = reinterpret_cast<uint32_t*>(w + join_chunk_bytes(d) + align_up(4 * na, 256));   // the counts, then their scan
+    uint32_t* split = reinterpret_cast<uint32_t*>(w + join_chunk_bytes(d) + 2 * align_up(4 * na, 256));
+    // the table of B: the search's, but never more than kJoinTableBytes of it
+    const size_t cap_keys = std::min((size_t)d->search_lds_keys, (size_t)adlhip::kJoinTableBytes / sizeof(K));
+    adlhip::SearchArgs sa;
+    sa.m = (uint32_t)nb;
+    sa.stride = (uint32_t)std::max<size_t>(1, (nb + cap_keys - 1) / cap_keys);
+    sa.samples = (uint32_t)((nb + sa.stride - 1) / sa.stride);   // <= cap_keys
+    sa.top_s = search_top_step(sa.samples);
+    sa.top_g = search_top_step(sa.stride);
+    const size_t lds = align_up((size_t)sa.samples * sizeof(K), 16);
+    const ChunkSplit cs = chunk_split(d, na, (size_t)adlhip::kRedTile, kJoinWgsPerCu, d->join_grid);
+    const int rc = launch(d, sizeof(K) == 4 ? "join_bounds_k32" : "join_bounds_k64", [&] {
+        hipLaunchKernelGGL((adlhip::join_bounds_kernel<K>), dim3(cs.wgs), dim3(adlhip::kSelNT), lds, d->stream, a, (uint32_t)na, b, sa, codec,
+                           kind, cs.tiles, cs.tiles_per_wg, base, start, chunk);
+    });
+    if (rc) return rc;
+    return expand_rows_stage<adlhip::MergeNone>(d, start, na, cap, cs, chunk, start, split, base, (const adlhip::MergeNone*)nullptr, index_a,
+                                                index_b, (adlhip::MergeNone*)nullptr, num_out);
+}
+
 // ---- sort within segments (segments_kernels.hpp) ---------------------------------------------------------------
 static_assert(ADLHIP_SEGMENT_INDEX_LOCAL == adlhip::kSegIndexLocal && ADLHIP_SEGMENT_INDEX_GLOBAL == adlhip::kSegIndexGlobal,
               "the header states the index bases");
@@ -1936,6 +2046,85 @@ int adlhip_search_sorted_typed(adlhip_device* d, int key_type, int order, int si
         return ADLHIP_FAILURE;
     const adlhip::RedCodec codec = {(uint32_t)t.kind, (uint32_t)order};
     return ADLHIP_BY_WIDTH(t.bytes, U, search_stage<U>(d, codec, side, (const U*)sorted, m, (const U*)needles, n, pos_out));
+}
+
+// ---- expansion of runs -----------------------------------------------------------------------------------
+int adlhip_expand_scratch_bytes(adlhip_device* d, size_t num_runs, size_t cap, size_t* work_bytes)
+{
+    if (!d) return fail("null device handle");
+    if (expand_check_sizes("expand scratch", "num_runs", num_runs, cap)) return ADLHIP_FAILURE;
+    if (work_bytes) *work_bytes = expand_work_bytes(d, num_runs, cap);
+    return ADLHIP_SUCCESS;
+}
+
+int adlhip_expand_runs(adlhip_device* d, const uint32_t* counts_in, size_t num_runs, int value_bytes, const void* vals_in, size_t cap,
+                       uint32_t* run_out, uint32_t* rank_out, void* vals_out, uint64_t* num_out, void* work, size_t work_bytes)
+{
+    const char* what = "expand runs";
+    if (bind(d) || merge_check_value_bytes(what, value_bytes) || expand_check_sizes(what, "num_runs", num_runs, cap)) return ADLHIP_FAILURE;
+    if (value_bytes == 0 && (vals_in || vals_out)) return fail("%s: value_bytes is 0, so d_vals_in and d_vals_out must be NULL", what);
+    if (cap == 0 && (run_out || rank_out || vals_out))
+        return fail("%s: cap is 0, so d_run_out, d_rank_out and d_vals_out must be NULL", what);
+    if (cap != 0 && !run_out && !rank_out && !vals_out)
+        return fail("%s: cap is %zu, so at least one of d_run_out, d_rank_out and d_vals_out must be given", what, cap);
+    if (vals_out && !vals_in) return fail("%s: d_vals_in is required with d_vals_out", what);
+    const size_t n = num_runs, vb = (size_t)value_bytes, va = vb ? vb : 1;
+    if (merge_check_buffers(what, {{counts_in, n * 4, "d_counts_in", n != 0, 4}, {vals_out ? vals_in : nullptr, n * vb, "d_vals_in", false, va}},
+                            {{run_out, cap * 4, "d_run_out", false, 16}, {rank_out, cap * 4, "d_rank_out", false, 16},
+                             {vals_out, cap * vb, "d_vals_out", false, 16}, {num_out, 8, "d_num_out", true, 8},
+                             {work, work_bytes, "d_work", n != 0, 16}}))
+        return ADLHIP_FAILURE;
+    const size_t need = n ? expand_work_bytes(d, n, cap) : 0;
+    if (work_bytes < need) return fail("work buffer too small: %zu < %zu (adlhip_expand_scratch_bytes)", work_bytes, need);
+    if (n == 0) {
+        HIPCHK(hipMemsetAsync(num_out, 0, 8, d->stream));
+        return ADLHIP_SUCCESS;
+    }
+    if (!vals_out)
+        return expand_stage<adlhip::MergeNone>(d, counts_in, n, cap, (const adlhip::MergeNone*)nullptr, run_out, rank_out,
+                                               (adlhip::MergeNone*)nullptr, num_out, work);
+    return ADLHIP_BY_WIDTH(value_bytes, V, expand_stage<V>(d, counts_in, n, cap, (const V*)vals_in, run_out, rank_out, (V*)vals_out, num_out, work));
+}
+
+// ---- join of sorted sequences ----------------------------------------------------------------------------
+int adlhip_join_scratch_bytes(adlhip_device* d, int key_type, size_t na, size_t nb, size_t cap, size_t* work_bytes)
+{
+    const char* what = "join scratch";
+    if (!d) return fail("null device handle");
+    TypeInfo t;
+    size_t n;
+    if (type_info("key_type", key_type, &t) || merge_total(what, na, nb, &n) || expand_check_sizes(what, "na", na, cap)) return ADLHIP_FAILURE;
+    if (work_bytes) *work_bytes = join_work_bytes(d, na, cap);
+    return ADLHIP_SUCCESS;
+}
+
+int adlhip_join_sorted_typed(adlhip_device* d, int key_type, int order, int kind, const void* keys_a, size_t na, const void* keys_b, size_t nb,
+                             size_t cap, uint32_t* index_a_out, uint32_t* index_b_out, uint64_t* num_out, void* work, size_t work_bytes)
+{
+    const char* what = "join";
+    TypeInfo t;
+    size_t n;
+    if (bind(d) || key_type_info(key_type, order, &t)) return ADLHIP_FAILURE;
+    if (kind < ADLHIP_JOIN_INNER || kind > ADLHIP_JOIN_ANTI)
+        return fail("%s: kind must be one of ADLHIP_JOIN_INNER .. ADLHIP_JOIN_ANTI (0..3), got %d", what, kind);
+    if (merge_total(what, na, nb, &n) || expand_check_sizes(what, "na", na, cap)) return ADLHIP_FAILURE;
+    if (cap == 0 && (index_a_out || index_b_out)) return fail("%s: cap is 0, so d_index_a_out and d_index_b_out must be NULL", what);
+    if (cap != 0 && !index_a_out && !index_b_out)
+        return fail("%s: cap is %zu, so at least one of d_index_a_out and d_index_b_out must be given", what, cap);
+    const size_t kb = (size_t)t.bytes;
+    if (merge_check_buffers(what, {{keys_a, na * kb, "d_keys_a", na != 0, kb}, {keys_b, nb * kb, "d_keys_b", nb != 0, kb}},
+                            {{index_a_out, cap * 4, "d_index_a_out", false, 16}, {index_b_out, cap * 4, "d_index_b_out", false, 16},
+                             {num_out, 8, "d_num_out", true, 8}, {work, work_bytes, "d_work", na != 0, 16}}))
+        return ADLHIP_FAILURE;
+    const size_t need = na ? join_work_bytes(d, na, cap) : 0;
+    if (work_bytes < need) return fail("work buffer too small: %zu < %zu (adlhip_join_scratch_bytes)", work_bytes, need);
+    if (na == 0) {
+        HIPCHK(hipMemsetAsync(num_out, 0, 8, d->stream));
+        return ADLHIP_SUCCESS;
+    }
+    const adlhip::RedCodec codec = {(uint32_t)t.kind, (uint32_t)order};
+    return ADLHIP_BY_WIDTH(t.bytes, K, join_stage<K>(d, codec, (uint32_t)kind, (const K*)keys_a, na, (const K*)keys_b, nb, cap, index_a_out,
+                                                    index_b_out, num_out, work));
 }
 
 }  // extern "C"

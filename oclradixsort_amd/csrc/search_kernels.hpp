@@ -74,6 +74,53 @@ __device__ __forceinline__ uint32_t search_step(F entry, uint32_t len, uint32_t 
     return (t <= len && below) ? t : pos;
 }
 
+// pos[e] = the bound of the code x[e] in sorted[0 .. a.m), the kRedItems searches side by side; s_tab: the table of a.samples codes in
+// LDS that search_table_load filled.  BOUNDS (1) .. (3).  The join's bounds kernel (join_kernels.hpp) runs it for both sides.
+template <typename U, int SIDE>
+__device__ __forceinline__ void search_bounds(const U* s_tab, const U* sorted, const SearchArgs a, const RedCodec codec, const U (&x)[kRedItems],
+                                              uint32_t (&pos)[kRedItems])
+{
+    const uint32_t m = a.m, S = a.samples, stride = a.stride;
+#pragma unroll
+    for (int e = 0; e < kRedItems; ++e) pos[e] = 0u;
+    for (uint32_t step = a.top_s; step; step >>= 1) {   // level 1, the 8 searches side by side: 8 independent LDS reads per step
+#pragma unroll
+        for (int e = 0; e < kRedItems; ++e) pos[e] = search_step<U, SIDE>([&](uint32_t i) { return s_tab[i]; }, S, step, x[e], pos[e]);
+    }
+    if (stride > 1u) {   // level 2 inside block pos[e]: 8 independent global loads per step.  BOUNDS (2)
+        uint32_t base[kRedItems], len[kRedItems];
+#pragma unroll
+        for (int e = 0; e < kRedItems; ++e) {
+            const uint64_t b = (uint64_t)pos[e] * (uint64_t)stride;
+            base[e] = b < (uint64_t)m ? (uint32_t)b : m;
+            len[e] = m - base[e] < stride ? m - base[e] : stride;
+            pos[e] = 0u;
+        }
+        for (uint32_t step = a.top_g; step; step >>= 1) {
+#pragma unroll
+            for (int e = 0; e < kRedItems; ++e)
+                pos[e] = search_step<U, SIDE>(
+                    [&](uint32_t i) {
+                        const uint32_t g = base[e] + i;   // (len 0: i = 2^32 - 1 and g = base - 1 = m - 1)
+                        return red_enc<U, kRedMax>(sorted[g < m ? g : m - 1u], codec);   // the clamp: [0, m - 1] whatever came before
+                    },
+                    len[e], step, x[e], pos[e]);
+        }
+#pragma unroll
+        for (int e = 0; e < kRedItems; ++e) pos[e] += base[e];   // <= base + len <= m.  BOUNDS (3)
+    }
+}
+
+// the table of the search to LDS: BOUNDS (0).  Every thread calls it; the caller passes a barrier before it searches.
+template <typename U>
+__device__ __forceinline__ void search_table_load(U* s_tab, const U* sorted, const SearchArgs a, const RedCodec codec)
+{
+    for (uint32_t i = threadIdx.x; i < a.samples; i += (uint32_t)kSelNT) {
+        const uint32_t g = i + 1u < a.samples ? (i + 1u) * a.stride - 1u : a.m - 1u;   // BOUNDS (0)
+        s_tab[i] = red_enc<U, kRedMax>(sorted[g], codec);
+    }
+}
+
 // pos_out[i] = the bound of needles[i] in sorted[0 .. a.m) for every i < n.  needles and pos_out are 16-byte aligned; sorted needs its
 // element's alignment only and may overlap needles.  Dynamic LDS: a.samples codes, rounded up to 16 bytes.
 template <typename U, int SIDE>
@@ -82,11 +129,7 @@ __global__ __launch_bounds__(kSelNT) void search_sorted_kernel(const U* sorted, 
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char s_search[];
     U* s_tab = reinterpret_cast<U*>(s_search);
-    const uint32_t m = a.m, S = a.samples, stride = a.stride;
-    for (uint32_t i = threadIdx.x; i < S; i += (uint32_t)kSelNT) {
-        const uint32_t g = i + 1u < S ? (i + 1u) * stride - 1u : m - 1u;   // BOUNDS (0)
-        s_tab[i] = red_enc<U, kRedMax>(sorted[g], codec);
-    }
+    search_table_load<U>(s_tab, sorted, a, codec);
     __syncthreads();
     const uint32_t t0 = blockIdx.x * tiles_per_wg;
     const uint32_t t1 = t0 + tiles_per_wg < tiles ? t0 + tiles_per_wg : tiles;
@@ -97,36 +140,8 @@ __global__ __launch_bounds__(kSelNT) void search_sorted_kernel(const U* sorted, 
         red_load<U>(needles, first, cnt, x);
         uint32_t pos[kRedItems];
 #pragma unroll
-        for (int e = 0; e < kRedItems; ++e) {
-            x[e] = red_enc<U, kRedMax>(x[e], codec);
-            pos[e] = 0u;
-        }
-        for (uint32_t step = a.top_s; step; step >>= 1) {   // level 1, the 8 searches side by side: 8 independent LDS reads per step
-#pragma unroll
-            for (int e = 0; e < kRedItems; ++e) pos[e] = search_step<U, SIDE>([&](uint32_t i) { return s_tab[i]; }, S, step, x[e], pos[e]);
-        }
-        if (stride > 1u) {   // level 2 inside block pos[e]: 8 independent global loads per step.  BOUNDS (2)
-            uint32_t base[kRedItems], len[kRedItems];
-#pragma unroll
-            for (int e = 0; e < kRedItems; ++e) {
-                const uint64_t b = (uint64_t)pos[e] * (uint64_t)stride;
-                base[e] = b < (uint64_t)m ? (uint32_t)b : m;
-                len[e] = m - base[e] < stride ? m - base[e] : stride;
-                pos[e] = 0u;
-            }
-            for (uint32_t step = a.top_g; step; step >>= 1) {
-#pragma unroll
-                for (int e = 0; e < kRedItems; ++e)
-                    pos[e] = search_step<U, SIDE>(
-                        [&](uint32_t i) {
-                            const uint32_t g = base[e] + i;   // (len 0: i = 2^32 - 1 and g = base - 1 = m - 1)
-                            return red_enc<U, kRedMax>(sorted[g < m ? g : m - 1u], codec);   // the clamp: [0, m - 1] whatever came before
-                        },
-                        len[e], step, x[e], pos[e]);
-            }
-#pragma unroll
-            for (int e = 0; e < kRedItems; ++e) pos[e] += base[e];   // <= base + len <= m.  BOUNDS (3)
-        }
+        for (int e = 0; e < kRedItems; ++e) x[e] = red_enc<U, kRedMax>(x[e], codec);
+        search_bounds<U, SIDE>(s_tab, sorted, a, codec, x, pos);
         if (cnt == (uint32_t)kRedItems) {
 #pragma unroll
             for (int u = 0; u < kRedItems / 4; ++u) {

@@ -25,6 +25,8 @@
     p.mergeKeys(device, a, b, out, na, nb)                 # the stable merge of two sorted key Buffers (mergePairs: with values)
     p.setOp(device, "intersection", a, b, out, na, nb)     # -> SetOpResult: also "union", "difference", "symmetric_difference"
     p.searchSorted(device, sortedKeys, needles, posOut, m, n)   # every needle's lower (right=True: upper) bound in m sorted keys
+    p.joinSorted(device, "inner", a, b, na, nb, cap=c, indexA=True, indexB=True)   # -> JoinResult: also "left", "semi", "anti"
+    p.expandRuns(device, counts, numRuns, cap=c, runOut=True)   # -> ExpandResult: run-length decode, repeat_interleave
 
 Like the reference object it owns lazily grown device scratch (m_u32WorkBuffer[0] = ping-pong data
 buffer, m_u32WorkBuffer[1] = histogram table; Pprims.h:44-45, Pprims.cpp:226-232, :332-337) and must be
@@ -74,6 +76,18 @@ SET_OPS = {"intersection": 0, "union": 1, "difference": 2, "symmetric_difference
 # What setOp returns: device Buffers (None where not asked).  `count` is a one-element uint32 Buffer that holds S, the number of result
 # elements; keys, values and index hold na (intersection, difference) or na + nb elements, of which the first S are written.
 SetOpResult = collections.namedtuple("SetOpResult", "keys values index count")
+
+# ADLHIP_JOIN_* (include/adlhip.h, "expansion of runs and join of sorted sequences"); JOIN_NONE stands for "no match" in indexB
+JOIN_KINDS = {"inner": 0, "left": 1, "semi": 2, "anti": 3}
+JOIN_NONE = 0xFFFFFFFF
+JOIN_MAX_ELEMS = 0xFFF00000
+
+# What joinSorted returns: device Buffers (None where not asked).  `count` is a one-element uint64 Buffer that holds T, the exact number
+# of rows, whatever cap was; indexA and indexB hold cap elements, of which the first min(T, cap) are written.
+JoinResult = collections.namedtuple("JoinResult", "indexA indexB count")
+
+# What expandRuns returns: the same for run, rank and values.
+ExpandResult = collections.namedtuple("ExpandResult", "run rank values count")
 
 # ADLHIP_HISTOGRAM_MAX_RANGE_BINS and ADLHIP_HISTOGRAM_TILE (include/adlhip.h, "histograms"): the most bins histogramRange takes, and
 # the elements of a tile of its count kernel (tests place their sizes around it)
@@ -937,6 +951,121 @@ class Pprims:
         check(_lib.load().adlhip_search_sorted_typed(device._h, kt, 1 if descending else 0, 1 if right else 0, sortedKeys.ptr(), m,
                                                      needles.ptr(), n, posOut.ptr()), what)
         return posOut
+
+    # -- join of sorted sequences and expansion of runs (no reference counterpart; include/adlhip.h adlhip_join_sorted_typed)
+    @staticmethod
+    def _count64(what, device, countOut, own):
+        if countOut is None:
+            countOut = Buffer(device, 1, np.uint64)
+            own.append(countOut)
+        return countOut
+
+    def joinSorted(self, device, kind, a, b, na, nb, cap=0, indexA=None, indexB=None, countOut=None, descending=False):
+        """The kind ("inner", "left", "semi", "anti") of join of the first na keys of `a` with the first nb keys of `b` -- Buffers of one
+        key type, each sorted in the order of sortKeys(descending) -- as pairs of positions -> JoinResult.  a[i] with m equal keys in
+        b, the first of them at lo, gives the rows (i, lo) .. (i, lo + m - 1) for "inner"; the same, or (i, JOIN_NONE) where m is 0, for
+        "left"; (i, lo) once where m > 0 for "semi"; (i, JOIN_NONE) where m is 0 for "anti".  Rows are ordered by i, then by the
+        position in b.  Keys are equal when their bits are.  result.count (one uint64, on the device; countOut to fill one) is T, the
+        exact number of rows, never clamped; rows below min(T, cap) are written to indexA / indexB (True for a new uint32 Buffer of cap
+        elements, or one to fill), nothing beyond.  cap = 0 without outputs only counts.  na + nb and na + cap are at most
+        0xFFF00000.  The inputs are left intact and may be the same Buffer.  Inputs that are not sorted give unspecified rows, never
+        an access outside the Buffers nor a position outside a and b.  Enqueues and returns; read result.count (toHost) to learn T."""
+        what = "joinSorted"
+        if device is None:
+            raise AdlHipError("%s needs a device" % what)
+        if kind not in JOIN_KINDS:
+            raise AdlHipError("%s: kind must be 'inner', 'left', 'semi' or 'anti', got %r" % (what, kind))
+        if a is None or b is None:
+            raise AdlHipError("%s: both inputs are required (an empty one with its count 0)" % what)
+        kt = self._key_type(a, what)
+        if np.dtype(b.dtype) != np.dtype(a.dtype):
+            raise AdlHipError("%s: a is %s, b %s" % (what, a.dtype, b.dtype))
+        na, nb, cap = int(na), int(nb), int(cap)
+        for name, buf, n in (("na", a, na), ("nb", b, nb)):
+            if n < 0 or buf.getSize() < n:
+                raise AdlHipError("%s: %s = %d outside [0, %d]" % (what, name, n, buf.getSize()))
+        if na + nb > JOIN_MAX_ELEMS:
+            raise AdlHipError("%s: na + nb = %d; at most %d elements" % (what, na + nb, JOIN_MAX_ELEMS))
+        if cap < 0 or na + cap > JOIN_MAX_ELEMS:
+            raise AdlHipError("%s: cap = %d outside [0, %d - na]" % (what, cap, JOIN_MAX_ELEMS))
+        asked = [v for v in (indexA, indexB) if v is not None and v is not False]
+        if cap == 0 and asked:
+            raise AdlHipError("%s: cap is 0, so indexA and indexB must not be given" % what)
+        if cap > 0 and not asked:
+            raise AdlHipError("%s: nothing asked (indexA or indexB) with cap = %d" % (what, cap))
+        if countOut is not None and (np.dtype(countOut.dtype) != np.uint64 or countOut.getSize() < 1):
+            raise AdlHipError("%s: countOut must hold one uint64 element" % what)
+        (ia, ib), own = self._runs_outputs(what, device, cap, [("indexA", indexA, cap), ("indexB", indexB, cap)])
+        try:
+            lib = _lib.load()
+            wb = ctypes.c_size_t()
+            check(lib.adlhip_join_scratch_bytes(device._h, kt, na, nb, cap, ctypes.byref(wb)), "adlhip_join_scratch_bytes")
+            self._scratch(device, 0, wb.value)
+            countOut = self._count64(what, device, countOut, own)
+
+            def p(buf):
+                return buf.ptr() if buf is not None else None
+            check(lib.adlhip_join_sorted_typed(device._h, kt, 1 if descending else 0, JOIN_KINDS[kind], p(a), na, p(b), nb, cap, p(ia), p(ib),
+                                               countOut.ptr(), self.m_work.ptr(), self.m_work.getSize()), what)
+        except AdlHipError:
+            for buf in own:
+                buf.release()
+            raise
+        return JoinResult(ia, ib, countOut)
+
+    def expandRuns(self, device, counts, numRuns, cap=0, values=None, runOut=None, rankOut=None, valuesOut=None, countOut=None):
+        """Run-length decode, the inverse of runLengthEncode: counts[i] rows for every run i < numRuns (`counts`: a uint32 Buffer), in the
+        order of the runs -> ExpandResult.  Row o of run i, whose rows start at start[i] = counts[0] + .. + counts[i - 1], gets
+        run[o] = i, rank[o] = o - start[i] and values[o] = values[i] (`values` and valuesOut: Buffers of one element type of 4 or 8
+        bytes).  result.count (one uint64, on the device; countOut to fill one) is T, the sum of the counts, never clamped; rows below
+        min(T, cap) are written to runOut / rankOut (True for a new uint32 Buffer of cap elements, or one to fill) and valuesOut (a
+        Buffer of cap elements), nothing beyond.  cap = 0 without outputs only counts.  numRuns + cap is at most 0xFFF00000.  The inputs
+        are left intact.  Enqueues and returns; read result.count (toHost) to learn T."""
+        what = "expandRuns"
+        if device is None:
+            raise AdlHipError("%s needs a device" % what)
+        if counts is None or not hasattr(counts, "getSize") or np.dtype(counts.dtype) != np.uint32:
+            raise AdlHipError("%s: counts must be a uint32 buffer" % what)
+        n, cap = int(numRuns), int(cap)
+        if n < 0 or counts.getSize() < n:
+            raise AdlHipError("%s: numRuns = %d outside [0, %d]" % (what, n, counts.getSize()))
+        if cap < 0 or n + cap > JOIN_MAX_ELEMS:
+            raise AdlHipError("%s: cap = %d outside [0, %d - numRuns]" % (what, cap, JOIN_MAX_ELEMS))
+        vbytes = 0
+        if values is not None or valuesOut is not None:
+            if values is None or valuesOut is None:
+                raise AdlHipError("%s: values and valuesOut go together" % what)
+            vbytes = np.dtype(values.dtype).itemsize
+            if vbytes not in (4, 8):
+                raise AdlHipError("%s: unsupported values type %s (4 or 8 bytes)" % (what, values.dtype))
+            if np.dtype(valuesOut.dtype) != np.dtype(values.dtype):
+                raise AdlHipError("%s: the values are %s and %s" % (what, values.dtype, valuesOut.dtype))
+            if values.getSize() < n or valuesOut.getSize() < cap:
+                raise AdlHipError("%s: the values must hold numRuns and %d elements" % (what, cap))
+        asked = [v for v in (runOut, rankOut, valuesOut) if v is not None and v is not False]
+        if cap == 0 and asked:
+            raise AdlHipError("%s: cap is 0, so runOut, rankOut and valuesOut must not be given" % what)
+        if cap > 0 and not asked:
+            raise AdlHipError("%s: nothing asked (runOut, rankOut or valuesOut) with cap = %d" % (what, cap))
+        if countOut is not None and (np.dtype(countOut.dtype) != np.uint64 or countOut.getSize() < 1):
+            raise AdlHipError("%s: countOut must hold one uint64 element" % what)
+        (run, rank), own = self._runs_outputs(what, device, cap, [("runOut", runOut, cap), ("rankOut", rankOut, cap)])
+        try:
+            lib = _lib.load()
+            wb = ctypes.c_size_t()
+            check(lib.adlhip_expand_scratch_bytes(device._h, n, cap, ctypes.byref(wb)), "adlhip_expand_scratch_bytes")
+            self._scratch(device, 0, wb.value)
+            countOut = self._count64(what, device, countOut, own)
+
+            def p(buf):
+                return buf.ptr() if buf is not None else None
+            check(lib.adlhip_expand_runs(device._h, p(counts), n, vbytes, p(values) if valuesOut is not None else None, cap, p(run), p(rank),
+                                         p(valuesOut), countOut.ptr(), self.m_work.ptr(), self.m_work.getSize()), what)
+        except AdlHipError:
+            for buf in own:
+                buf.release()
+            raise
+        return ExpandResult(run, rank, valuesOut, countOut)
 
     def copy(self, device, dst, src, n):
         """Pprims::copy (Pprims.cpp:31-67, commented out in the reference): first n elements of src -> dst."""

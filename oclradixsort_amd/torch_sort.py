@@ -20,6 +20,7 @@ back-end on torch's own stream.
     m = s.merge(a, b); m, v, i = s.merge(a, b, values=(va, vb), return_indices=True)   # torch.sort(torch.cat((a, b)), stable=True) of sorted a, b
     i = s.intersect(a, b); u = s.union(a, b); d = s.difference(a, b); x = s.symmetric_difference(a, b)   # of sorted a, b: numpy.intersect1d / union1d / setdiff1d / setxor1d
     pos = s.searchsorted(sorted_t, values, right=False); b = s.bucketize(values, boundaries)   # torch.searchsorted / torch.bucketize on a 1-D sorted tensor
+    ia, ib = s.join(a, b, how="inner"); r = s.repeat_interleave(values, repeats)    # all pairs of equal elements of sorted a, b; torch.repeat_interleave
     s.close()
 
 Always out of place and always stable.  The ONE difference from `torch.sort(t, stable=True)`: floats are ordered by
@@ -745,6 +746,102 @@ class TorchSorter:
         """numpy.setxor1d(a, b, assume_unique=True) of sorted 1-D tensors without duplicates; with duplicates thrust's
         set_symmetric_difference: |m - n| copies, the last of a's or of b's.  Everything else as intersect()."""
         return self._set_op("symmetric_difference", "symmetric_difference", a, b, descending, values, return_indices)
+
+    def join(self, a, b, how="inner", descending=False):
+        """The join of the sorted 1-D tensors a and b of one dtype, as int64 positions (index_a, index_b): every pair (i, j) with
+        a[i] equal to b[j] -- all m x n pairs of an element that occurs m times in a and n times in b, where intersect() keeps
+        min(m, n) elements -- ordered by i, then by j.  how="left" also keeps every a[i] without a match, once, with index_b -1;
+        how="semi" returns index_a alone, every i with a match once; how="anti" index_a alone, every i without one.  Elements are
+        equal when their bits are; the order the inputs must be sorted in is that of merge().  Inputs that are not sorted give
+        unspecified rows, never a position outside a and b.  Contiguous views at any element offset are read where they lie.  It
+        makes a counting call, ONE host read of the 8-byte row count, then the filling call; it raises ValueError when the rows
+        plus the elements of a exceed 0xFFF00000."""
+        from .pprims import JOIN_KINDS, JOIN_MAX_ELEMS
+        if how not in JOIN_KINDS:
+            raise ValueError("TorchSorter.join: how must be 'inner', 'left', 'semi' or 'anti', got %r" % (how,))
+        ka, kb = self._merge_input(a, "join"), self._merge_input(b, "join")
+        if ka.dtype != kb.dtype:
+            raise TypeError("TorchSorter.join: a is %s, b %s" % (ka.dtype, kb.dtype))
+        if torch.cuda.current_stream(self.torch_device).cuda_stream != self.raw_stream:
+            raise RuntimeError("TorchSorter: bound to the stream that was current at construction; another stream is current now")
+        na, nb = ka.numel(), kb.numel()
+        if na + nb > JOIN_MAX_ELEMS:
+            raise ValueError("TorchSorter.join: at most %d elements" % JOIN_MAX_ELEMS)
+        dev = ka.device
+        pairs = how in ("inner", "left")
+        total = 0
+        kdt = _NP_DTYPE[ka.dtype]
+        wa, wb = self._wrap(ka, kdt), self._wrap(kb, kdt)
+        if na:
+            count = torch.empty(1, dtype=torch.int64, device=dev)
+            self.pprims.joinSorted(self.device, how, wa, wb, na, nb, countOut=self._wrap(count, np.uint64), descending=bool(descending))
+            self.device.checkFault()
+            total = int(count.item())   # the one host read
+            if na + total > JOIN_MAX_ELEMS:
+                raise ValueError("TorchSorter.join: %d rows; the rows and the %d elements of a are at most %d together" % (total, na, JOIN_MAX_ELEMS))
+        ia32 = torch.empty(total, dtype=torch.int32, device=dev)   # uint32 positions in int32 tensors
+        ib32 = torch.empty(total, dtype=torch.int32, device=dev) if pairs else None
+        if total:
+            self.pprims.joinSorted(self.device, how, wa, wb, na, nb, cap=total, indexA=self._wrap(ia32, np.uint32),
+                                   indexB=self._wrap(ib32, np.uint32) if pairs else None, countOut=self._wrap(count, np.uint64),
+                                   descending=bool(descending))
+            self.device.checkFault()
+        ia = ia32.to(torch.int64) & 0xffffffff
+        if not pairs:
+            return ia
+        ib = ib32.to(torch.int64)
+        return ia, torch.where(ib == -1, ib, ib & 0xffffffff)   # ADLHIP_JOIN_NONE is -1 as an int32
+
+    def repeat_interleave(self, values, repeats, output_size=None):
+        """What torch.repeat_interleave(values, repeats, output_size=output_size) returns for a 1-D `values` of 4 or 8 bytes per
+        element and a 1-D integer tensor `repeats` of the same length (or of one element, or a Python int, for all of them):
+        values[i] repeated repeats[i] times, in order.  The repeats are non-negative and below 2^32, and their number plus their sum
+        is at most 0xFFF00000.  With output_size given -- it must be the sum of the repeats, as torch asks; that is not checked, and
+        elements behind the sum are left unwritten -- nothing reaches the host; without it there is a counting call and one host read
+        of the 8-byte sum.  Contiguous views at any element offset are read where they lie."""
+        from .pprims import JOIN_MAX_ELEMS
+        if not isinstance(values, torch.Tensor):
+            raise TypeError("TorchSorter: expected a torch.Tensor, got %s" % type(values).__name__)
+        if values.dim() != 1 or values.element_size() not in (4, 8) or values.is_complex():
+            raise TypeError("TorchSorter.repeat_interleave: values is 1-D with 4 or 8 bytes per element, got %s with %d dimensions"
+                            % (values.dtype, values.dim()))
+        if values.device != self.torch_device:
+            raise ValueError("TorchSorter: tensor is on %s, the sorter on %s" % (values.device, self.torch_device))
+        n = values.numel()
+        if isinstance(repeats, int) and not isinstance(repeats, bool):
+            repeats = torch.full((1,), repeats, dtype=torch.int64, device=values.device)
+        if not isinstance(repeats, torch.Tensor) or repeats.dtype not in (torch.int32, torch.int64, torch.int16, torch.int8, torch.uint8):
+            raise TypeError("TorchSorter.repeat_interleave: repeats is an integer tensor or a Python int")
+        if repeats.device != self.torch_device:
+            raise ValueError("TorchSorter: tensor is on %s, the sorter on %s" % (repeats.device, self.torch_device))
+        if repeats.dim() > 1 or repeats.numel() not in (1, n):
+            raise ValueError("TorchSorter.repeat_interleave: repeats has one element or one per element of values")
+        if torch.cuda.current_stream(self.torch_device).cuda_stream != self.raw_stream:
+            raise RuntimeError("TorchSorter: bound to the stream that was current at construction; another stream is current now")
+        counts = repeats.reshape(-1).expand(n).to(torch.int32).contiguous()   # uint32 counts in an int32 tensor
+        src = values.contiguous()
+        vdt = np.uint32 if values.element_size() == 4 else np.uint64
+        dev = values.device
+        wc, wv = self._wrap(counts, np.uint32), self._wrap(src, vdt)
+        if output_size is None:
+            total = 0
+            if n:
+                count = torch.empty(1, dtype=torch.int64, device=dev)
+                self.pprims.expandRuns(self.device, wc, n, countOut=self._wrap(count, np.uint64))
+                self.device.checkFault()
+                total = int(count.item())   # the one host read
+        else:
+            total = int(output_size)
+            if total < 0:
+                raise ValueError("TorchSorter.repeat_interleave: output_size is negative")
+        if n + total > JOIN_MAX_ELEMS:
+            raise ValueError("TorchSorter.repeat_interleave: %d elements from %d; at most %d together" % (total, n, JOIN_MAX_ELEMS))
+        out = torch.empty(total, dtype=values.dtype, device=dev)
+        if total and n:
+            count = torch.empty(1, dtype=torch.int64, device=dev)
+            self.pprims.expandRuns(self.device, wc, n, cap=total, values=wv, valuesOut=self._wrap(out, vdt), countOut=self._wrap(count, np.uint64))
+            self.device.checkFault()
+        return out
 
     def searchsorted(self, sorted_sequence, values, right=False, side=None, out_int32=False, descending=False):
         """What torch.searchsorted(sorted_sequence, values, right=right, side=side, out_int32=out_int32) returns for a 1-D

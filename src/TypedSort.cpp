@@ -12,7 +12,8 @@
 // adlhip_histogram_range_typed / adlhip_bincount_typed, or a plain loop.  Pprims::mergeKeys / mergePairs: adlhip_merge_typed, or a
 // plain two-pointer loop in which a tie takes the first input.  Pprims::searchSorted: adlhip_search_sorted_typed, or a binary search
 // per needle.  Pprims::setOp: adlhip_set_op_typed (it waits for the count), or
-// thrust's two-pointer loops.
+// thrust's two-pointer loops.  Pprims::joinSorted / expandRuns: adlhip_join_sorted_typed / adlhip_expand_runs (they wait for the
+// count), or a two-pointer loop / a loop over the runs.
 #include <Tahoe/ParallelPrimitives/Pprims.h>
 
 #include <algorithm>
@@ -1106,6 +1107,148 @@ TAHOE_SEARCH(double)
 TAHOE_SEARCH(u32)
 TAHOE_SEARCH(u64)
 #undef TAHOE_SEARCH
+
+// ---- join of sorted sequences: adlhip_join_sorted_typed, or a two-pointer loop ----
+template <typename K>
+unsigned long long Pprims::joinSorted(const adl::Device* device, int kind, const adl::Buffer<K>& keysA, const adl::Buffer<K>& keysB,
+                                      adl::Buffer<u32>* indexA, adl::Buffer<u32>* indexB, int na, int nb, int cap, bool descending)
+{
+    ADLASSERT(na >= 0 && nb >= 0 && cap >= 0);
+    ADLASSERT(kind >= ADLHIP_JOIN_INNER && kind <= ADLHIP_JOIN_ANTI);
+    ADLASSERT((long long)na + nb <= 0x7fffffffLL && (long long)na + cap <= 0x7fffffffLL);   // (the facade counts in int)
+    ADLASSERT(cap ? (indexA || indexB) : (!indexA && !indexB));
+    if (na <= 0 || nb < 0 || cap < 0 || (long long)na + nb > 0x7fffffffLL || (long long)na + cap > 0x7fffffffLL) return 0;
+    if (kind < ADLHIP_JOIN_INNER || kind > ADLHIP_JOIN_ANTI || (cap ? (!indexA && !indexB) : (indexA || indexB))) return 0;
+    ADLASSERT(device != 0);
+    ADLASSERT((adl::u64)na <= keysA.getSize() && (adl::u64)nb <= keysB.getSize() && (!indexA || (adl::u64)cap <= indexA->getSize()) &&
+              (!indexB || (adl::u64)cap <= indexB->getSize()));
+    if (!onDevice(device)) {
+        ADLASSERT(device->getType() == adl::TYPE_HOST);   // a HIP device never falls back to the CPU
+        if (device->getType() != adl::TYPE_HOST) return 0;
+        K* a = keysA.getHostPtr(na);
+        K* b = nb ? keysB.getHostPtr(nb) : 0;
+        u32* ia = indexA ? indexA->getHostPtr(cap) : 0;
+        u32* ib = indexB ? indexB->getHostPtr(cap) : 0;
+        adl::DeviceUtils::waitForCompletion(device);
+        unsigned long long total = 0;
+        int lo = 0;
+        for (int i = 0; i < na; ++i) {
+            while (lo < nb && ordinal(b[lo], descending) < ordinal(a[i], descending)) ++lo;   // (A is sorted: lo only moves on)
+            int m = 0;
+            while (lo + m < nb && ordinal(b[lo + m], descending) == ordinal(a[i], descending)) ++m;
+            const int rows = kind == ADLHIP_JOIN_INNER ? m : kind == ADLHIP_JOIN_LEFT ? (m ? m : 1) : kind == ADLHIP_JOIN_SEMI ? (m ? 1 : 0) : (m ? 0 : 1);
+            for (int r = 0; r < rows && total + (unsigned long long)r < (unsigned long long)cap; ++r) {
+                if (ia) ia[total + r] = (u32)i;
+                if (ib) ib[total + r] = m && kind != ADLHIP_JOIN_ANTI ? (u32)(lo + r) : ADLHIP_JOIN_NONE;
+            }
+            total += (unsigned long long)rows;
+        }
+        keysA.returnHostPtr(a);
+        if (b) keysB.returnHostPtr(b);
+        if (ia) indexA->returnHostPtr(ia);
+        if (ib) indexB->returnHostPtr(ib);
+        adl::DeviceUtils::waitForCompletion(device);
+        return total;
+    }
+    size_t wb = 0;
+    const int rcq = adlhip_join_scratch_bytes(device->hip(), KeyTraits<K>::TYPE, (size_t)na, (size_t)nb, (size_t)cap, &wb);
+    ADLASSERT(rcq == ADLHIP_SUCCESS);
+    reserve(device, 16, wb);   // m_tmp holds the count word
+    const int rc = adlhip_join_sorted_typed(device->hip(), KeyTraits<K>::TYPE, descending ? ADLHIP_ORDER_DESCENDING : ADLHIP_ORDER_ASCENDING, kind,
+                                            keysA.m_ptr, (size_t)na, nb ? keysB.m_ptr : 0, (size_t)nb, (size_t)cap,
+                                            indexA ? (uint32_t*)indexA->m_ptr : 0, indexB ? (uint32_t*)indexB->m_ptr : 0, (uint64_t*)m_tmp->m_ptr,
+                                            m_work->m_ptr, (size_t)m_work->getSize());
+    if (rc != ADLHIP_SUCCESS) TH_LOG_ERROR("Pprims::joinSorted: %s\n", adlhip_last_error());
+    ADLASSERT(rc == ADLHIP_SUCCESS);
+    if (rc != ADLHIP_SUCCESS) return 0;
+    unsigned char word[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    m_tmp->read(word, 8);
+    adl::DeviceUtils::waitForCompletion(device);
+    unsigned long long total = 0;
+    memcpy(&total, word, 8);
+    return total;
+}
+
+#define TAHOE_JOIN(K)                                                                                                                     \
+    template unsigned long long Pprims::joinSorted<K>(const adl::Device*, int, const adl::Buffer<K>&, const adl::Buffer<K>&, adl::Buffer<u32>*, \
+                                                      adl::Buffer<u32>*, int, int, int, bool);
+TAHOE_JOIN(int)
+TAHOE_JOIN(float)
+TAHOE_JOIN(long long)
+TAHOE_JOIN(double)
+TAHOE_JOIN(u32)
+TAHOE_JOIN(u64)
+#undef TAHOE_JOIN
+
+// ---- expansion of runs: adlhip_expand_runs, or a loop over the runs ----
+template <typename V>
+unsigned long long Pprims::expandRuns(const adl::Device* device, const adl::Buffer<u32>& counts, const adl::Buffer<V>* values, adl::Buffer<u32>* runOut,
+                                      adl::Buffer<u32>* rankOut, adl::Buffer<V>* valuesOut, int numRuns, int cap)
+{
+    ADLASSERT(numRuns >= 0 && cap >= 0 && (long long)numRuns + cap <= 0x7fffffffLL);
+    ADLASSERT(cap ? (runOut || rankOut || valuesOut) : (!runOut && !rankOut && !valuesOut));
+    ADLASSERT(!valuesOut || values);
+    if (numRuns <= 0 || cap < 0 || (long long)numRuns + cap > 0x7fffffffLL || (valuesOut && !values)) return 0;
+    if (cap ? (!runOut && !rankOut && !valuesOut) : (runOut || rankOut || valuesOut)) return 0;
+    ADLASSERT(device != 0);
+    ADLASSERT((adl::u64)numRuns <= counts.getSize() && (!valuesOut || (adl::u64)numRuns <= values->getSize()) &&
+              (!runOut || (adl::u64)cap <= runOut->getSize()) && (!rankOut || (adl::u64)cap <= rankOut->getSize()) &&
+              (!valuesOut || (adl::u64)cap <= valuesOut->getSize()));
+    if (!onDevice(device)) {
+        ADLASSERT(device->getType() == adl::TYPE_HOST);   // a HIP device never falls back to the CPU
+        if (device->getType() != adl::TYPE_HOST) return 0;
+        u32* c = counts.getHostPtr(numRuns);
+        V* v = valuesOut ? values->getHostPtr(numRuns) : 0;
+        u32* run = runOut ? runOut->getHostPtr(cap) : 0;
+        u32* rank = rankOut ? rankOut->getHostPtr(cap) : 0;
+        V* vout = valuesOut ? valuesOut->getHostPtr(cap) : 0;
+        adl::DeviceUtils::waitForCompletion(device);
+        unsigned long long total = 0;
+        for (int i = 0; i < numRuns; ++i) {
+            for (u32 r = 0; r < c[i] && total + r < (unsigned long long)cap; ++r) {
+                if (run) run[total + r] = (u32)i;
+                if (rank) rank[total + r] = r;
+                if (vout) vout[total + r] = v[i];
+            }
+            total += c[i];
+        }
+        counts.returnHostPtr(c);
+        if (v) values->returnHostPtr(v);
+        if (run) runOut->returnHostPtr(run);
+        if (rank) rankOut->returnHostPtr(rank);
+        if (vout) valuesOut->returnHostPtr(vout);
+        adl::DeviceUtils::waitForCompletion(device);
+        return total;
+    }
+    size_t wb = 0;
+    const int rcq = adlhip_expand_scratch_bytes(device->hip(), (size_t)numRuns, (size_t)cap, &wb);
+    ADLASSERT(rcq == ADLHIP_SUCCESS);
+    reserve(device, 16, wb);   // m_tmp holds the count word
+    const int rc = adlhip_expand_runs(device->hip(), (const uint32_t*)counts.m_ptr, (size_t)numRuns, valuesOut ? (int)sizeof(V) : 0,
+                                      valuesOut ? values->m_ptr : 0, (size_t)cap, runOut ? (uint32_t*)runOut->m_ptr : 0,
+                                      rankOut ? (uint32_t*)rankOut->m_ptr : 0, valuesOut ? valuesOut->m_ptr : 0, (uint64_t*)m_tmp->m_ptr,
+                                      m_work->m_ptr, (size_t)m_work->getSize());
+    if (rc != ADLHIP_SUCCESS) TH_LOG_ERROR("Pprims::expandRuns: %s\n", adlhip_last_error());
+    ADLASSERT(rc == ADLHIP_SUCCESS);
+    if (rc != ADLHIP_SUCCESS) return 0;
+    unsigned char word[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    m_tmp->read(word, 8);
+    adl::DeviceUtils::waitForCompletion(device);
+    unsigned long long total = 0;
+    memcpy(&total, word, 8);
+    return total;
+}
+
+#define TAHOE_EXPAND(V)                                                                                                                     \
+    template unsigned long long Pprims::expandRuns<V>(const adl::Device*, const adl::Buffer<u32>&, const adl::Buffer<V>*, adl::Buffer<u32>*, \
+                                                      adl::Buffer<u32>*, adl::Buffer<V>*, int, int);
+TAHOE_EXPAND(int)
+TAHOE_EXPAND(float)
+TAHOE_EXPAND(long long)
+TAHOE_EXPAND(double)
+TAHOE_EXPAND(u32)
+TAHOE_EXPAND(u64)
+#undef TAHOE_EXPAND
 
 #define TAHOE_TYPED(T)                                                                                                              \
     void Pprims::sortKeys(const adl::Device* device, const adl::Buffer<T>& inout, int n, bool descending)                         \

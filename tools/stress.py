@@ -15,7 +15,9 @@ one a sorted search (the keys cut into a sequence, sorted by the library as int3
 ones and elements of the sequence --, either side, random table capacity and grid knob, checked against numpy.searchsorted on the codes),
 one a sort within segments (the keys as int32 or float32 in either order, cut into segments of uniform or heavy-tailed lengths with runs
 of empty ones, on the segment kernel or the flat path with a random grid knob and index base, checked against one numpy lexsort on
-(segment, code)).
+(segment, code)),
+one a join (the keys folded and cut in two as for the set operations, a random kind, capacity and "debug.join_grid", checked against
+tests/join_oracle.py), one an expansion of runs (counts with stretches of zeros and a few long runs, 8-byte values along).
    python tools/stress.py [--seconds 60]"""
 import argparse, os, sys, time
 import numpy as np
@@ -24,6 +26,7 @@ import oracle
 import ctypes
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
 import setop_oracle   # the numpy oracle of the set operation tests
+import join_oracle    # ... and of the join and expansion tests
 from oclradixsort_amd import Buffer, DeviceUtils, Pprims, _lib
 from oclradixsort_amd._lib import check
 ap = argparse.ArgumentParser(); ap.add_argument("--seconds", type=float, default=60.0)
@@ -44,7 +47,7 @@ def checks(a):
     return int(a64.sum(dtype=np.uint64)), int(np.bitwise_xor.reduce(a64)) if a.size else 0
 while time.time() < t_end and it < args.stop_after:
     it += 1
-    kind = rng.choice(["u32", "kv", "u64", "soa", "soaw", "compact", "hist", "merge", "setop", "search", "segments"])
+    kind = rng.choice(["u32", "kv", "u64", "soa", "soaw", "compact", "hist", "merge", "setop", "search", "segments", "join", "expand"])
     n = int(2 ** rng.uniform(10, 25.5)) + int(rng.randint(0, 1000))
     if it % 7 == 0: n = int(2 ** rng.uniform(21, 26.3))   # more of the large sort's range
     if kind == "u32" and it % 23 == 0: n = (1 << 26) + int(rng.randint(1, 1 << 22))     # past 256 MiB: pointer stores
@@ -63,7 +66,7 @@ while time.time() < t_end and it < args.stop_after:
             else: rng.randint(1, 4)
         continue
     if verbose: print("it %d %s n=%d algo=%d bits=%d tile=%d msd2=%d dist=%s shift=%d" % (it, kind, n, algo, bits, tile, msd2_mode, dist, shift), flush=True)
-    if kind in ("u32", "soa", "kv", "soaw", "compact", "hist", "merge", "setop", "search", "segments"):
+    if kind in ("u32", "soa", "kv", "soaw", "compact", "hist", "merge", "setop", "search", "segments", "join", "expand"):
         k = oracle.keys_u32(n, seed=it)
         if dist == "heavy": k = np.where(np.arange(n) % 10 != 0, (k >> np.uint32(8)) | np.uint32(0x37000000), k).astype(np.uint32)
         elif dist == "vals4096": k = (k >> np.uint32(20)) * np.uint32(0x00100801)
@@ -198,6 +201,55 @@ while time.time() < t_end and it < args.stop_after:
         d.setParam("debug.setop_grid", 0)
         wi, wk, wv, wc = setop_oracle.setop_oracle(sa, sb, tname, setop_oracle.OP_IDS[opname], 1 if desc else 0, sva, svb)
         assert cnt == wc and np.array_equal(gi, wi) and np.array_equal(ok, wk) and np.array_equal(ov, wv), (it, kind, opname, n, na, tname, desc, dist)
+    elif kind == "join":   # a join of two sorted parts of the keys, against the oracle of the tests
+        sr = np.random.RandomState(args.seed + 23 * it)
+        n = min(n, 1 << 22)
+        na = int(sr.choice([1, n // 2, n - 1, n, int(sr.randint(1, n + 1))])); nb = n - na
+        tname, desc, how = ["i32", "f32"][sr.randint(0, 2)], bool(sr.randint(0, 2)), join_oracle.KINDS[sr.randint(0, 4)]
+        dt = {"i32": np.int32, "f32": np.float32}[tname]
+        k = k[:n] % np.uint32(sr.choice([max(n // 64, 1), max(n // 2, 1), 1 << 31]))   # runs of a few dozen keys down to hardly a key shared
+        d.setParam("debug.join_grid", int(sr.choice([0, 0, 1, 7, 300])))
+        d.setParam("debug.search_lds_keys", int(sr.choice([0, 0, 2, 100])))
+        ka = Buffer(d, na, dt); kb = Buffer(d, max(nb, 1), dt)
+        ka.write(k[:na].view(dt)); p.sortKeys(d, ka, na, descending=desc)
+        if nb: kb.write(k[na:n].view(dt)); p.sortKeys(d, kb, nb, descending=desc)
+        sa, sb = ka.toHost()[:na].view(np.uint32), kb.toHost()[:nb].view(np.uint32)
+        total = int(p.joinSorted(d, how, ka, kb, na, nb, descending=desc).count.toHost()[0])
+        cap = min(int(sr.choice([total, total // 2, total + 5, 1])), 1 << 25)
+        wa, wb_, wt = join_oracle.join_oracle(sa, sb, tname, join_oracle.KIND_IDS[how], 1 if desc else 0, limit=cap)
+        assert total == wt, (it, kind, how, n, na, tname, desc, dist)
+        if cap:
+            r = p.joinSorted(d, how, ka, kb, na, nb, cap=cap, indexA=True, indexB=True, descending=desc)
+            rows = min(total, cap)
+            ga, gb, cnt = r.indexA.toHost()[:rows], r.indexB.toHost()[:rows], int(r.count.toHost()[0])
+            for b in (r.indexA, r.indexB, r.count): b.release()
+            assert cnt == wt and np.array_equal(ga, wa) and np.array_equal(gb, wb_), (it, kind, how, n, na, cap, tname, desc, dist)
+        for b in (ka, kb): b.release()
+        d.setParam("debug.join_grid", 0); d.setParam("debug.search_lds_keys", 0)
+    elif kind == "expand":   # run-length decode of counts drawn from the keys, 8-byte values along
+        sr = np.random.RandomState(args.seed + 29 * it)
+        n = min(n, 1 << 21)
+        counts = (k[:n] % np.uint32(sr.choice([1, 2, 5, 40]))).astype(np.uint32)
+        for _ in range(int(sr.randint(0, 4))):   # stretches of runs without rows, and a few long runs
+            at = int(sr.randint(0, n)); counts[at:at + int(sr.randint(1, 20000))] = 0
+            counts[int(sr.randint(0, n))] = int(sr.randint(1000, 3000000))
+        v = np.arange(n, dtype=np.uint64) * np.uint64(0x9E3779B97F4A7C15)
+        wr, wk, wv, total = join_oracle.expand_oracle(counts, v)
+        cap = int(sr.choice([total, total // 2, total + 5, 1]))
+        d.setParam("debug.join_grid", int(sr.choice([0, 0, 1, 7, 300])))
+        cb = Buffer(d, n, np.uint32); vb = Buffer(d, n, np.uint64); vo = Buffer(d, max(cap, 1), np.uint64)
+        cb.write(counts); vb.write(v)
+        if cap:
+            r = p.expandRuns(d, cb, n, cap=cap, values=vb, runOut=True, rankOut=True, valuesOut=vo)
+            rows = min(total, cap)
+            assert int(r.count.toHost()[0]) == total, (it, kind, n, cap, dist)
+            assert np.array_equal(r.run.toHost()[:rows], wr[:rows]) and np.array_equal(r.rank.toHost()[:rows], wk[:rows]) and np.array_equal(vo.toHost()[:rows], wv[:rows]), (it, kind, n, cap, dist)
+            for b in (r.run, r.rank, r.count): b.release()
+        else:
+            r = p.expandRuns(d, cb, n)
+            assert int(r.count.toHost()[0]) == 0; r.count.release()
+        for b in (cb, vb, vo): b.release()
+        d.setParam("debug.join_grid", 0)
     elif kind == "hist":   # a histogram of the keys: mode, type, bins and grid knob from a generator of this iteration's own
         hr = np.random.RandomState(args.seed + 7 * it)
         n = min(n, 1 << 24)
