@@ -1400,6 +1400,8 @@ __device__ __forceinline__ Msd2Placement msd2_placement(const uint32_t* __restri
 // which overshoots the quotient for some operands (n = 7726351: 13 of the 16384 samples), the "remainder" wraps to ~2^24 and
 // the load lands 64 MiB past the array -- a memory fault whenever nothing is mapped there (found by tools/stress.py;
 // adlhip_selftest_probe_positions checks the positions on the device).
+// tests/sample_adversary.py holds numpy twins of this function, of sample_position below and of big_sample_index
+// (dict_big_kernels.hpp), and builds keys against them: a change of a constant here must be followed there.
 __device__ __forceinline__ size_t probe_sample_index(uint32_t k, uint32_t n)
 {
     const uint32_t cell = n >> 14;                                                           // < 2^18
