@@ -242,8 +242,8 @@ int adlhip_sort_typed_scratch_bytes(adlhip_device* dev, int key_type, int mode, 
 /* Sorts n typed keys in place (no reference counterpart): encode in place -> adlhip_radix_sort_u32 / _u64 on whole keys -> decode in
  * place.  Cost: two streaming sweeps of n keys (read + write each) on top of the unsigned sort; U32 / U64 ascending launch no codec
  * kernel and cost what adlhip_radix_sort_u32 / _u64 cost.  NaN and -0 order: above.  d_tmp: n keys.  Enqueues and returns.
- * If the unsigned sort refuses after the encode has been enqueued (knobs changed since the scratch was sized: "sort.algo" = 0 or
- * "sort.digit_bits" = 7 with a work buffer that does not hold the one-sweep path), the decode is enqueued all the same: the call
+ * If the unsigned sort refuses after the encode has been enqueued (knobs changed since the scratch was sized: "sort.algo" = 0
+ * with a work buffer that does not hold the one-sweep path), the decode is enqueued all the same: the call
  * fails with the sort's message and the keys are what they were, unsorted. */
 int adlhip_sort_keys_typed(adlhip_device* dev, int key_type, int order, void* d_keys_inout, void* d_tmp,
                            void* d_work, size_t work_bytes, size_t n);
@@ -1021,10 +1021,10 @@ int adlhip_generate_keys(adlhip_device* dev, int elem_kind, void* dptr, size_t n
  *                      0 = onesweep (one sweep per digit, 16 decoupled look-back chains)
  *                      1 = three kernels per pass: count -> table scan -> sort+scatter (the
  *                          reference's pass structure, Pprims.cpp:357-398)
- *   "sort.digit_bits"  8 [default], 4 (the reference's R32SORT_BITS_PER_PASS, Pprims.h:31) or 7 (one-sweep passes only: 7,7,7,7,4)
+ *   "sort.digit_bits"  8 [default] or 4 (the reference's R32SORT_BITS_PER_PASS, Pprims.h:31)
  *   "sort.tile"        tile geometry variant (threads x elements per thread): -1 [default] = best known
  *                      per element size (512x32 for 4-byte, 1024x16 for 8-byte elements); 0 = 256x16,
- *                      1 = 512x16, 2 = 1024x16, 3 = 512x8, 4 = 1024x8, 5 = 256x32, 6 = 512x32
+ *                      1 = 512x16, 2 = 1024x16, 3 = 512x32
  *   "sort.rank"        1 [default when the device self-test passes] = in-tile ranking by lane-ordered
  *                      returning LDS atomics; 0 = ranking by 64-lane ballot match.  Mode 1 depends on a
  *                      hardware behaviour no ISA document promises (lanes of ONE returning DS atomic

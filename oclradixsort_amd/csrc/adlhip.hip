@@ -43,7 +43,7 @@ namespace {
 struct TileVariant {
     int nt, k;
 };
-constexpr TileVariant kVariants[] = {{256, 16}, {512, 16}, {1024, 16}, {512, 8}, {1024, 8}, {256, 32}, {512, 32}};
+constexpr TileVariant kVariants[] = {{256, 16}, {512, 16}, {1024, 16}, {512, 32}};
 constexpr int kNumVariants = (int)(sizeof(kVariants) / sizeof(kVariants[0]));
 }  // namespace
 int adlhip_internal::num_tile_variants() { return kNumVariants; }
@@ -61,12 +61,7 @@ std::vector<PassPlan> plan_passes(int sort_bits, int digit_bits)
     std::vector<PassPlan> p;
     int sb = 0;
     while (sb < sort_bits) {
-        // 7-bit digits only where the key width allows 7,...,7(,4); every other width falls back to 8-bit digits
-        // (and up to 32 sorted bits: a 7-bit digit starting at bit 28 would straddle the two dwords of a 64-bit key,
-        // which digit_of() rules out)
-        const bool seven = digit_bits == 7 && sort_bits % 7 % 4 == 0 && sort_bits <= 32;
-        int nb = ((digit_bits == 8 || (digit_bits == 7 && !seven)) && sort_bits - sb >= 8) ? 8 : 4;
-        if (seven && sort_bits - sb >= 7) nb = 7;
+        const int nb = (digit_bits == 8 && sort_bits - sb >= 8) ? 8 : 4;
         p.push_back({sb, nb});
         sb += nb;
     }
@@ -96,12 +91,11 @@ Geometry geometry(const adlhip_device* d, size_t n, uint32_t tile)
 //   4-byte elements up to 24 MiB: 512 x 16
 int effective_variant(const adlhip_device* d, size_t elem_bytes, size_t n)
 {
-    if (d->digit_bits == 7) return elem_bytes == 4 ? 6 : 2;   // 7-bit digits are instantiated for the default large tiles only
     if (d->tile_variant >= 0) return d->tile_variant;
     if (n * elem_bytes <= (size_t(8) << 20)) return 0;
     // 4-byte keys between 8 and 24 MiB (three-kernel passes): 512 x 16 (8 Ki keys) -- 4Mi keys 75 vs 79 us with 512 x 32
     if (elem_bytes == 4 && n * elem_bytes < (size_t(24) << 20)) return 1;
-    return elem_bytes == 4 ? 6 : 2;
+    return elem_bytes == 4 ? 3 : 2;
 }
 uint32_t current_tile(const adlhip_device* d, size_t elem_bytes, size_t n)
 {
@@ -177,7 +171,7 @@ struct SoaBuf {
 template <typename Buf, int NBITS>
 const char* kernel_name(const char* stem)
 {
-    return intern(std::string(stem) + Buf::tag() + (NBITS == 8 ? "_8b" : (NBITS == 7 ? "_7b" : "_4b")));
+    return intern(std::string(stem) + Buf::tag() + (NBITS == 8 ? "_8b" : "_4b"));
 }
 
 // tile variant: SoA pairs are instantiated for two geometries only (256x16 for small inputs, 1024x16 otherwise)
@@ -196,11 +190,6 @@ uint32_t buf_tile(const adlhip_device* d, size_t n)
 }
 
 #define ADLHIP_DISPATCH_TILE(FN, Buf, NBITS, ...)                                                     \
-    if constexpr (NBITS == 7) {   /* 7-bit digits: the default tiles only */                          \
-        if (Buf::kElemBytes == 4 && !Buf::kSoa)                                                       \
-            return d->rank_mode ? FN<Buf, NBITS, 512, 32, 1>(__VA_ARGS__) : FN<Buf, NBITS, 512, 32, 0>(__VA_ARGS__); \
-        return d->rank_mode ? FN<Buf, NBITS, 1024, 16, 1>(__VA_ARGS__) : FN<Buf, NBITS, 1024, 16, 0>(__VA_ARGS__);   \
-    }                                                                                                 \
     if (Buf::kSoa) {                                                                                  \
         switch (buf_variant<Buf>(d, n) * 2 + (d->rank_mode ? 1 : 0)) {                                \
         case 0: return FN<Buf, NBITS, 256, 16, 0>(__VA_ARGS__);                                       \
@@ -216,14 +205,8 @@ uint32_t buf_tile(const adlhip_device* d, size_t n)
     case 3: return FN<Buf, NBITS, 512, 16, 1>(__VA_ARGS__);                                           \
     case 4: return FN<Buf, NBITS, 1024, 16, 0>(__VA_ARGS__);                                          \
     case 5: return FN<Buf, NBITS, 1024, 16, 1>(__VA_ARGS__);                                          \
-    case 6: return FN<Buf, NBITS, 512, 8, 0>(__VA_ARGS__);                                            \
-    case 7: return FN<Buf, NBITS, 512, 8, 1>(__VA_ARGS__);                                            \
-    case 8: return FN<Buf, NBITS, 1024, 8, 0>(__VA_ARGS__);                                           \
-    case 9: return FN<Buf, NBITS, 1024, 8, 1>(__VA_ARGS__);                                           \
-    case 10: return FN<Buf, NBITS, 256, 32, 0>(__VA_ARGS__);                                          \
-    case 11: return FN<Buf, NBITS, 256, 32, 1>(__VA_ARGS__);                                          \
-    case 12: return FN<Buf, NBITS, 512, 32, 0>(__VA_ARGS__);                                          \
-    case 13: return FN<Buf, NBITS, 512, 32, 1>(__VA_ARGS__);                                          \
+    case 6: return FN<Buf, NBITS, 512, 32, 0>(__VA_ARGS__);                                           \
+    case 7: return FN<Buf, NBITS, 512, 32, 1>(__VA_ARGS__);                                           \
     default: return fail("bad tile variant %d", d->tile_variant);                                     \
     }
 
@@ -312,7 +295,6 @@ size_t status_rows(size_t n, uint32_t tile) { return (n + tile - 1) / tile + adl
 // most passes a sort of `key_bits`-bit keys can need with the current digit width (8,8,8,4 style plans included)
 int max_passes_for(const adlhip_device* d, int key_bits)
 {
-    if (d->digit_bits == 7) return key_bits / 7 + 1;
     return d->digit_bits == 8 ? (key_bits + 7) / 8 : key_bits / 4;
 }
 
@@ -426,9 +408,8 @@ int onesweep_sort(adlhip_device* d, Buf data, Buf tmp, void* work, size_t n, con
     for (int i = 0; i < P; ++i) {
         uint32_t* st = status + (size_t)i * rows * 256;
         uint32_t* tk = ctrl + i * adlhip::kChains * adlhip::kTicketStride;
-        rc = (plan[i].nbits == 8)   ? dispatch_onesweep<Buf, 8>(d, src, dst, tables + i, st, tk, n, plan[i].start_bit)
-             : (plan[i].nbits == 7) ? dispatch_onesweep<Buf, 7>(d, src, dst, tables + i, st, tk, n, plan[i].start_bit)
-                                    : dispatch_onesweep<Buf, 4>(d, src, dst, tables + i, st, tk, n, plan[i].start_bit);
+        rc = (plan[i].nbits == 8) ? dispatch_onesweep<Buf, 8>(d, src, dst, tables + i, st, tk, n, plan[i].start_bit)
+                                  : dispatch_onesweep<Buf, 4>(d, src, dst, tables + i, st, tk, n, plan[i].start_bit);
         if (rc) return rc;
         std::swap(src, dst);
     }
@@ -1572,17 +1553,16 @@ namespace {
 template <typename Buf>
 int run_sort(adlhip_device* d, Buf data, Buf tmp, void* work, size_t work_bytes, size_t n, const std::vector<PassPlan>& plan)
 {
-    const bool seven = !plan.empty() && plan[0].nbits == 7;   // 7-bit digits exist in the one-sweep pass only
     {   // a work buffer sized by the reference's contract (level 0) holds the three-kernel pass's table and nothing else
         const size_t os = onesweep_layout(d, n, max_passes_for(d, Buf::kElemBytes == 4 && !Buf::kSoa ? 32 : 64), buf_tile<Buf>(d, n)).total;
         if (work_bytes < os) {
-            if (seven || d->sort_algo == 0)
+            if (d->sort_algo == 0)
                 return fail("work buffer too small for the one-sweep path the knobs ask for: %zu < %zu (adlhip_radix_sort_scratch_bytes)",
                             work_bytes, os);
             return three_kernel_sort<Buf>(d, data, tmp, work, n, plan);
         }
     }
-    if (d->sort_algo < 0 && !seven) {   // automatic choice by size (profiles/r1_ncurve.txt)
+    if (d->sort_algo < 0) {   // automatic choice by size (profiles/r1_ncurve.txt)
         // the one-sweep path has more fixed cost (histogram, tables) and wins from ~24 MiB of data (fresh random keys,
         // profiles/r1_ncurve.txt: 4Mi u32 keys 78 vs 88 us, 8Mi 124 vs 117 us, 16Mi 224 vs 174 us)
         // (AoS pairs: from ~36 MiB; 4 Mi pairs 0.103 vs 0.125 ms, 5 Mi pairs 0.149 vs 0.127 ms)
@@ -1590,8 +1570,7 @@ int run_sort(adlhip_device* d, Buf data, Buf tmp, void* work, size_t work_bytes,
         if (n * Buf::kElemBytes < edge) return three_kernel_sort<Buf>(d, data, tmp, work, n, plan);
     }
     // tile status words carry 30-bit counts: beyond 2^30 elements use the table-based pass
-    if (seven && n >= (size_t(1) << 30)) return fail("sort.digit_bits = 7 supports fewer than 2^30 elements");
-    if (!seven && (d->sort_algo == 1 || n >= (size_t(1) << 30))) return three_kernel_sort<Buf>(d, data, tmp, work, n, plan);
+    if (d->sort_algo == 1 || n >= (size_t(1) << 30)) return three_kernel_sort<Buf>(d, data, tmp, work, n, plan);
     return onesweep_sort<Buf>(d, data, tmp, work, n, plan);
 }
 

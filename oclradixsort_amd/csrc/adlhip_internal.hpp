@@ -85,7 +85,7 @@ struct adlhip_device {
     int persist_grid = 0;     // "debug.persist_grid": workgroups of the large sort's persistent passes, rounded up to a
                               // multiple of 8 (0: two per CU)
     // (with a rule of their own)
-    int digit_bits = 8;       // "sort.digit_bits": 8, 7 or 4
+    int digit_bits = 8;       // "sort.digit_bits": 8 or 4
     int unique_algo = -1;     // "unique.algo": -1 the keys path unless first_index or inverse is asked, 1 always the index path
     int tile_variant = -1;    // "sort.tile": index into kVariants; -1 = best known per element size
     int net_lookback = 1;     // "sort.net_lookback": the large sort's safety net runs look-back passes (0: count-scan-scatter passes)

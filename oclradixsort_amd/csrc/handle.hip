@@ -164,7 +164,7 @@ int create_common(int device_idx, void* stream, bool own, adlhip_device** out)
     if (const char* r = getenv("ADLHIP_SORT_RANK")) d->rank_mode = (atoi(r) && d->lds_ordered) ? 1 : 0;
     if (const char* m = getenv("ADLHIP_SORT_MID")) d->mid_path = atoi(m) ? 1 : 0;
     if (const char* m = getenv("ADLHIP_SORT_MSD2")) { int v = atoi(m); if (v >= 0 && v <= 2) d->msd2_path = v; }
-    if (const char* b = getenv("ADLHIP_DIGIT_BITS")) { int v = atoi(b); d->digit_bits = (v == 4 || v == 7) ? v : 8; }
+    if (const char* b = getenv("ADLHIP_DIGIT_BITS")) { int v = atoi(b); d->digit_bits = v == 4 ? 4 : 8; }
     *out = d;
     return ADLHIP_SUCCESS;
 }
@@ -229,7 +229,7 @@ const Knob kKnobs[] = {
     {"debug.persist_grid", &adlhip_device::persist_grid, 0, 4096, "debug.persist_grid must be in [0, 4096]", nullptr},
     // ---- with a rule of their own
     {"sort.digit_bits", &adlhip_device::digit_bits, 0, 0, nullptr,
-     [](adlhip_device*, int* v) { return *v == 4 || *v == 7 || *v == 8 ? ADLHIP_SUCCESS : fail("sort.digit_bits must be 4, 7 or 8"); }},
+     [](adlhip_device*, int* v) { return *v == 4 || *v == 8 ? ADLHIP_SUCCESS : fail("sort.digit_bits must be 4 or 8"); }},
     {"unique.algo", &adlhip_device::unique_algo, 0, 0, nullptr, [](adlhip_device*, int* v) {
          return *v == -1 || *v == 1 ? ADLHIP_SUCCESS : fail("unique.algo must be -1 (by the outputs asked) or 1 (always the index path)"); }},
     {"sort.tile", &adlhip_device::tile_variant, 0, 0, nullptr, [](adlhip_device*, int* v) {

@@ -61,15 +61,18 @@ def test_no_float_expanded_integer_division_in_the_device_code(tmp_path):
     at = [m.start() for m in re.finditer(b"\x7fELF", data) if int.from_bytes(data[m.start() + 18:m.start() + 20], "little") == 224]
     assert at, "no AMDGPU code object inside the library"
     co = tmp_path / "device.co"
-    co.write_bytes(data[at[0]:])
-    out = subprocess.run([objdump, "-d", "--mcpu=gfx950", str(co)], capture_output=True, text=True).stdout
-    assert out.count("s_endpgm") >= 50, "disassembly failed"
-    kernel, hits = None, []
-    for line in out.splitlines():
-        if line.endswith(">:"):
-            kernel = line.split("<", 1)[1][:-2]
-        elif "v_trunc_f32" in line:
-            hits.append(kernel)
+    ends, kernel, hits = 0, None, []
+    for start in at:   # one code object per translation unit
+        co.write_bytes(data[start:])
+        out = subprocess.run([objdump, "-d", "--mcpu=gfx950", str(co)], capture_output=True, text=True).stdout
+        assert "s_endpgm" in out, "disassembly failed"
+        ends += out.count("s_endpgm")
+        for line in out.splitlines():
+            if line.endswith(">:"):
+                kernel = line.split("<", 1)[1][:-2]
+            elif "v_trunc_f32" in line:
+                hits.append(kernel)
+    assert ends >= 50, "disassembly failed"
     assert not hits, sorted(set(hits))
 
 

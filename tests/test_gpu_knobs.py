@@ -40,9 +40,9 @@ PLAIN = {
 }
 # name: ({value set: value read back}, [refused values], refusal).  "R" stands for the device's resident workgroup count
 SPECIAL = {
-    "sort.digit_bits": ({4: 4, 7: 7, 8: 8}, [3, 5, 6, 9, 0, -1], "sort.digit_bits must be 4, 7 or 8"),
+    "sort.digit_bits": ({4: 4, 8: 8}, [3, 5, 6, 7, 9, 0, -1], "sort.digit_bits must be 4 or 8"),
     "unique.algo": ({1: 1, -1: -1}, [-2, 0, 2], "unique.algo must be -1 (by the outputs asked) or 1 (always the index path)"),
-    "sort.tile": ({-1: -1, 0: 0, 6: 6}, [-2, 7], "sort.tile must be in [-1,7)"),
+    "sort.tile": ({-1: -1, 0: 0, 3: 3}, [-2, 4, 6], "sort.tile must be in [-1,4)"),
     "sort.net_lookback": ({0: 0, 1: 1, 5: 1, -3: 1, INT_MAX: 1}, [], None),
     "partition.lookback": ({0: 0, 1: 1, 5: 1, -3: 1, INT_MAX: 1}, [], None),
     "profile": ({1: 1, 0: 0, 5: 1, -3: 1}, [], None),
@@ -200,12 +200,16 @@ def knobs_of_a_fresh_process(env):
 def test_environment_switches():
     """One child after the other.  Valid values are taken; out of range, each switch clamps its own way: the tile, the algorithm and the
     large sort keep their defaults (ADLHIP_SORT_MSD2 takes 0..2 only), ADLHIP_SORT_MID and ADLHIP_SORT_RANK are read as flags (the rank
-    ANDed with the self-test's result), and a digit width that is neither 4 nor 7 means 8."""
+    ANDed with the self-test's result), and a digit width other than 4 means 8.  A tile index and a digit width that
+    earlier versions took (6, 7) are out of range like any other."""
     got = knobs_of_a_fresh_process({"ADLHIP_SORT_ALGO": "1", "ADLHIP_SORT_TILE": "3", "ADLHIP_SORT_RANK": "0", "ADLHIP_SORT_MID": "0",
                                     "ADLHIP_SORT_MSD2": "2", "ADLHIP_DIGIT_BITS": "4"})
     ordered = got.pop("sort.lds_ordered")
     assert got == {"sort.algo": 1, "sort.tile": 3, "sort.rank": 0, "sort.mid": 0, "sort.msd2": 2, "sort.digit_bits": 4}
     got = knobs_of_a_fresh_process({"ADLHIP_SORT_ALGO": "2", "ADLHIP_SORT_TILE": "99", "ADLHIP_SORT_RANK": "7", "ADLHIP_SORT_MID": "5",
                                     "ADLHIP_SORT_MSD2": "3", "ADLHIP_DIGIT_BITS": "5"})
+    assert got.pop("sort.lds_ordered") == ordered
+    assert got == {"sort.algo": -1, "sort.tile": -1, "sort.rank": ordered, "sort.mid": 1, "sort.msd2": 1, "sort.digit_bits": 8}
+    got = knobs_of_a_fresh_process({"ADLHIP_SORT_TILE": "6", "ADLHIP_DIGIT_BITS": "7"})
     assert got.pop("sort.lds_ordered") == ordered
     assert got == {"sort.algo": -1, "sort.tile": -1, "sort.rank": ordered, "sort.mid": 1, "sort.msd2": 1, "sort.digit_bits": 8}

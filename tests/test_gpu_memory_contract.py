@@ -341,7 +341,7 @@ def stable_order(keys, bits):
 KNOB_SETS = [
     ("default", {}),
     ("onesweep4", {"sort.algo": 0, "sort.digit_bits": 4}),
-    ("onesweep7", {"sort.algo": 0, "sort.digit_bits": 7}),
+    ("onesweep8", {"sort.algo": 0}),
     ("threekernel", {"sort.algo": 1}),
     ("rank0", {"sort.rank": 0}),
     ("msd2forced", {"sort.msd2": 2}),
@@ -412,7 +412,7 @@ def _case_id(c):
 
 
 def _one_sweep_knobs(knobs):
-    return knobs.get("sort.algo") == 0 or knobs.get("sort.digit_bits") == 7
+    return knobs.get("sort.algo") == 0
 
 
 def sort_call(dev, kind, regs, work_bytes, n, bits):

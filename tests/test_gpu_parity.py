@@ -21,10 +21,9 @@ pytestmark = pytest.mark.gpu
 
 # (sort.algo, sort.digit_bits, sort.tile, sort.rank)
 ALGOS = [(-1, 8, -1, 1), (-1, 4, -1, 0), (0, 8, -1, 1), (0, 4, -1, 1), (1, 8, -1, 1), (1, 4, -1, 1), (0, 8, -1, 0), (1, 8, 0, 0), (0, 8, 0, 1), (1, 8, 1, 1),
-         (0, 8, 3, 1), (1, 8, 4, 0), (0, 8, 5, 1), (0, 8, 2, 1), (0, 4, 0, 0), (0, 7, -1, 1)]
+         (0, 8, 3, 1), (0, 8, 2, 1), (0, 4, 0, 0)]
 ALGO_IDS = ["auto8", "auto4-ballot", "onesweep8", "onesweep4", "threekernel8", "threekernel4", "onesweep8-ballot", "threekernel8-256x16-ballot",
-            "onesweep8-256x16", "threekernel8-512x16", "onesweep8-512x8", "threekernel8-1024x8-ballot",
-            "onesweep8-256x32", "onesweep8-1024x16", "onesweep4-256x16-ballot", "onesweep7"]
+            "onesweep8-256x16", "threekernel8-512x16", "onesweep8-512x32", "onesweep8-1024x16", "onesweep4-256x16-ballot"]
 
 
 @pytest.fixture(scope="module")
@@ -36,7 +35,7 @@ def dev():
 
 @pytest.fixture(autouse=True)
 def _knobs_back_to_default(request):
-    """Every test starts from the default knobs on the shared device handle (a test that ends with "sort.rank" = 0 or 7-bit
+    """Every test starts from the default knobs on the shared device handle (a test that ends with "sort.rank" = 0 or 4-bit
     digits must not decide which path the next one takes)."""
     if "dev" in request.fixturenames:
         d = request.getfixturevalue("dev")

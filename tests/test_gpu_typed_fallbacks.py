@@ -32,7 +32,7 @@ mid-size form's layout (4 MiB of slabs at least) and, above 16384 elements, the 
 look-back passes' status rows -- the only part that grows with "sort.digit_bits" and "sort.tile" -- stay below both at every n the
 large sort takes (up to 260 Mi elements), and "sort.algo", "sort.rank" and "debug.resident_wgs" enter no layout.
 test_no_configuration_asks_for_more_scratch_than_the_default asserts exactly that on the host, for every entry point, size and
-configuration used here and for "sort.digit_bits" = 7 and every "sort.tile": the day one of them asks for more, it fails and the refusal
+configuration used here and for every "sort.tile": the day one of them asks for more, it fails and the refusal
 can be tested.  (The in-place entry points are covered by test_a_refused_typed_sort_leaves_keys_and_values_as_they_were, which hands the
 base sort less than the typed query.)
 """
@@ -723,9 +723,9 @@ def every_query(d, n):
 def test_no_configuration_asks_for_more_scratch_than_the_default(dev):
     """Why no entry point has a test of a call refused for knobs changed after its scratch was sized (the module's docstring): such a
     test needs a configuration whose query is strictly larger than the default's, and there is none -- not among the five
-    configurations, not with "sort.digit_bits" = 7, not with any "sort.tile".  Host only: nothing is enqueued."""
+    configurations, not with any "sort.tile".  Host only: nothing is enqueued."""
     sizes = sorted(set(tf.PAIR_RUNGS + tf.KEY_RUNGS[4] + tf.KEY_RUNGS[8] + [1000, 16384, 16385]))
-    others = [(name, knobs) for name, knobs in tf.CONFIGS[1:]] + [("digit_bits 7", [("sort.digit_bits", 7)])]
+    others = [(name, knobs) for name, knobs in tf.CONFIGS[1:]]
     tile = 0
     while True:   # every "sort.tile" the library knows
         try:
@@ -736,7 +736,7 @@ def test_no_configuration_asks_for_more_scratch_than_the_default(dev):
             dev.setParam("sort.tile", -1)
         others.append(("tile %d" % tile, [("sort.tile", tile)]))
         tile += 1
-    assert tile >= 7
+    assert tile == 4
     dev.setParam("sort.rows_algo", ROWS_FLAT)   # (the row kernel asks for nothing)
     try:
         for n in sizes:

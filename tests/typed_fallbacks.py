@@ -149,7 +149,7 @@ def check_labels(config, labels, sorts, net_delta=(0, 0)):
                 assert any(k.startswith("msd2") for k in inner), "no label of the large sort -- " + what
         if "mid" in forms and not any(k.startswith("mid_") for k in inner):
             assert any(_is_8bit_pass(k) and k != "scan_table" for k in inner), "neither the mid-size form nor the per-digit passes -- " + what
-        bad = {k for k in inner if k.endswith(("_4b", "_7b")) and "_soa_" not in k}   # (the (class, id) sort is on 4 bits by itself)
+        bad = {k for k in inner if k.endswith("_4b") and "_soa_" not in k}   # (the (class, id) sort is on 4 bits by itself)
         assert not bad, "digits of another width: %s -- %s" % (sorted(bad), what)
     elif config == "small_partition":
         bad = {k for k in inner if k.startswith(("mid_", "msd2", "segment_sort"))}

@@ -8,8 +8,8 @@ OUT=$PWD/gpurun_out/$TAG; mkdir -p $OUT
 if [ "$PART" != b ]; then
 echo "== smoke";  timeout -k 10 600 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -2
 echo "== pytest -m gpu"; timeout -k 10 1000 python -m pytest tests -m gpu -x -q 2>&1 | tail -5 | tee $OUT/pytest_gpu.txt
-echo "== sweep u32"; timeout -k 10 600 python tools/sweep.py --steps 10 --verify --configs=-1:8:-1:1,0:8:-1:1,0:7:-1:1,0:4:-1:1,1:8:-1:1,0:8:-1:0 2>&1 | tee $OUT/sweep_u32.txt
-echo "== sweep kv";  timeout -k 10 600 python tools/sweep.py --steps 10 --verify --kind kv --configs=-1:8:-1:1,0:8:-1:1,0:8:6:1,1:8:-1:1 2>&1 | tee $OUT/sweep_kv32.txt
+echo "== sweep u32"; timeout -k 10 600 python tools/sweep.py --steps 10 --verify --configs=-1:8:-1:1,0:8:-1:1,0:4:-1:1,1:8:-1:1,0:8:-1:0 2>&1 | tee $OUT/sweep_u32.txt
+echo "== sweep kv";  timeout -k 10 600 python tools/sweep.py --steps 10 --verify --kind kv --configs=-1:8:-1:1,0:8:-1:1,0:8:3:1,1:8:-1:1 2>&1 | tee $OUT/sweep_kv32.txt
 echo "== sweep soa"; timeout -k 10 600 python tools/sweep.py --steps 10 --verify --kind soa --configs=-1:8:-1:1,0:8:-1:1,1:8:-1:1 2>&1 | tee $OUT/sweep_soa32.txt
 echo "== sweep u64 256Mi"; timeout -k 10 600 python tools/sweep.py --steps 3 --kind u64 --n 268435456 --configs=-1:8:-1:1,0:8:-1:1,1:8:-1:1 2>&1 | tee $OUT/sweep_u64.txt
 echo "== distributions"; timeout -k 10 600 python tools/distributions.py 2>&1 | tee $OUT/distributions.txt

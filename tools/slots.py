@@ -4,14 +4,14 @@ workgroup's FIRST instruction, of the first instruction after the ticket, and of
 the CU it ran on.  Prints how long a CU's workgroup slots sit between one tile's last instruction and the next
 tile's first (stores draining + dispatch), the ticket latency, and the chip-wide occupancy curve.
    make -C oclradixsort_amd/csrc stamps
-   ADLHIP_LIB=$PWD/oclradixsort_amd/lib/libadlhip_stamps.so python tools/slots.py [--tile 6]"""
+   ADLHIP_LIB=$PWD/oclradixsort_amd/lib/libadlhip_stamps.so python tools/slots.py [--tile 3]"""
 import argparse, ctypes, os, sys
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from oclradixsort_amd import Buffer, DeviceUtils, Pprims, _lib
 ap = argparse.ArgumentParser()
 ap.add_argument("--n", type=int, default=1 << 26)
-ap.add_argument("--tile", type=int, default=6)
+ap.add_argument("--tile", type=int, default=3)
 ap.add_argument("--slots", type=int, default=2, help="workgroups per CU the variant fits")
 args = ap.parse_args()
 n = args.n

@@ -8,7 +8,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from oclradixsort_amd import Buffer, DeviceUtils, Pprims, _lib
 ap = argparse.ArgumentParser()
 ap.add_argument("--n", type=int, default=1 << 26)
-ap.add_argument("--configs", default="0:8:6:1,0:8:1:1")
+ap.add_argument("--configs", default="0:8:3:1,0:8:1:1")
 args = ap.parse_args()
 n = args.n
 d = DeviceUtils.allocate(); p = Pprims()
@@ -20,7 +20,7 @@ old_names = {(11, 0): "ticket", (0, 1): "load", (1, 2): "rank", (2, 3): "barA", 
              (5, 6): "bar", (6, 7): "lds-scatter", (7, 8): "bar", (8, 9): "write-out", (9, 10): "bar"}
 new_names = {(0, 2): "load+rank", (2, 3): "barA", (3, 4): "bookkeeping(w0)", (4, 5): "barB", (5, 6): "lds-scatter",
              (6, 7): "lookback(w0)", (7, 9): "barC", (9, 10): "write-out"}
-tiles_of = {0: 4096, 1: 8192, 2: 16384, 3: 4096, 4: 8192, 5: 8192, 6: 16384}
+tiles_of = {0: 4096, 1: 8192, 2: 16384, 3: 16384}
 buf = Buffer(d, n, np.uint32)
 for cfg in args.configs.split(","):
     algo, bits, tile, rank = (int(x) for x in cfg.split(":"))

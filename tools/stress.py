@@ -52,7 +52,7 @@ while time.time() < t_end and it < args.stop_after:
     if it % 7 == 0: n = int(2 ** rng.uniform(21, 26.3))   # more of the large sort's range
     if kind == "u32" and it % 23 == 0: n = (1 << 26) + int(rng.randint(1, 1 << 22))     # past 256 MiB: pointer stores
     if kind == "u32" and it % 37 == 0: n = int(2 ** rng.uniform(27.1, 28.6))            # 140 Mi ... 400 Mi keys: segments finished by a workgroup each
-    algo = int(rng.choice([0, 0, 1, -1, -1, -1])); bits = int(rng.choice([8, 8, 8, 4])); tile = int(rng.choice([-1, -1, 0, 1, 2, 5]))
+    algo = int(rng.choice([0, 0, 1, -1, -1, -1])); bits = int(rng.choice([8, 8, 8, 4])); tile = int(rng.choice([-1, -1, 0, 1, 2, 3]))
     if algo < 0: bits, tile = 8, -1   # what the automatic paths run with
     d.setParam("sort.algo", algo); d.setParam("sort.digit_bits", bits); d.setParam("sort.tile", tile)
     if args.mix_rank: d.setParam("sort.rank", int(mix_rng.choice([1, 1, 0])))   # ballot ranking on a third of the sorts (own generator: replays stay aligned)

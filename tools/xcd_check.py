@@ -7,7 +7,7 @@ d = DeviceUtils.allocate(); p = Pprims()
 lib = _lib.load()
 lib.adlhip_debug_set_stamp_buffer.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
 stamps = Buffer(d, ((n + 4095) // 4096 + 64) * 16, np.uint64)
-d.setParam("sort.algo", 0); d.setParam("sort.tile", 6)
+d.setParam("sort.algo", 0); d.setParam("sort.tile", 3)
 buf = Buffer(d, n, np.uint32); buf.generate(n, seed=5); stamps.clear()
 assert lib.adlhip_debug_set_stamp_buffer(d._h, stamps.ptr()) == 0
 p.radixSort(d, buf, n, 8)
