@@ -3,6 +3,7 @@
 // Tahoe/ParallelPrimitives/Pprims.cpp (pass drivers).  The runtime under it -- handle, buffers, profiling, knobs -- is handle.hip.
 // gfx950 only; kernels are compiled ahead of time into this shared object.
 #include "adlhip_internal.hpp"
+#include "large_plan.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -441,7 +442,7 @@ int three_kernel_sort(adlhip_device* d, Buf data, Buf tmp, void* work, size_t n,
 }
 
 // ---- small inputs: the whole sort in one workgroup ---------------------------------------------------
-constexpr size_t kSmallMax = 16384;
+// (kSmallMax: large_plan.hpp, where the large sort starts from it)
 
 template <typename E, int NT, int K, int RANK>
 int launch_small(adlhip_device* d, E* data, size_t n, const adlhip::SmallPlan& sp)
@@ -742,92 +743,9 @@ int mid_sort_keys(adlhip_device* d, uint32_t* data, uint32_t* tmp, void* work, s
     return launch_segment_sort<E, 512, 32, 8>(d, slab, data, nullptr, 256, 24, nullptr, coop, sl);
 }
 
-// ---- large keys-only sort: two unstable MSD passes with bucket cursors + LDS finish (hybrid_kernels.hpp "sort.msd2") ------
-// u32 keys and u64 keys (equal keys are indistinguishable, so the passes need not be stable); pairs keep the stable paths.
-constexpr size_t kMsd2Min = kSmallMax;                             // elements; the path works from here ("sort.msd2" >= 2) ...
-constexpr size_t kMsd2AutoMin = size_t(2) << 20;                   // ... and is chosen above the mid-size sort's range
-                                                                   // (profiles/r2_msd2_size_curve.txt: 2.5 Mi keys 58 vs 70 us)
-// up to 280 Mi keys a segment (mean n / 65536 = 4480, + 7.5 sd <= 5120) fits the 80 rows one wave holds; beyond, the finish takes one
-// workgroup per segment (wg_segment_sort_kernel: tiles of 8192 ... 20480 keys) up to a mean of 17408 + 7.5 sd
-constexpr size_t kMsd2MaxU32 = size_t(1088) << 20;
-constexpr size_t kMsd2MaxU64 = (size_t(1) << 28) + (size_t(1) << 22);   // mean segment 4160
-// the wave-per-segment finish's tiles: 64 * 20, 64 * 40, 64 * 80 elements
-
-// from here the 16-bit second slab of whole u32 keys always fits the caller's n-element scratch array (1.5 x the mean + 72 per
-// segment <= 2 x the mean); one fixed threshold keeps the work requirement piecewise monotone in n (sort_work_bytes' edges)
-constexpr size_t kSlabInTmpMin = size_t(16) << 20;
-
-struct Msd2Layout {
-    size_t off_mode, off_cnt, off_off, off_hard, off_coop, off_slab_a, off_slab_b, total;
-    uint32_t stride_a, stride_b, tier_b, tiles_per_bucket, seg_shift, slots;
-    bool slab_b_in_tmp;   // the second slab fits the caller's n-element scratch array (u32 keys from ~40 Mi keys: 16-bit elements,
-                          // 1.5 x the mean per segment = 0.75 n * 4 bytes); the safety net, which needs that array as its partner,
-                          // only ever runs when the slabs' contents are void
-};
-
-// slab of a segment = the smallest of the finish's tiles that holds its mean + 7.5 standard deviations of a uniform key
-// distribution (64 Mi keys: 1024 + 240 = 1264, slab 1536; a segment beyond its slab sends the sort to the safety net, it is never
-// wrong; at 7.5 sd that is one sort in 10^8)
-// slab and finish tile of the first tier: 64 * 24 elements.  With 64 * 20 = 1280 (mean 1024 at 64 Mi keys + 7.5 sd) keys whose
-// density varied by 20 % over the key range already went to the safety net; 1536 takes ~45 % and costs nothing measurable
-// (finish 118.0 vs 118.3 us at 64 Mi keys: five workgroups of four waves per CU instead of three of eight)
-constexpr uint32_t kMsd2Stride0 = 1536;
-// tile of the finish for n elements: 1280 / 1536 / 2560 / 5120 (what a wave -- or a workgroup of the binning finish -- holds),
-// 8192 ... 20480 for the workgroup-per-segment finish
-// fine: whole u32 keys with a 16-bit second slab -- from 2560 keys up their finish is the workgroup kernel, which has tiles of 3072
-// and 4096 keys too (a half-empty 5120-key tile costs its 20 predicated rows all the same: 144 Mi keys 0.35 ms for the finish)
-uint32_t msd2_tier_b(size_t n, uint32_t slots = 65536, bool fine = false)
-{
-    const size_t mean = (n + slots - 1) / slots;
-    size_t sd = 1;
-    while (sd * sd < mean) ++sd;
-    const size_t need = mean + (15 * sd + 1) / 2;
-    if (fine && need > 2560 && need <= 4096) return need <= 3072 ? 3072u : 4096u;
-    // (the tiers' bounds on the mean stay as they were; up to a mean of ~640 the 1280-element tile already leaves 1.5 x)
-    if (need <= 5120) return need <= 832 ? 1280u : need <= 1280 ? kMsd2Stride0 : need <= 2560 ? 2560u : 5120u;
-    // (u32 keys beyond 280 Mi only: the workgroup-per-segment finish, 512 threads x 16 / 24 rows, 1024 x 16 / 20)
-    return need <= 8192 ? 8192u : need <= 12288 ? 12288u : need <= 16384 ? 16384u : 20480u;
-}
-// elements between two segment slabs: the mean + 50 % (or + 7.5 sd where that is more), at most the finish's tile.  (Round 2 spaced
-// the slabs by the tile whatever n was: 168 MB of second slab for 2 Mi keys.)
-uint32_t msd2_stride_b(size_t n, uint32_t slots = 65536, bool fine = false, bool lean = false)
-{
-    const size_t mean = (n + slots - 1) / slots;
-    size_t sd = 1;
-    while (sd * sd < mean) ++sd;
-    // lean (level 2 of adlhip_radix_sort_scratch_bytes_for, stable form): the mean + 7.5 sd only -- what evenly spread keys need
-    const size_t want = align_up(std::max(lean ? mean : mean + mean / 2, mean + (15 * sd + 1) / 2) + 8, 64);
-    return (uint32_t)std::min<size_t>(want, msd2_tier_b(n, slots, fine));
-}
-
-// Width w of the second digit of the cursor form (hybrid_kernels.hpp slot_to_segment): 8 from 12 Mi elements up; below, as many
-// bits as leave segments of about a thousand elements -- 256 << w slots instead of 65536.  The finish then sorts 8 - w bits more
-// (u32 keys: more than 16, so the second slab holds whole keys), which costs less than launching 65536 waves for a few dozen
-// keys each (profiles/r3_narrow_second_digit.txt).
-// Measured (cursor form, 65536 segments | narrow): u32 keys 2.5 Mi 71 | 51 us, 4 Mi 81 | 58, 8 Mi 104 | 91, 16 Mi 140 | 138, 24 Mi
-// 177 | 199; u64 keys (binning finish on the ~1000-key segments) 1.5 Mi 117 | 47 us, 4 Mi 154 | 79, 16 Mi 289 | 221, 24 Mi 397 | 346.
-// bin_finish: the segments go to the binning finish (whole u64 keys, cursor form), which likes them a thousand keys long at any n;
-// the LSD finish pays for every extra bit with LDS passes, so there the narrow digit stops at 16 Mi elements.
-uint32_t msd2_seg_shift(size_t n, bool bin_finish)
-{
-    const size_t max_n = bin_finish ? size_t(1) << 40 : size_t(16) << 20;
-    if (n >= max_n) return 8u;
-    uint32_t w = 2u;
-    while (w < 8u && (n >> (8u + w)) > 1024u) ++w;
-    return w;
-}
-
-
-// head-room of a first-pass bucket slab over the mean bucket, in per cent: 50 at full speed; the lean work size
-// (adlhip_radix_sort_scratch_bytes_for, level 2) takes 12 -- 64 Mi u32 keys then need 306 MB of work instead of 451, and keys whose
-// density varies by more than ~10 % over the key range are sorted by the safety net inside the sort
-constexpr int kFullHeadroomPct = 50, kLeanHeadroomPct = 12;
-
-// Workgroups of the kernels that host the safety net (512 threads, one tile of the one-sweep pass's size in LDS: two per CU).
-// All of them must be resident at once -- the net's phases are separated by grid-wide barriers -- and the first 256 serve the
-// 256 buckets in the kernel's ordinary role.
-constexpr uint32_t kNetWgsMax = 512;
-constexpr size_t kNetTableBytes = (size_t)256 * kNetWgsMax * 4 + 1024;   // [256][workgroups] digit table + 256 totals
+// ---- large sort: two MSD passes into slabs + LDS finish ("sort.msd2") -----------------------------------------------------
+// Its limits, slab and tile sizes, layouts, forms and the plan of one sort call are large_plan.hpp; here are its launches.
+static_assert(kLargeTicketStride == adlhip::kTicketStride, "large_plan.hpp sizes the stable form's ticket area for the kernels' counter stride");
 uint32_t net_wgs(const adlhip_device* d) { return d->resident_wgs >= (int)kNetWgsMax ? kNetWgsMax : 256u; }
 // two handle-owned counters: nets run, and of those, sorted by counting (net_sort; "stat.net_runs" / "stat.net_counting")
 // d_msd2: 256 first-pass cursors (one line each) + 65536 second-pass cursors + 64 words (flag, done, barrier, sample words, the
@@ -847,7 +765,8 @@ constexpr size_t kMsd2TicketWords = (size_t)adlhip::kTileTicketCounters * adlhip
 // the areas are zeroed with the handle, so a stray store into them shows.
 enum IdleRegion { kRegionMsd2 = 1, kRegionMidHist = 2, kRegionDict = 3, kRegionFault = 4, kIdleRegions = 4 };
 enum IdleKind { kIdleValue, kResetOnEntry, kFreeRunning };
-constexpr uint32_t kMsd2Flag = 8192 + 65536;                       // flag = d_msd2 + kMsd2Flag
+constexpr uint32_t kMsd2CursorsB = 8192;                           // second-pass cursors = d_msd2 + kMsd2CursorsB (65536, packed)
+constexpr uint32_t kMsd2Flag = kMsd2CursorsB + 65536;              // flag = d_msd2 + kMsd2Flag
 constexpr uint32_t kMsd2SampleAnd = kMsd2Flag + 10, kMsd2SampleAndWords = 2;   // flag[10..11]: all ones when idle (sort_state_create)
 constexpr uint32_t kMsd2NetStats = kMsd2Flag + 16;                 // flag[16..17] the net's counters, flag[20..29] its time stamps
 uint32_t* net_stats(const adlhip_device* d) { return d->d_msd2 + kMsd2NetStats; }
@@ -1001,51 +920,24 @@ adlhip::OsNet net_onesweep_args(const adlhip_device* d, char* region, size_t reg
     return os;
 }
 
-Msd2Layout msd2_layout(size_t n, size_t elem_bytes, int headroom_pct = kFullHeadroomPct)
-{
-    Msd2Layout L;
-    const uint32_t tile = elem_bytes == 4 ? 16384u : 8192u;   // TileCfg<E, 8, 512, 32 | 16>
-    // mean bucket + 50 % + 4096: the head-room of the segment slabs below (1536 for a mean of 1024), so that keys whose density
-    // varies by up to ~45 % over the key range stay on this path (with + 3 % any mild skew went to the safety net)
-    L.stride_a = (uint32_t)align_up(n / 256 + (n / 256) * (size_t)headroom_pct / 100 + 4096, 64);
-    L.seg_shift = msd2_seg_shift(n, elem_bytes == 8);   // the cursor form sorts whole keys: 8-byte elements = u64 keys
-    L.slots = 256u << L.seg_shift;
-    const bool fine = elem_bytes == 4 && L.seg_shift == 8;   // whole u32 keys, 16-bit second slab
-    L.stride_b = msd2_stride_b(n, L.slots, fine);
-    L.tier_b = msd2_tier_b(n, L.slots, fine);
-    L.tiles_per_bucket = (L.stride_a + tile - 1) / tile;
-    L.off_mode = 0;
-    L.off_cnt = L.off_mode + 256;
-    L.off_off = L.off_cnt + 65536 * 4;
-    L.off_hard = align_up(L.off_off + 65537 * 4, 256);                       // segments the binning finish hands to the LSD finish
-    L.off_coop = L.off_hard + 65536 * 4;                                     // safety net: table [256][256] + 256 totals
-    L.off_slab_a = align_up(L.off_coop + kNetTableBytes, 256);
-    L.off_slab_b = align_up(L.off_slab_a + (size_t)256 * L.stride_a * elem_bytes, 256);
-    // u32 keys: 16-bit second slab (when the finish has 16 bits to sort: w = 8)
-    const size_t slab_b_bytes = (size_t)L.slots * L.stride_b * (elem_bytes == 4 && L.seg_shift == 8 ? 2 : elem_bytes);
-    L.slab_b_in_tmp = elem_bytes == 4 && L.seg_shift == 8 && n >= kSlabInTmpMin && slab_b_bytes <= n * elem_bytes;
-    L.total = L.off_slab_b + (L.slab_b_in_tmp ? 0 : slab_b_bytes);
-    return L;
-}
-
 template <typename E, typename S, bool SOA = false>
 int launch_large_finish(adlhip_device* d, const E* slab_b, E* out, uint32_t* out_vals, uint32_t* seg_off, uint32_t* seg_cnt, uint32_t stride_b,
                         uint32_t tier_b, uint32_t* mode, uint32_t* hard, int low_bits_max, bool bin, uint32_t seg_shift = 8);
-bool use_bin_finish(const adlhip_device* d, size_t elem_bytes, bool key64, size_t n, bool whole_keys);
 
 template <typename E>
-int msd2_sort(adlhip_device* d, E* data, E* tmp, void* work, size_t n, int headroom_pct = kFullHeadroomPct)
+int msd2_sort(adlhip_device* d, E* data, E* tmp, void* work, size_t n, const LargePlan& plan)
 {
+    if (plan.form != kLargeCursor) return fail("internal: the cursor form was handed another form's plan");
     constexpr int K = sizeof(E) == 4 ? 32 : 16;
     constexpr int KEY_BITS = 8 * (int)sizeof(E);
     constexpr bool k32 = sizeof(E) == 4;   // profile names are kept by pointer: literals only
     // d_msd2 (allocated at device creation): cursors of both passes + flag + done counter + sample words, idle values between sorts
     uint32_t* cur_a = d->d_msd2;            // 256 cursors, one 128-byte line each
-    uint32_t* cur_b = d->d_msd2 + 8192;     // 65536 cursors, packed (16 atomics each per sort)
-    uint32_t* flag = d->d_msd2 + 8192 + 65536;
+    uint32_t* cur_b = d->d_msd2 + kMsd2CursorsB;   // 65536 cursors, packed (16 atomics each per sort)
+    uint32_t* flag = d->d_msd2 + kMsd2Flag;
     uint32_t* done = flag + 1;
     uint32_t* sample = flag + 8;            // or lo, or hi, and lo, and hi (hybrid_kernels.hpp msd2_placement)
-    const Msd2Layout L = msd2_layout(n, sizeof(E), headroom_pct);
+    const LargeLayout& L = plan.L;
     char* wb = reinterpret_cast<char*>(work);
     uint32_t* mode = reinterpret_cast<uint32_t*>(wb + L.off_mode);
     uint32_t* seg_cnt = reinterpret_cast<uint32_t*>(wb + L.off_cnt);
@@ -1075,7 +967,7 @@ int msd2_sort(adlhip_device* d, E* data, E* tmp, void* work, size_t n, int headr
     // round 4: the same pass as a persistent kernel -- 2 workgroups per CU take the tiles in turns, the next tile's keys are in
     // flight (non-temporal 16-byte buffer loads) while the current one is ranked, and no wait ever covers a tile's stores
     // (persist_kernels.hpp).  Buffer addressing: the slabs must lie within 4 GiB of their base.
-    const bool slab16 = sizeof(E) == 4 && L.seg_shift == 8;
+    const bool slab16 = plan.slab16;
     const bool persist = d->persist && (size_t)256 * L.stride_a * sizeof(E) < (size_t(1) << 32) - (1u << 20) &&
                          (size_t)L.slots * L.stride_b * (slab16 ? 2 : sizeof(E)) < (size_t(1) << 32) - (1u << 20);
     using PC = adlhip::PersistCfg<E, 512, K>;
@@ -1141,129 +1033,9 @@ int msd2_sort(adlhip_device* d, E* data, E* tmp, void* work, size_t n, int headr
     using S = typename std::conditional<sizeof(E) == 4, uint16_t, E>::type;   // what pass 2 wrote (w = 8)
     uint32_t* hard = reinterpret_cast<uint32_t*>(wb + L.off_hard);
     const int low_max = KEY_BITS - 8 - (int)L.seg_shift;
-    // (whole u64 keys: the binning finish wants segments of ~384 keys and more -- 24 Mi keys in 65536 segments, or any n with a
-    // narrow second digit, which leaves segments of about a thousand keys)
-    const bool bin = use_bin_finish(d, sizeof(E), sizeof(E) == 8, L.seg_shift < 8 ? (size_t(24) << 20) : n, true);
     if (sizeof(E) == 4 && !slab16)
-        return launch_large_finish<E, E>(d, slab_b, data, nullptr, seg_off, seg_cnt, L.stride_b, L.tier_b, mode, hard, low_max, bin, L.seg_shift);
-    return launch_large_finish<E, S>(d, slab_b, data, nullptr, seg_off, seg_cnt, L.stride_b, L.tier_b, mode, hard, low_max, bin, L.seg_shift);
-}
-
-// ---- the same for {key, value} pairs, STABLE: look-back instead of cursors (hybrid_kernels.hpp msd_lookback_scatter_kernel) --
-constexpr size_t kMsd2sAutoMin = size_t(1) << 20;   // pairs; measured with the narrow second digit: 1.5 Mi pairs 55 vs 89 us (three-kernel
-                                                    // passes), 4 Mi 89 vs 105, 8 Mi 135 vs 183 (profiles/r3_narrow_second_digit.txt)
-constexpr size_t kMsd2sMax = (size_t(1) << 28) + (size_t(1) << 22);
-// tile of the look-back passes: TileCfg<uint64_t, 8, 512, 16> = 8192 pairs, TileCfg<uint32_t, 8, 512, 32> = 16384 keys
-constexpr uint32_t msd2s_tile(size_t elem_bytes) { return elem_bytes == 8 ? 8192u : 16384u; }
-
-struct Msd2sLayout {
-    size_t off_mode, off_place, off_cnt, off_off, off_hard, off_coop, off_tickets, off_status_a, off_status_b, off_slab_a, off_slab_b, total;
-    uint32_t pieces, slice, rows_a, rows_b, stride_a, stride_b, tier_b, ticket_words, seg_shift, slots;
-    size_t status_bytes_a, status_bytes_b;
-    bool slab_b_in_tmp;
-};
-
-// slab16: whole u32 keys -- the second slab holds their low 16 bits and, from 16 Mi keys, sits in the caller's n-element scratch
-// array (see Msd2Layout::slab_b_in_tmp)
-// lean: the sub-slabs of the first pass and the segment slabs keep statistical head-room only (mean + 8 sd / + 7.5 sd instead of
-// + 50 %): 64 Mi pairs 1.25 GB of work instead of 1.7.  Evenly spread keys run at the same speed; keys whose density varies by more
-// than a few per cent between neighbouring parts of their range take the safety net.
-Msd2sLayout msd2s_layout(size_t n, size_t elem_bytes = 8, bool slab16 = false, bool lean = false)
-{
-    Msd2sLayout L;
-    const uint32_t kMsd2sTile = msd2s_tile(elem_bytes);
-    // pieces = chains of pass A = sub-slabs per bucket.  16 = twice the number of XCDs: workgroup i runs on XCD i % 8 and takes
-    // chain i % 16, so a chain's tiles stay on ONE XCD -- its status rows and the abutting runs of consecutive tiles meet in
-    // that XCD's L2.  Chain counts that break this measured slower although they make pass B's tiles fuller (64 Mi pairs,
-    // pass A / pass B: 16 chains 0.252 / 0.309 ms, 12 chains 0.282 / 0.325, 18 chains 0.303 / 0.324).  The code below keeps
-    // the choice open (any count up to 24 works).
-    double best = 1e30;
-    for (uint32_t p : {16u}) {
-        const size_t slice = align_up((n + p - 1) / p, kMsd2sTile);
-        const size_t mean = slice / 256;
-        size_t sd = 1;
-        while (sd * sd < mean) ++sd;
-        const size_t stride = align_up(mean + (lean ? 0 : mean / 2) + 8 * sd + 64, 64);   // + 50 %: as much skew as the segment slabs take
-        const double waste = (double)((stride + kMsd2sTile - 1) / kMsd2sTile) * kMsd2sTile / (double)mean;
-        if (waste < best - 1e-9) {
-            best = waste;
-            L.pieces = p;
-            L.slice = (uint32_t)slice;
-            L.stride_a = (uint32_t)stride;
-        }
-    }
-    L.rows_a = L.slice / kMsd2sTile;
-    // the most tiles a bucket can have: pass B's tiles run across the sub-slabs, and a sub-slab holds at most its stride
-    L.rows_b = (uint32_t)(((size_t)L.pieces * L.stride_a + kMsd2sTile - 1) / kMsd2sTile);
-    // (whole u32 keys keep 65536 segments: their second slab holds 16-bit keys only while the finish has 16 bits to sort)
-    L.seg_shift = slab16 ? 8u : msd2_seg_shift(n, false);
-    L.slots = 256u << L.seg_shift;
-    L.stride_b = msd2_stride_b(n, L.slots, slab16, lean);
-    L.tier_b = msd2_tier_b(n, L.slots, slab16);
-    L.ticket_words = (32 + 256) * adlhip::kTicketStride;
-    L.status_bytes_a = (size_t)L.pieces * L.rows_a * 1024;
-    L.status_bytes_b = (size_t)256 * L.rows_b * 1024;
-    L.off_mode = 0;
-    L.off_place = 128;
-    L.off_cnt = 256;
-    L.off_off = L.off_cnt + 65536 * 4;
-    L.off_hard = align_up(L.off_off + 65537 * 4, 256);
-    L.off_coop = L.off_hard + 65536 * 4;
-    L.off_tickets = align_up(L.off_coop + kNetTableBytes, 256);
-    // the regions are sized by bounds that do not depend on `pieces` and grow with n, so that the scratch for n suffices
-    // for every smaller n (adlhip_radix_sort_scratch_bytes): sub-slabs of a bucket together <= n/256 + 16 * (head-room),
-    // rows of pass A <= n/tile + 16, rows of a bucket in pass B <= its sub-slabs / tile + 16
-    size_t sdb = 1;
-    while (sdb * sdb * 4096 < n) ++sdb;   // >= sd of every choice (a sub-slab's mean is at most n / 4096 + 32)
-    const size_t bucket_bound = n / 256 + (lean ? 0 : n / 512) + 24 * (32 + 16 + 8 * (sdb + 1) + 128);
-    const size_t rows_a_bound = n / kMsd2sTile + 24;
-    const size_t rows_b_bound = bucket_bound / kMsd2sTile + 25;
-    L.off_status_a = align_up(L.off_tickets + (size_t)L.ticket_words * 4, 256);
-    L.off_status_b = L.off_status_a + rows_a_bound * 1024;
-    L.off_slab_a = align_up(L.off_status_b + 256 * rows_b_bound * 1024, 256);
-    L.off_slab_b = align_up(L.off_slab_a + 256 * bucket_bound * elem_bytes, 256);
-    const size_t slab_b_bytes = (size_t)L.slots * L.stride_b * (slab16 ? 2 : elem_bytes);
-    L.slab_b_in_tmp = slab16 && n >= kSlabInTmpMin && slab_b_bytes <= n * elem_bytes;
-    L.total = L.off_slab_b + (L.slab_b_in_tmp ? 0 : slab_b_bytes);
-    if ((size_t)L.pieces * L.rows_a > rows_a_bound || L.rows_b > rows_b_bound || (size_t)L.pieces * L.stride_a > bucket_bound)
-        L.total = 0;   // cannot happen; msd2s_sort refuses
-    return L;
-}
-
-// Which sorts take the large sort, and in which form.  keys: the element is the key (u32 / u64 keys), else {key, value} pairs.
-//   whole u32 keys from 96 Mi keys               -> hybrid: stable first pass + cursor-placed second pass (msd2s_sort, hybrid)
-//   whole u64 keys from 48 Mi keys               -> stable passes (msd2s_sort) + binning finish
-//   whole keys below                            -> cursor passes (msd2_sort: smaller fixed cost)
-//   pairs; partial sortBits (>= 16)             -> stable passes (msd2s_sort)
-// "sort.msd2" = 3 / 4 / 5 force the stable / cursor / hybrid form where it applies (tests, A/B measurements).
-enum LargeForm { kLargeNone = 0, kLargeCursor, kLargeStable, kLargeHybrid };
-LargeForm large_sort_form(const adlhip_device* d, size_t elem_bytes, bool keys, size_t n, int sort_bits, int max_bits)
-{
-    if (!(d->sort_algo < 0 && d->msd2_path && d->digit_bits == 8 && d->tile_variant < 0)) return kLargeNone;
-    if (d->resident_wgs < 256) return kLargeNone;   // the safety net's grid barrier spans 256 workgroups
-    if (sort_bits < 16) return kLargeNone;          // two 8-bit digits must fit inside the sorted bits
-    const bool forced = d->msd2_path >= 2;
-    const bool whole = sort_bits == max_bits;
-    // "sort.rank" = 0 (no reliance on the lane order of colliding DS atomics): pairs keep the stable form -- its passes and its
-    // wave-per-segment finish have ballot-ranked variants (tiles up to 2560 pairs: n <= 96 Mi) --, keys take the per-digit passes
-    if (d->rank_mode != 1 && (keys || n > (size_t(96) << 20) || msd2_tier_b(n, 256u << msd2_seg_shift(n, false)) > 2560u)) return kLargeNone;
-    if (!keys) return n > (forced ? kMsd2Min : kMsd2sAutoMin) && n <= kMsd2sMax ? kLargeStable : kLargeNone;
-    // u64 keys have no mid-size sort (it serves 32-bit keys), and with the narrow second digit and the binning finish the large sort
-    // beats their per-digit passes from the one-workgroup sort's limit up: 100 K keys 78 -> 32 us, 1 Mi 117 -> 47, 2 Mi 172 -> 52
-    // (profiles/r3_small_sizes_large_sort_vs_auto.txt)
-    if (n <= (forced || elem_bytes == 8 ? kMsd2Min : kMsd2AutoMin)) return kLargeNone;
-    const size_t cursor_max = elem_bytes == 4 ? kMsd2MaxU32 : kMsd2MaxU64;
-    if (!whole || d->msd2_path == 3) return n <= kMsd2sMax ? kLargeStable : kLargeNone;
-    if (d->msd2_path == 4) return n <= cursor_max ? kLargeCursor : kLargeNone;
-    if (d->msd2_path == 5) return n <= kMsd2sMax ? kLargeHybrid : kLargeNone;
-    // profiles/r3_forms_by_size.txt -- u32 keys: cursor | hybrid 64 Mi 0.424 | 0.423 ms, 128 Mi 0.782 | 0.751, 256 Mi 1.700 | 1.620
-    // (16 Mi: 0.140 | 0.159); u64 keys: cursor | stable 16 Mi 0.294 | 0.312, 64 Mi 0.846 | 0.803, 256 Mi 3.18 | 2.99 (hybrid 2.96)
-    // round 4 (profiles/r4_forms_by_size.txt, persistent cursor passes): u32 keys cursor | hybrid 64 Mi 0.355 | 0.420 ms, 96 Mi 0.559 | 0.585,
-    // 128 Mi 0.688 | 0.743, 256 Mi 1.496 | 1.436 -- the cursor-placed first pass loses ground with n (4.3 TB/s at 64 Mi, 3.4 at 256 Mi)
-    const size_t hybrid_min = d->persist ? (size_t(192) << 20) : (size_t(96) << 20);
-    if (elem_bytes == 4 && n >= hybrid_min && n <= kMsd2sMax) return kLargeHybrid;
-    if (elem_bytes == 8 && n >= (size_t(48) << 20) && n <= kMsd2sMax) return kLargeStable;
-    return n <= cursor_max ? kLargeCursor : kLargeNone;
+        return launch_large_finish<E, E>(d, slab_b, data, nullptr, seg_off, seg_cnt, L.stride_b, L.tier_b, mode, hard, low_max, plan.bin, L.seg_shift);
+    return launch_large_finish<E, S>(d, slab_b, data, nullptr, seg_off, seg_cnt, L.stride_b, L.tier_b, mode, hard, low_max, plan.bin, L.seg_shift);
 }
 
 // The finish of either large sort: the binning finish (whole u64 keys from ~24 Mi up: one counting pass + compares, then the
@@ -1350,15 +1122,6 @@ int launch_large_finish(adlhip_device* d, const E* slab_b, E* out, uint32_t* out
     return launch_wave_segment_sort<E, 80, S, SOA>(d, slab_b, out, seg_off, slots, low_bits_max, seg_cnt, stride_b, mode, lowb, out_vals, nullptr, nullptr, seg_shift);
 }
 
-// whole u64 keys: the binning finish pays from a mean segment of ~384 keys (16 Mi keys: 0.144 vs 0.148 ms, 4 Mi: 0.116 vs 0.098,
-// 64 Mi: 0.263 vs 0.406, profiles/r3_bin_finish.txt)
-bool use_bin_finish(const adlhip_device* d, size_t elem_bytes, bool key64, size_t n, bool whole_keys)
-{
-    if (!whole_keys || !d->bin_finish) return false;
-    if (d->bin_finish == 2) return elem_bytes == 4 || key64;   // forced (tests, A/B): any size, u32 keys too
-    return elem_bytes == 8 && key64 && n >= (size_t(24) << 20);
-}
-
 // The stable large sort.  E / KEY64: uint64_t / false = {key, value} pairs (AoS: data / tmp; SoA: soa_keys != nullptr, the input and
 // output are the two u32 arrays, data / tmp are unused -- the safety net packs the input into the first slab area and sorts it
 // there against the second); uint64_t / true = u64 keys; uint32_t / false = u32 keys (whole keys: the second slab holds their low
@@ -1371,17 +1134,19 @@ bool use_bin_finish(const adlhip_device* d, size_t elem_bytes, bool key64, size_
 // chain's consecutive tiles meet in one XCD's L2: 1.05 x instead of 1.21 x bytes written), second pass 0.124 with cursors vs
 // 0.172 by look-back (profiles/r3_first_ab_cursor_vs_lookback_u32.txt).
 template <typename E, bool KEY64>
-int msd2s_sort(adlhip_device* d, E* data, E* tmp, void* work, size_t n, int sort_bits, uint32_t* soa_keys = nullptr,
-               uint32_t* soa_vals = nullptr, bool hybrid = false, bool lean = false)
+int msd2s_sort(adlhip_device* d, E* data, E* tmp, void* work, size_t n, int sort_bits, const LargePlan& plan, uint32_t* soa_keys = nullptr,
+               uint32_t* soa_vals = nullptr)
 {
+    if (plan.form != kLargeStable && plan.form != kLargeHybrid) return fail("internal: the stable form was handed another form's plan");
+    const bool hybrid = plan.form == kLargeHybrid;
     constexpr int K = sizeof(E) == 8 ? 16 : 32;
     constexpr bool k32 = sizeof(E) == 4;
     constexpr int KEY_BITS = KEY64 ? 64 : 32;
     const bool whole = sort_bits == KEY_BITS;
-    uint32_t* flag = d->d_msd2 + 8192 + 65536;
+    uint32_t* flag = d->d_msd2 + kMsd2Flag;
     uint32_t* done = flag + 1;
     uint32_t* bar = flag + 2;
-    const Msd2sLayout L = msd2s_layout(n, sizeof(E), k32 && whole, lean);
+    const LargeLayout& L = plan.L;
     if (L.total == 0) return fail("internal: layout bounds of the stable large sort");
     char* wb = reinterpret_cast<char*>(work);
     uint32_t* mode = reinterpret_cast<uint32_t*>(wb + L.off_mode);
@@ -1423,12 +1188,12 @@ int msd2s_sort(adlhip_device* d, E* data, E* tmp, void* work, size_t n, int sort
         hipLaunchKernelGGL(kern, dim3(L.pieces * L.rows_a), dim3(512), CT::LDS_BYTES, d->stream, pa);
     });
     if (rc) return rc;
-    const bool slab16 = k32 && whole;   // whole u32 keys: a segment's keys share everything above their low 16 bits
+    const bool slab16 = plan.slab16;    // whole u32 keys: a segment's keys share everything above their low 16 bits
     uint32_t* cur_b = nullptr;
     if constexpr (sizeof(E) == 4 || KEY64) {
         if (hybrid) {
             if (!whole || soa_keys) return fail("internal: the hybrid form sorts whole keys only");
-            cur_b = d->d_msd2 + 8192;   // 65536 cursors [bucket][digit], zero between sorts (the offsets kernel clears them)
+            cur_b = d->d_msd2 + kMsd2CursorsB;   // 65536 cursors [bucket][digit], zero between sorts (the offsets kernel clears them)
             auto kern2 = adlhip::msd_bucket_scatter_kernel<E, 512, K, 3>;
             if (ensure_lds(kern2, CT::LDS_BYTES)) return ADLHIP_FAILURE;
             adlhip::BucketPass<E> pc;
@@ -1481,7 +1246,7 @@ int msd2s_sort(adlhip_device* d, E* data, E* tmp, void* work, size_t n, int sort
     });
     if (rc) return rc;
     const int low_max = sort_bits - 8 - (int)L.seg_shift;
-    const bool bin = use_bin_finish(d, sizeof(E), KEY64, L.seg_shift < 8 ? (size_t(24) << 20) : n, whole);
+    const bool bin = plan.bin;
     if constexpr (k32) {
         if (slab16) return launch_large_finish<E, uint16_t>(d, slab_b, data, nullptr, seg_off, seg_cnt, L.stride_b, L.tier_b, mode, hard, low_max, bin, L.seg_shift);
         return launch_large_finish<E, E>(d, slab_b, data, nullptr, seg_off, seg_cnt, L.stride_b, L.tier_b, mode, hard, low_max, false, L.seg_shift);
@@ -1491,14 +1256,6 @@ int msd2s_sort(adlhip_device* d, E* data, E* tmp, void* work, size_t n, int sort
                                                    hard, low_max, false, L.seg_shift);
         return launch_large_finish<E, E>(d, slab_b, data, nullptr, seg_off, seg_cnt, L.stride_b, L.tier_b, mode, hard, low_max, bin, L.seg_shift);
     }
-}
-
-// what the large sort's form for this sort needs (0: the sort does not take the large sort)
-size_t large_work_bytes(LargeForm form, size_t elem_bytes, size_t n, bool whole)
-{
-    if (form == kLargeCursor) return msd2_layout(n, elem_bytes).total;
-    if (form == kLargeStable || form == kLargeHybrid) return msd2s_layout(n, elem_bytes, elem_bytes == 4 && whole).total;
-    return 0;
 }
 
 // Work bytes with which a sort of n elements on sort_bits bits runs at full speed (level 1), or runs at all (level 0: the
@@ -1515,22 +1272,7 @@ size_t sort_work_bytes_at(const adlhip_device* d, int elem_kind, size_t n, int s
     else if (elem_kind == ADLHIP_ELEM_SOA32) b = onesweep_layout(d, n, max_passes_for(d, 64), buf_tile<SoaBuf>(d, n)).total;
     else b = onesweep_layout(d, n, max_passes_for(d, 64), buf_tile<AosBuf<uint64_t>>(d, n)).total;   // as onesweep_sort<Buf>()
     const size_t c = n <= kMidMaxU32 ? mid_layout(n).total : mid_layout(kMidMaxU32).total;   // mid-size sort (monotone in n)
-    // the large sort: every form this (kind, n, sort_bits) can take, whatever "sort.msd2" says now (the knob may change between
-    // the query and the sort)
-    size_t e = 0;
-    const size_t eb = elem_kind == ADLHIP_ELEM_U32 ? 4 : 8;
-    const int max_bits = elem_kind == ADLHIP_ELEM_U64 ? 64 : 32;
-    const bool whole = sort_bits == max_bits;
-    const bool keys = elem_kind == ADLHIP_ELEM_U32 || elem_kind == ADLHIP_ELEM_U64;
-    if (n > kMsd2Min && sort_bits >= 16) {
-        if (level == 2) {   // lean: whole keys keep the cursor form with little head-room, pairs and partial sorts the stable form
-            if (keys && whole && n <= (eb == 4 ? kMsd2MaxU32 : kMsd2MaxU64)) e = msd2_layout(n, eb, kLeanHeadroomPct).total;
-            else if (n <= kMsd2sMax) e = msd2s_layout(n, eb, eb == 4 && whole, true).total;   // as msd2s_sort (test_gpu_memory_contract.py sweep)
-        } else {
-            if (n <= kMsd2sMax) e = msd2s_layout(n, eb, eb == 4 && whole).total;
-            if (keys && whole && n <= (eb == 4 ? kMsd2MaxU32 : kMsd2MaxU64)) e = std::max(e, msd2_layout(n, eb).total);
-        }
-    }
+    const size_t e = large_work_bytes_at(elem_kind, n, sort_bits, level);   // the large sort (large_plan.hpp)
     return std::max(std::max(a, b), std::max(c, e));
 }
 
@@ -1617,40 +1359,19 @@ int sort_entry(adlhip_device* d, int elem_kind, E* data, E* tmp, void* work, siz
     }
     if (small) return small_sort<E>(d, data, n, plan);
     const bool keys = (int)sizeof(E) * 8 == max_bits;
-    LargeForm form = large_sort_form(d, sizeof(E), keys, n, sort_bits, max_bits);
-    int headroom = kFullHeadroomPct;
-    bool lean_stable = false;
-    if (form != kLargeNone && large_work_bytes(form, sizeof(E), n, sort_bits == max_bits) > work_bytes) {
-        // the slabs do not fit the caller's work buffer: whole keys may still fit the cursor form (its second slab is smaller),
-        // at full head-room or at the lean one (level 2 of adlhip_radix_sort_scratch_bytes_for)
-        const bool whole = sort_bits == max_bits;
-        const bool cursor_ok = keys && whole && n <= (sizeof(E) == 4 ? kMsd2MaxU32 : kMsd2MaxU64);
-        if (cursor_ok && large_work_bytes(kLargeCursor, sizeof(E), n, true) <= work_bytes) {
-            form = kLargeCursor;
-        } else if (cursor_ok && msd2_layout(n, sizeof(E), kLeanHeadroomPct).total <= work_bytes) {
-            form = kLargeCursor;
-            headroom = kLeanHeadroomPct;
-        } else if (n <= kMsd2sMax && msd2s_layout(n, sizeof(E), sizeof(E) == 4 && whole, true).total <= work_bytes) {
-            // (the layout msd2s_sort takes: whole u32 keys have the 16-bit second slab; tests/test_gpu_memory_contract.py in-between sweep)
-            form = kLargeStable;   // pairs, partial sorts: the stable form with statistical head-room only
-            lean_stable = true;
-        } else {
-            form = kLargeNone;
-        }
-    }
+    // the form, its head-room and its layout, by what the caller's work buffer holds (large_plan.hpp)
+    const LargePlan large = large_plan(d, sizeof(E), keys, n, sort_bits, max_bits, work_bytes);
     // The large sort takes every input it is eligible for by size, bits and scratch -- whatever the keys are like: runs that do not fit
     // their slabs are detected on the device and the sort's own offsets kernel then sorts the untouched input (net_sort: counting
     // sort for few distinct values, else LSD passes with grid barriers).  Nothing is reported to the host and nothing is remembered:
     // a handle's first sort of an input takes the time its hundredth does.
-    if (form != kLargeNone) {
-        if (form == kLargeCursor) return msd2_sort<E>(d, data, tmp, work, n, headroom);
-        const bool hybrid = form == kLargeHybrid;
+    if (large.form != kLargeNone) {
+        if (large.form == kLargeCursor) return msd2_sort<E>(d, data, tmp, work, n, large);
         if constexpr (sizeof(E) == 4) {
-            // (lean: whole u32 keys would have taken the cursor form; here the keys are sorted on part of their bits)
-            return msd2s_sort<E, false>(d, data, tmp, work, n, sort_bits, nullptr, nullptr, hybrid, lean_stable);
+            return msd2s_sort<E, false>(d, data, tmp, work, n, sort_bits, large);
         } else {
-            if (keys) return msd2s_sort<E, true>(d, data, tmp, work, n, sort_bits, nullptr, nullptr, hybrid, lean_stable);
-            return msd2s_sort<E, false>(d, data, tmp, work, n, sort_bits, nullptr, nullptr, false, lean_stable);
+            if (keys) return msd2s_sort<E, true>(d, data, tmp, work, n, sort_bits, large);
+            return msd2s_sort<E, false>(d, data, tmp, work, n, sort_bits, large);
         }
     }
     return run_sort<AosBuf<E>>(d, AosBuf<E>{data}, AosBuf<E>{tmp}, work, work_bytes, n, plan);
@@ -2003,12 +1724,8 @@ int adlhip_radix_sort_soa32(adlhip_device* d, uint32_t* keys, uint32_t* vals, ui
     if (!vals || !tmp_vals) return fail("null value buffer passed to radix sort");
     if ((reinterpret_cast<uintptr_t>(vals) | reinterpret_cast<uintptr_t>(tmp_vals)) & 15u)
         return fail("sort buffers must be 16-byte aligned");
-    if (large_sort_form(d, 8, false, n, sort_bits, 32) != kLargeNone) {
-        if (large_work_bytes(kLargeStable, 8, n, sort_bits == 32) <= work_bytes)
-            return msd2s_sort<uint64_t, false>(d, nullptr, nullptr, work, n, sort_bits, keys, vals);
-        if (msd2s_layout(n, 8, false, true).total <= work_bytes)   // level 2, lean
-            return msd2s_sort<uint64_t, false>(d, nullptr, nullptr, work, n, sort_bits, keys, vals, false, true);
-    }
+    const LargePlan large = large_plan(d, 8, /*keys=*/false, n, sort_bits, 32, work_bytes);   // pairs: the stable form, full or lean
+    if (large.form != kLargeNone) return msd2s_sort<uint64_t, false>(d, nullptr, nullptr, work, n, sort_bits, large, keys, vals);
     const std::vector<PassPlan> plan = plan_passes(sort_bits, d->digit_bits);
     return run_sort<SoaBuf>(d, SoaBuf{keys, vals}, SoaBuf{tmp_keys, tmp_vals}, work, work_bytes, n, plan);
 }

@@ -5,7 +5,7 @@ computes from n: pass-1 bucket slabs (or per-chain sub-slabs), segment slabs and
 raises a flag and the safety net re-sorts the untouched input -- correct, 3-4x slower, and visible only in "stat.net_runs".
 Random keys stay far below those edges, so here every targeted region is filled to exactly cap - 1, cap and cap + 1 keys.
 
-A Python mirror of the host's capacities (below, with the source it restates) predicts each run's outcome: the result is
+A Python mirror of the host's capacities (tests/large_plan.py and below, with the source it restates) predicts each run's outcome: the result is
 bit-exact against the oracle, the safety net runs exactly when some region overflows, the kernels that ran are the form and
 finish the case claims, and the device fault word stays clean.
 """
@@ -19,118 +19,21 @@ import oracle
 from oclradixsort_amd import DeviceUtils, Buffer, _lib
 from oclradixsort_amd._lib import check
 
-MI = 1 << 20
-U32, KV32, U64, SOA32 = 0, 1, 2, 3   # ADLHIP_ELEM_*
+from large_plan import KV32, LEAN_PCT, MI, SOA32, U32, U64, large_sort_form, msd2_layout, msd2s_layout
 
 
 # ---------------------------------------------------------------------------------------------
-# mirror of the host's capacities (oclradixsort_amd/csrc/adlhip.hip)
+# mirror of the host's capacities: the large sort's is tests/large_plan.py (oclradixsort_amd/csrc/large_plan.hpp)
 # ---------------------------------------------------------------------------------------------
-FULL_PCT, LEAN_PCT = 50, 12   # kFullHeadroomPct, kLeanHeadroomPct (adlhip.hip)
-STRIDE0 = 1536                # kMsd2Stride0 (adlhip.hip)
-
-
-def _align_up(x, a):
-    return (x + a - 1) // a * a
-
-
-def _sd(mean):
-    """the host's integer standard deviation: the smallest sd >= 1 with sd * sd >= mean"""
-    sd = 1
-    while sd * sd < mean:
-        sd += 1
-    return sd
-
-
-def msd2_tier_b(n, slots=65536, fine=False):
-    """adlhip.hip msd2_tier_b: the finish's tile that holds the mean segment + 7.5 sd"""
-    mean = (n + slots - 1) // slots
-    need = mean + (15 * _sd(mean) + 1) // 2
-    if fine and 2560 < need <= 4096:
-        return 3072 if need <= 3072 else 4096
-    if need <= 5120:
-        return 1280 if need <= 832 else STRIDE0 if need <= 1280 else 2560 if need <= 2560 else 5120
-    return 8192 if need <= 8192 else 12288 if need <= 12288 else 16384 if need <= 16384 else 20480
-
-
-def msd2_stride_b(n, slots=65536, fine=False, lean=False):
-    """adlhip.hip msd2_stride_b: mean + 50 % (lean: the mean), or mean + 7.5 sd where that is more, + 8, in steps of 64,
-    at most the tile"""
-    mean = (n + slots - 1) // slots
-    want = _align_up(max(mean if lean else mean + mean // 2, mean + (15 * _sd(mean) + 1) // 2) + 8, 64)
-    return min(want, msd2_tier_b(n, slots, fine))
-
-
-def msd2_seg_shift(n, bin_finish):
-    """adlhip.hip msd2_seg_shift: width w of the second digit (256 << w segments)"""
-    max_n = (1 << 40) if bin_finish else (16 << 20)
-    if n >= max_n:
-        return 8
-    w = 2
-    while w < 8 and (n >> (8 + w)) > 1024:
-        w += 1
-    return w
-
-
-def msd2_layout(n, elem_bytes, headroom_pct=FULL_PCT):
-    """adlhip.hip msd2_layout (cursor form): bucket slab stride_a, segment slabs stride_b, finish tile tier_b"""
-    w = msd2_seg_shift(n, elem_bytes == 8)
-    fine = elem_bytes == 4 and w == 8
-    return dict(stride_a=_align_up(n // 256 + (n // 256) * headroom_pct // 100 + 4096, 64), seg_shift=w,
-                stride_b=msd2_stride_b(n, 256 << w, fine), tier_b=msd2_tier_b(n, 256 << w, fine))
-
-
-def msd2s_layout(n, elem_bytes=8, slab16=False, lean=False):
-    """adlhip.hip msd2s_layout (stable and hybrid forms): 16 chains, each a slice of the input; one sub-slab of stride_a per
-    (bucket, chain); slab16 = whole u32 keys (65536 segments, 16-bit second slab)"""
-    tile = 8192 if elem_bytes == 8 else 16384   # msd2s_tile (adlhip.hip)
-    pieces = 16
-    slice_ = _align_up((n + pieces - 1) // pieces, tile)
-    mean = slice_ // 256
-    w = 8 if slab16 else msd2_seg_shift(n, False)
-    return dict(pieces=pieces, slice=slice_, stride_a=_align_up(mean + (0 if lean else mean // 2) + 8 * _sd(mean) + 64, 64),
-                seg_shift=w, stride_b=msd2_stride_b(n, 256 << w, slab16, lean), tier_b=msd2_tier_b(n, 256 << w, slab16))
-
-
 def mid_stride(n):
     """adlhip.hip mid_layout().stride: the mid-size sort's bucket slab (= its LDS tile; adlhip.hip mid_sort uses the same cap)"""
     return 4096 if n <= (512 << 10) else 8192 if n <= MI else 16384
 
 
-def large_sort_form(kind, n, sort_bits, knob, rank=1, persist=1):
-    """adlhip.hip large_sort_form: 'cursor' / 'stable' / 'hybrid' / None for a sort of n elements of `kind` with the
-    "sort.msd2" knob (default device: 8-bit digits, automatic algorithm, at least 256 resident workgroups)"""
-    if knob == 0 or sort_bits < 16:
-        return None
-    elem_bytes = 4 if kind == U32 else 8
-    max_bits = 64 if kind == U64 else 32
-    keys = kind in (U32, U64)
-    forced, whole = knob >= 2, sort_bits == max_bits
-    if rank != 1 and (keys or n > (96 << 20) or msd2_tier_b(n, 256 << msd2_seg_shift(n, False)) > 2560):
-        return None
-    if not keys:
-        return "stable" if (n > (16384 if forced else MI)) and n <= (1 << 28) + (1 << 22) else None
-    if n <= (16384 if forced or elem_bytes == 8 else 2 * MI):
-        return None
-    cursor_max = (1088 << 20) if elem_bytes == 4 else (1 << 28) + (1 << 22)
-    stable_max = (1 << 28) + (1 << 22)
-    if not whole or knob == 3:
-        return "stable" if n <= stable_max else None
-    if knob == 4:
-        return "cursor" if n <= cursor_max else None
-    if knob == 5:
-        return "hybrid" if n <= stable_max else None
-    if elem_bytes == 4 and (192 << 20 if persist else 96 << 20) <= n <= stable_max:
-        return "hybrid"
-    if elem_bytes == 8 and (48 << 20) <= n <= stable_max:
-        return "stable"
-    return "cursor" if n <= cursor_max else None
-
-
 def finish_names(kind, form, w, tier_b, whole=True):
     """The finish's launches (adlhip.hip launch_large_finish, default knobs): the workgroup-per-segment finish for whole u32
     keys with 65536 segments and a tile of 3072 and more (or beyond 5120), the binning finish + its listed hand-over for whole
-    u64 keys (adlhip.hip use_bin_finish: n >= 24 Mi, or any n with a narrow second digit), else the wave LSD finish
+    u64 keys (large_plan.hpp use_bin_finish: n >= 24 Mi, or any n with a narrow second digit), else the wave LSD finish
     (wave_finish16_kernel for the 16-bit second slab, 1280 / 1536 / 2560)."""
     if kind == U32:
         return {"segment_sort_wg_u32"} if (tier_b > 5120 or (whole and w == 8 and tier_b >= 3072)) else {"segment_sort_wave_u32"}

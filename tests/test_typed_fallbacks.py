@@ -36,7 +36,8 @@ def refused(config, labels, sorts, net_delta=(0, 0)):
 
 
 def test_the_constants_are_those_of_the_library():
-    src = (ROOT / "oclradixsort_amd" / "csrc" / "adlhip.hip").read_text()
+    csrc = ROOT / "oclradixsort_amd" / "csrc"   # the large sort's limits, and kSmallMax with them, are large_plan.hpp's
+    src = (csrc / "adlhip.hip").read_text() + (csrc / "large_plan.hpp").read_text()
 
     def const(name):
         m = re.search(r"constexpr size_t %s = ([^;]+);" % name, src)

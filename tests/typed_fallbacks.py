@@ -5,7 +5,7 @@ tests/test_typed_fallbacks.py checks this module on the CPU, tests/test_gpu_type
 Nine typed entry points run the unsigned radix sort beneath them (primitives.hip: sort_elements, typed_index_sort,
 adlhip_radix_sort_soa32).  The library leaves the configuration an unpartitioned MI355X picks by itself in two cases -- a partition
 that cannot keep 256 workgroups resident, a device whose LDS-order self-test failed -- and the user can leave it through "sort.algo"
-and "sort.digit_bits".  CONFIGS names the five configurations; the constants are those of adlhip.hip.
+and "sort.digit_bits".  CONFIGS names the five configurations; the constants are those of adlhip.hip and large_plan.hpp.
 
 The inner sorts of one call are described by Sort(kind, n): kind "pairs" is the stable {key dword, index} pair sort of
 typed_index_sort, "keys32" / "keys64" the whole-key sort of adlhip_sort_keys_typed, "positions" the u32 sort of the k positions the
@@ -17,7 +17,7 @@ from collections import namedtuple
 
 import numpy as np
 
-# adlhip.hip
+# adlhip.hip, large_plan.hpp
 SMALL_MAX = 16384                 # kSmallMax: one workgroup sorts up to here
 MID_MIN_U32 = 8192                # kMidMinU32
 MID_MAX_E64 = 1 << 20             # kMidMaxE64 = kMsd2sAutoMin: pairs leave the mid-size form for the large stable form above
